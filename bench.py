@@ -14,14 +14,23 @@ One "step" = one pass of the hot path over one batch of synthetic input:
   (b) one PPO minibatch update of 50,000 samples drawn from the device-resident rollout buffer: fused gather,
       actor_ft + critic forward, loss, backward, [gradient all-reduce over ranks], AdamW on both networks and
       re-packing of the updated weights for the next step.
-Each timed region is EXACTLY `steps` steps bracketed by barrier + torch.cuda.synchronize(), MAX over ranks.  The update leg
-is timed `--passes` (10) times over, each pass its own bracketed region of the same `steps` steps: `value` / `ms_per_step`
-are the MEDIAN pass, min / max are reported beside it (`passes`), so the number survives a noisy neighbour or a slow clock
-ramp.  The sampler (a 0.06 ms call) runs ten passes of its `steps` calls inside one region.  After the `warmup` steps and
-before the first timed region of a leg `--spin-up` (default 300, reported as `spin_up`) more untimed calls bring the GPU's
-clocks up (same count on every rank).
-`value` is the headline the north star puts the target on -- PPO-update samples/s, whole job -- and the sampler's
-env-steps/s is reported beside it (BASELINE.json's metric names both).  Weak scaling: per-GPU load is fixed.
+`value` is the headline the north star puts the target on -- PPO-update samples/s, whole job -- and `ms_per_step` the
+milliseconds of one update step.  Weak scaling: per-GPU load is fixed.
+
+A plain run measures the headline and nothing else: set-up, `warmup` update steps, `--spin-up` (default 300, reported as
+`spin_up`) more untimed update steps that bring the GPU's clocks up (same count on every rank), then ONE timed region of
+EXACTLY `steps` update steps bracketed by barrier + torch.cuda.synchronize(), MAX over ranks; ms_per_step = region / steps.
+
+`--full` adds everything else the benchmark measures.  The update leg is then timed `--passes` (10) times over, each pass
+its own bracketed region of the same `steps` steps: `value` / `ms_per_step` are the MEDIAN pass, min / max are reported
+beside it (`passes`), so the number survives a noisy neighbour or a slow clock ramp.  The sampler leg (a 0.06 ms call) runs
+ten passes of its `steps` calls inside one region and is reported as env-steps/s beside the headline (BASELINE.json's metric
+names both), after its own `warmup` and `spin_up` calls.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed update step computed -- the stats vector that
+ppo_update returns (stats.npy, float64), both networks' flat gradients (actor_ft_grads.npy, critic_grads.npy) and their
+flat weights after the AdamW step (actor_ft_params.npy, critic_params.npy), float32, rank 0's.  Every input is seeded, so
+two builds run with the same arguments can be compared output for output.
 
 Synthetic data (seed 42): random-init networks of the reference architecture, obs ~ U(-1,1),
 N(0,1) noise clipped at +-3, the rollout buffer is the sampler's own chains over 500 obs batches, rewards ~ N(0,1),
@@ -29,10 +38,11 @@ terminated ~ Bernoulli(0.002), values from the random critic.
 
 The line also carries
   `roofline`     SURVEY.md 8(d)'s figure: the update path's algorithmic FLOP rate (samples/s x 4.11 MFLOP) against the
-                 dense MFMA peak of the operand dtype, the sampler's (chunks/s x 22.06 MFLOP) beside it, and as
+                 dense MFMA peak of the operand dtype; with --full the sampler's (chunks/s x 22.06 MFLOP) beside it, and as
                  `dominant_kernel` the largest kernel of the step (`gemm_tn_group_kernel`: every weight gradient of one
                  network's backward pass in one launch) timed live with HIP events on its launch stream: its operand
-                 bytes per second against the HBM peak and its own MFMA fraction;
+                 bytes per second against the HBM peak and its own MFMA fraction.
+and with --full
   `fp32`         the same two legs with fp32 operands (the reference's arithmetic), secondary;
   `configs`      BASELINE configs[2] (robomimic can, K=100 DDPM, Ta=8, 256 envs, minibatch 7,500) and one GPU's share of
                  configs[3] (halfcheetah, 512 envs, minibatch 50,000): the same two legs, each with its 8(d)-style fraction;
@@ -100,9 +110,14 @@ def parse_args(argv=None):
     ap.add_argument("--n-envs", type=int, default=512)
     ap.add_argument("--n-steps", type=int, default=500, help="rollout length behind the update buffer")
     ap.add_argument("--batch", type=int, default=50000)
-    ap.add_argument("--passes", type=int, default=10,
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline: sampler leg, median of --passes, roofline probe pass, "
+                         "all-reduce alone, fp32, other configs, pixel path, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed update step computed to DIR/<name>.npy")
+    ap.add_argument("--passes", type=int, default=None,
                     help="timed passes of the update leg, each its own barrier-bracketed region of exactly --steps steps; the "
-                         "line reports the median pass (min / max beside it)")
+                         "line reports the median pass (min / max beside it).  Default 1, with --full 10")
     ap.add_argument("--spin-up", type=int, default=300,
                     help="untimed calls in front of each leg's first timed region, beyond --warmup, so that the GPU's clocks have ramped")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -116,7 +131,7 @@ def parse_args(argv=None):
                     help="N > 1: gradient bucket all-reduced in two slices, the critic's overlapped with the actor's backward "
                          "(default), or in one piece behind the update")
     ap.add_argument("--probe", type=int, default=2,
-                    help="kernel timed live for `roofline.dominant_kernel`: 2 gemm_tn (weight grads), 3 fused fwd, "
+                    help="kernel timed live for `roofline.dominant_kernel` (--full): 2 gemm_tn (weight grads), 3 fused fwd, "
                          "4 fused bwd, 5 sampler")
     ap.add_argument("--graph", action="store_true",
                     help="replay the update step as captured hipGraphs (dppo_amd.util.graphed) instead of issuing its "
@@ -127,7 +142,10 @@ def parse_args(argv=None):
     # test hooks of the launcher path (tests/test_bench_launcher.py): ranks rendezvous over gloo on the CPU, report and exit
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-check-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.passes is None:
+        args.passes = 10 if args.full else 1
+    return args
 
 
 def launch_ranks(args, argv):
@@ -359,7 +377,7 @@ def main(argv=None):
     import ctypes as C
     import statistics
 
-    import numpy as np  # noqa: F401
+    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -402,10 +420,11 @@ def main(argv=None):
             dt = float(t.item())
         return dt
 
-    def run_path(prec, nranks, probe_id, wl, n_envs, n_steps, batch, passes):
-        """Both legs of a step at one operand precision: `steps` sampling calls and `steps` update steps, each timed
-        between barriers (+ the serial roofline pass of the update when `probe_id` is set).  nranks = 1 runs the path
-        rank-locally (no collective): the secondary passes."""
+    def run_path(prec, nranks, probe_id, wl, n_envs, n_steps, batch, passes, dump=None):
+        """The update leg at one operand precision, `steps` update steps timed between barriers; with --full also the
+        sampler leg (`steps` sampling calls) and the serial roofline pass of the update when `probe_id` is set.  nranks = 1
+        runs the path rank-locally (no collective): the secondary passes.  `dump` (a dict) receives host copies of what the
+        last timed update step computed."""
         KFT, K = wl["kft"], wl["K"]
         model = build_model(str(device), prec, wl)  # same seed on every rank => identical initial weights
         gen = torch.Generator(device=device).manual_seed(42 + rank)  # env shards differ per rank
@@ -490,20 +509,28 @@ def main(argv=None):
                 dp.split = False
                 dp._critic_done = False
             r["dp_mode"] = "two slices (critic slice overlapped from inside the update call)" if dp.split else "one bucket"
-        # the sampler leg (secondary): a call is ~0.07 ms, so `steps` calls are timed ten times over in one region (1.4 ms of
-        # work gave 26-30 M env-steps/s from run to run); with the per-launch probe on it stays at one pass
-        probe_sampler = rank == 0 and probe_id == 5
-        r["dt_sample"] = timed(sample_step, probe=probe_sampler, reps=1 if probe_id == 5 else 10)[0]
+        # the sampler leg (secondary, --full): a call is ~0.07 ms, so `steps` calls are timed ten times over in one region
+        # (1.4 ms of work gave 26-30 M env-steps/s from run to run); with the per-launch probe on it stays at one pass
+        r["dt_sample"] = None
+        if args.full:
+            probe_sampler = rank == 0 and probe_id == 5
+            r["dt_sample"] = timed(sample_step, probe=probe_sampler, reps=1 if probe_id == 5 else 10)[0]
         r["dt_update_passes"] = timed(update_step, passes=passes)
         r["dt_update"] = statistics.median(r["dt_update_passes"])
+        if dump is not None:  # before any later pass moves the weights on
+            dump.update(stats=model._stats.cpu().numpy(),
+                        actor_ft_grads=model.actor_ft.flat_grads().cpu().numpy(),
+                        critic_grads=model.critic.flat_grads().cpu().numpy(),
+                        actor_ft_params=model.actor_ft.flat_params().cpu().numpy(),
+                        critic_params=model.critic.flat_params().cpu().numpy())
         # the collective alone, same bucket, same `steps`: lets an N-GPU run be read as compute + all-reduce
-        r["dt_allreduce"] = timed(allreduce_only)[0] if nranks > 1 else None
-        # Roofline pass: the same update steps once more with the library's side streams off (knob 2 = 0).  In the timed
-        # region above the critic half and the gradient tails run beside the probed kernel, so an event-bracketed launch
+        r["dt_allreduce"] = timed(allreduce_only)[0] if nranks > 1 and args.full else None
+        # Roofline pass (--full): the same update steps once more with the library's side streams off (knob 2 = 0).  In the
+        # timed region above the critic half and the gradient tails run beside the probed kernel, so an event-bracketed launch
         # duration there includes its co-runners' share of the chip; serial, it is the kernel's own (rocprofv3 on
         # `bench.py --tune 2=0` reports the same average).  `value` always comes from the default (overlapped) pass.
         r["dt_serial"] = None
-        if probe_id not in (None, 5):
+        if args.full and probe_id not in (None, 5):
             overlap = next((int(kv.split("=")[1]) for kv in args.tune if kv.split("=")[0] == "2"), 1)
             hip.check(lib.dppo_tune_set(2, 0), "dppo_tune_set")
             eager[0] = True
@@ -515,7 +542,7 @@ def main(argv=None):
         # ... and what of it the step actually waits for: the same update steps with the collectives skipped (gradients stay
         # rank-local: timing only, run last on a throw-away model state) -- exposed = step - step_without
         r["dt_update_nocomm"] = None
-        if nranks > 1:
+        if nranks > 1 and args.full:
             dp.skip_collectives = True
             r["dt_update_nocomm"] = statistics.median(timed(update_step, passes=max(3, passes // 2)))
             dp.skip_collectives = False
@@ -529,12 +556,17 @@ def main(argv=None):
     WL = WORKLOADS["hopper"]
     ACT_STEPS = WL["act_steps"]
     FLOP_PER_SAMPLE, FLOP_PER_CHUNK = flop_per_sample(WL), flop_per_chunk(WL)  # 4.11 MFLOP, 22.06 MFLOP
-    main_run = run_path(args.prec, world, args.probe, WL, args.n_envs, args.n_steps, args.batch, args.passes)
+    dump = {} if args.dump_outputs and rank == 0 else None
+    main_run = run_path(args.prec, world, args.probe, WL, args.n_envs, args.n_steps, args.batch, args.passes, dump)
     model = main_run["model"]
     dt_sample, dt_update, dt_serial = main_run["dt_sample"], main_run["dt_update"], main_run["dt_serial"]
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
     kernel_probe = None  # the dominant kernel of the update, timed live with HIP events on its launch stream
-    if rank == 0:
+    if rank == 0 and args.full:
         ms, cnt, fl, nb_lib = C.c_double(), C.c_int(), C.c_double(), C.c_double()
         hip.check(lib.dppo_probe_collect_bytes(C.byref(ms), C.byref(cnt), C.byref(fl), C.byref(nb_lib)),
                   "dppo_probe_collect_bytes")
@@ -578,13 +610,14 @@ def main(argv=None):
     torch.cuda.empty_cache()
 
     fp32_run = None
-    if world == 1 and args.prec != "fp32" and not args.no_fp32:  # the reference's own arithmetic, same steps, same shapes
+    # the reference's own arithmetic, same steps, same shapes
+    if args.full and world == 1 and args.prec != "fp32" and not args.no_fp32:
         fp32_run = run_path("fp32", 1, None, WL, args.n_envs, args.n_steps, args.batch, 3)
         del fp32_run["model"]
         torch.cuda.empty_cache()
 
     other = None  # BASELINE configs[2] and one GPU's share of configs[3]: same legs, same clocks, secondary
-    if world == 1 and not args.no_configs:
+    if args.full and world == 1 and not args.no_configs:
         other = {}
         for key, name in (("C3_can", "can"), ("C4_halfcheetah_per_gpu", "halfcheetah")):
             wl = WORKLOADS[name]
@@ -602,29 +635,20 @@ def main(argv=None):
                           "sampler_frac": cps * flop_per_chunk(wl) / 1e12 / peak}
 
     pixel = None
-    if world == 1 and args.prec == "bf16" and not args.no_pixel:
+    if args.full and world == 1 and args.prec == "bf16" and not args.no_pixel:
         pixel = pixel_leg()
         torch.cuda.empty_cache()
 
     stats = main_run["stats"]
     if rank == 0:
         ms_update = dt_update / args.steps * 1e3
-        ms_sample = dt_sample / args.steps * 1e3
         samples_per_s = args.batch * world / (dt_update / args.steps)
-        chunks_per_s = args.n_envs * world / (dt_sample / args.steps)
-        env_steps_per_s = chunks_per_s * ACT_STEPS
         peak_tf = MFMA_PEAK_TFLOPS[args.prec] * world
-        upd_tf, smp_tf = samples_per_s * FLOP_PER_SAMPLE / 1e12, chunks_per_s * FLOP_PER_CHUNK / 1e12
+        upd_tf = samples_per_s * FLOP_PER_SAMPLE / 1e12
         # the path is MFMA-bound (20 kFLOP per algorithmic byte); achieved = units/s x algorithmic FLOP per
         # unit (necessary network evaluations only), priced against the dense MFMA peak of the operand dtype.
         roofline = {"bound": "mfma", "achieved": upd_tf, "peak": peak_tf, "unit": "TFLOP/s", "frac": upd_tf / peak_tf,
-                    "traffic": None if kernel_probe is None else kernel_probe["traffic"],
-                    "what": "PPO update path: samples/s x 4.11 MFLOP per sample (SURVEY 8d) / dense MFMA peak of the dtype",
-                    "sampler": {"achieved": smp_tf, "frac": smp_tf / peak_tf,
-                                "what": "chunks/s x 22.06 MFLOP per action chunk / the same peak"},
-                    "dominant_kernel": kernel_probe,
-                    "traffic_is": "HBM bytes per launch of dominant_kernel (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE)"}
-        ar_ms = None if main_run["dt_allreduce"] is None else main_run["dt_allreduce"] / args.steps * 1e3
+                    "what": "PPO update path: samples/s x 4.11 MFLOP per sample (SURVEY 8d) / dense MFMA peak of the dtype"}
         out = {
             "metric": "PPO-update samples/sec (+ env-steps/sec of the K=20 sampler), hopper K=20 n_envs=512",
             "value": samples_per_s, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -636,15 +660,28 @@ def main(argv=None):
                        "n_envs_per_gpu": args.n_envs, "minibatch_per_gpu": args.batch,
                        "rollout_rows_per_gpu": args.n_envs * args.n_steps,
                        "parallelism": f"dp{world} (env-sharded, RCCL grad all-reduce)"},
-            "env_steps_per_sec": env_steps_per_s, "sampler_ms_per_call": ms_sample, "chunks_per_sec": chunks_per_s,
-            "allreduce_ms": ar_ms, "dp_mode": main_run.get("dp_mode"),
-            "allreduce_exposed_ms": None if main_run.get("dt_update_nocomm") is None else
-            (dt_update - main_run["dt_update_nocomm"]) / args.steps * 1e3,
-            "allreduce_is": "gradient bucket [critic | actor | stats] SUM-reduced in two slices; allreduce_ms = both alone, "
-                            "allreduce_exposed_ms = ms_per_step minus the same step with the collectives skipped",
+            "dp_mode": main_run.get("dp_mode"),
             "last_stats": {"pg_loss": stats[0], "v_loss": stats[1], "approx_kl": stats[2], "ratio": stats[4]},
             "roofline": roofline,
         }
+        if args.full:
+            ms_sample = dt_sample / args.steps * 1e3
+            chunks_per_s = args.n_envs * world / (dt_sample / args.steps)
+            smp_tf = chunks_per_s * FLOP_PER_CHUNK / 1e12
+            roofline.update({"traffic": None if kernel_probe is None else kernel_probe["traffic"],
+                             "sampler": {"achieved": smp_tf, "frac": smp_tf / peak_tf,
+                                         "what": "chunks/s x 22.06 MFLOP per action chunk / the same peak"},
+                             "dominant_kernel": kernel_probe,
+                             "traffic_is": "HBM bytes per launch of dominant_kernel "
+                                           "(rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE)"})
+            ar_ms = None if main_run["dt_allreduce"] is None else main_run["dt_allreduce"] / args.steps * 1e3
+            out.update({
+                "env_steps_per_sec": chunks_per_s * ACT_STEPS, "sampler_ms_per_call": ms_sample, "chunks_per_sec": chunks_per_s,
+                "allreduce_ms": ar_ms,
+                "allreduce_exposed_ms": None if main_run.get("dt_update_nocomm") is None else
+                (dt_update - main_run["dt_update_nocomm"]) / args.steps * 1e3,
+                "allreduce_is": "gradient bucket [critic | actor | stats] SUM-reduced in two slices; allreduce_ms = both alone, "
+                                "allreduce_exposed_ms = ms_per_step minus the same step with the collectives skipped"})
         if fp32_run is not None:
             f_sps = args.batch / (fp32_run["dt_update"] / args.steps)
             f_cps = args.n_envs / (fp32_run["dt_sample"] / args.steps)
@@ -658,7 +695,7 @@ def main(argv=None):
             out["configs"] = other
         if pixel is not None:
             out["pixel"] = pixel
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.n_envs, args.batch)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -70,6 +70,15 @@ def test_launcher_never_imports_torch_in_the_parent():
     assert names <= {"argparse", "json", "os", "socket", "subprocess", "sys", "time"}, names
 
 
+def test_plain_run_times_one_pass_and_full_keeps_the_median_of_ten():
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert plain.passes == 1 and not plain.full and plain.dump_outputs is None
+    assert bench.parse_args(["--full"]).passes == 10
+    assert bench.parse_args(["--full", "--passes", "3", "--dump-outputs", "d"]).passes == 3
+
+
 @pytest.mark.parametrize("name,mflop", [("hopper", 4.11), ("can", 4.44), ("halfcheetah", 4.21)])
 def test_flop_counts_follow_survey_8d(name, mflop):
     sys.path.insert(0, ROOT)

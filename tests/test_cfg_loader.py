@@ -1,6 +1,7 @@
 """The YAML surface: a cfg written in the reference's style (same keys as
 cfg/gym/finetune/hopper-v2/ft_ppo_diffusion_mlp.yaml, typed in here -- not a copy of the file) resolves and
 instantiates the dppo_amd classes through `_target_` strings that still name the reference package."""
+import fnmatch
 import os
 import textwrap
 
@@ -94,25 +95,26 @@ def test_targets_map_onto_this_package(tmp_path, monkeypatch):
     assert get_class(cfg._target_).__name__ == "TrainPPODiffusionAgent"
 
 
-REF_CFG = "/root/reference/dppo/cfg"
+SHIPPED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shipped_cfgs.json")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference checkout not present (GPU box)")
+def shipped(pattern):
+    """(path, cfg) of every cfg the reference ships whose path under cfg/ matches `pattern`: tests/golden/shipped_cfgs.json
+    holds each one as the loader resolved it (device=cpu except for ft_ppo_diffusion_mlp.yaml; make_cfg_fixture.py)."""
+    cfgs = load_config(SHIPPED)
+    return [(p, cfgs[p]) for p in sorted(cfgs) if fnmatch.fnmatch(p, pattern)]
+
+
 def test_every_shipped_diffusion_mlp_cfg_builds():
     """Each ft_ppo_diffusion_mlp.yaml the reference ships resolves through the loader, its actor / critic build as
     dppo_amd containers, and the C ABI accepts both descriptors (parameter count == the containers' flat size)."""
     import ctypes as C
-    import glob
 
     from dppo_amd import hip
-    os.environ.setdefault("DPPO_LOG_DIR", "/tmp/log")
-    os.environ.setdefault("DPPO_DATA_DIR", "/tmp/data")
-    os.environ.setdefault("DPPO_WANDB_ENTITY", "none")
-    paths = sorted(glob.glob(os.path.join(REF_CFG, "*", "finetune", "*", "ft_ppo_diffusion_mlp.yaml")))
-    assert len(paths) >= 19
+    cfgs = shipped("*/finetune/*/ft_ppo_diffusion_mlp.yaml")
+    assert len(cfgs) >= 19
     lib = hip.load()
-    for p in paths:
-        cfg = load_config(p)
+    for p, cfg in cfgs:
         actor = instantiate(cfg.model.actor)
         critic = instantiate(cfg.model.critic)
         for net in (actor, critic):
@@ -122,54 +124,42 @@ def test_every_shipped_diffusion_mlp_cfg_builds():
                 assert lib.dppo_packed_bytes(C.byref(net.net_desc()), prec, int(cfg.denoising_steps)) > 0, p
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference checkout not present (GPU box)")
 def test_every_shipped_pretraining_cfg_builds():
     """Each pre_diffusion_mlp.yaml the reference ships resolves, maps onto dppo_amd's pre-training agent and model, and
     its network is one the C ABI accepts (the supervised loss runs on the update's kernels)."""
     import ctypes as C
-    import glob
 
     from dppo_amd import hip
     from dppo_amd.agent.pretrain.train_diffusion_agent import TrainDiffusionAgent
     from dppo_amd.model.diffusion.diffusion import DiffusionModel
-    os.environ.setdefault("DPPO_LOG_DIR", "/tmp/log")
-    os.environ.setdefault("DPPO_DATA_DIR", "/tmp/data")
-    os.environ.setdefault("DPPO_WANDB_ENTITY", "none")
-    paths = sorted(glob.glob(os.path.join(REF_CFG, "*", "pretrain", "*", "pre_diffusion_mlp.yaml")))
-    assert len(paths) >= 19
+    cfgs = shipped("*/pretrain/*/pre_diffusion_mlp.yaml")
+    assert len(cfgs) >= 19
     lib = hip.load()
     built = 0
-    for p in paths:
-        cfg = load_config(p, overrides=["device=cpu"])
+    for p, cfg in cfgs:
         assert get_class(cfg._target_) is TrainDiffusionAgent, p
         assert get_class(cfg.model._target_) is DiffusionModel, p
         net = instantiate(cfg.model.network)
         assert lib.dppo_net_param_count(C.byref(net.net_desc())) == net.flat_params().numel(), (p, hip.last_error())
         assert cfg.train.batch_size >= 1 and cfg.ema.decay < 1
         built += 1
-    assert built == len(paths)
+    assert built == len(cfgs)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference checkout not present (GPU box)")
 def test_every_shipped_state_unet_gaussian_and_eval_cfg_builds():
     """Round 2's rows through the same loader: every ft_ppo_diffusion_unet.yaml / pre_diffusion_unet.yaml (conv actor: model
     builds on CPU, state-dict order = the C ABI's flat layout), every ft_ppo_gaussian_mlp.yaml with a fixed-std residual trunk,
     and every eval_diffusion_{mlp,unet}.yaml's model target (DiffusionEval, incl. the `diffusion_eval_ft` module path)."""
     import ctypes as C
-    import glob
 
     from dppo_amd import hip
     from dppo_amd.model.diffusion.diffusion_eval import DiffusionEval
     from dppo_amd.model.diffusion.unet import Unet1D
     from dppo_amd.model.rl.gaussian_ppo import PPO_Gaussian
-    os.environ.setdefault("DPPO_LOG_DIR", "/tmp/log")
-    os.environ.setdefault("DPPO_DATA_DIR", "/tmp/data")
-    os.environ.setdefault("DPPO_WANDB_ENTITY", "none")
     lib = hip.load()
     n_unet = 0
     for pat in ("*/finetune/*/ft_ppo_diffusion_unet.yaml", "*/pretrain/*/pre_diffusion_unet.yaml"):
-        for p in sorted(glob.glob(os.path.join(REF_CFG, pat))):
-            cfg = load_config(p, overrides=["device=cpu"])
+        for p, cfg in shipped(pat):
             node = cfg.model.actor if "actor" in cfg.model else cfg.model.network
             net = instantiate(node)
             assert isinstance(net, Unet1D), p
@@ -181,8 +171,7 @@ def test_every_shipped_state_unet_gaussian_and_eval_cfg_builds():
             n_unet += 1
     assert n_unet >= 20  # incl. the dim: 40 cfgs (robomimic can / lift): maps padded to 64 / 128 channels in their images
     n_gauss = 0
-    for p in sorted(glob.glob(os.path.join(REF_CFG, "*", "finetune", "*", "ft_ppo_gaussian_mlp.yaml"))):
-        cfg = load_config(p, overrides=["device=cpu"])
+    for p, cfg in shipped("*/finetune/*/ft_ppo_gaussian_mlp.yaml"):
         if cfg.model.actor.get("fixed_std", None) is None or not cfg.model.actor.get("residual_style", False):
             with pytest.raises(NotImplementedError):
                 instantiate(cfg.model.actor)
@@ -194,33 +183,26 @@ def test_every_shipped_state_unet_gaussian_and_eval_cfg_builds():
     assert n_gauss >= 7
     n_eval = 0
     for pat in ("*/eval/*/eval_diffusion_mlp.yaml", "*/eval/*/eval_diffusion_unet.yaml"):
-        for p in sorted(glob.glob(os.path.join(REF_CFG, pat))):
-            cfg = load_config(p, overrides=["device=cpu"])
+        for p, cfg in shipped(pat):
             assert get_class(cfg.model._target_) is DiffusionEval, p
             n_eval += 1
     assert n_eval >= 10
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference checkout not present (GPU box)")
 def test_every_shipped_pixel_diffusion_cfg_builds():
     """The image cfgs (ft_ppo_diffusion_{mlp,unet}_img.yaml, pre_diffusion_{mlp,unet}_img.yaml, eval_diffusion_*_img.yaml):
     the pixel networks build on CPU, their state dict splits into encoder | trunk in the C ABI's two flat layouts, and the
     fine-tuning cfgs resolve to the image agent with a ViTCritic."""
     import ctypes as C
-    import glob
 
     from dppo_amd import hip
     from dppo_amd.model.common.critic import ViTCritic
-    os.environ.setdefault("DPPO_LOG_DIR", "/tmp/log")
-    os.environ.setdefault("DPPO_DATA_DIR", "/tmp/data")
-    os.environ.setdefault("DPPO_WANDB_ENTITY", "none")
     lib = hip.load()
     n = 0
     for pat in ("*/finetune/*/ft_ppo_diffusion_mlp_img.yaml", "*/finetune/*/ft_ppo_diffusion_unet_img.yaml",
                 "*/pretrain/*/pre_diffusion_mlp_img.yaml", "*/pretrain/*/pre_diffusion_unet_img.yaml",
                 "*/eval/*/eval_diffusion_mlp_img.yaml", "*/eval/*/eval_diffusion_unet_img.yaml"):
-        for p in sorted(glob.glob(os.path.join(REF_CFG, pat))):
-            cfg = load_config(p, overrides=["device=cpu"])
+        for p, cfg in shipped(pat):
             node = cfg.model.actor if "actor" in cfg.model else cfg.model.network
             net = instantiate(node)
             assert getattr(net, "is_vision", False), p
@@ -238,8 +220,7 @@ def test_every_shipped_pixel_diffusion_cfg_builds():
             n += 1
     assert n >= 20
     n_g = 0
-    for p in sorted(glob.glob(os.path.join(REF_CFG, "*", "finetune", "*", "ft_ppo_gaussian_mlp_img.yaml"))):
-        cfg = load_config(p, overrides=["device=cpu"])
+    for p, cfg in shipped("*/finetune/*/ft_ppo_gaussian_mlp_img.yaml"):
         net = instantiate(cfg.model.actor)
         assert getattr(net, "is_vision", False) and net.learn_fixed_std and net.tanh_output, p
         assert get_class(cfg._target_).__name__ == "TrainPPOImgGaussianAgent", p
@@ -248,22 +229,16 @@ def test_every_shipped_pixel_diffusion_cfg_builds():
     assert n_g == 4
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference checkout not present (GPU box)")
 def test_every_shipped_gmm_mlp_cfg_builds():
     """ft_ppo_gmm_mlp.yaml (d3il: plain 256 x 2 trunks; robomimic: residual trunks with 140 / 560 mean outputs): the model builds,
     the two trunk descriptors pass the C ABI's checks, and the cfg resolves to the Gaussian agent like in the reference."""
     import ctypes as C
-    import glob
 
     from dppo_amd import hip
     from dppo_amd.model.rl.gmm_ppo import PPO_GMM
-    os.environ.setdefault("DPPO_LOG_DIR", "/tmp/log")
-    os.environ.setdefault("DPPO_DATA_DIR", "/tmp/data")
-    os.environ.setdefault("DPPO_WANDB_ENTITY", "none")
     lib = hip.load()
     n = 0
-    for p in sorted(glob.glob(os.path.join(REF_CFG, "*", "finetune", "*", "ft_ppo_gmm_mlp.yaml"))):
-        cfg = load_config(p, overrides=["device=cpu"])
+    for p, cfg in shipped("*/finetune/*/ft_ppo_gmm_mlp.yaml"):
         cfg.model.network_path = None
         model = instantiate(cfg.model)
         assert isinstance(model, PPO_GMM) and get_class(cfg._target_).__name__ == "TrainPPOGaussianAgent", p

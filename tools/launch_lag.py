@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host launch time vs device start time of every kernel of one update step, from
-    rocprofv3 --hip-runtime-trace --kernel-trace --output-format csv -d out -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline
+    rocprofv3 --hip-runtime-trace --kernel-trace --output-format csv -d out -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline
     python tools/launch_lag.py out/*/*_hip_api_trace.csv out/*/*_kernel_trace.csv [loss index]
 Tells a GPU idle gap caused by a late host launch from one caused by a device-side dependency."""
 import csv

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MFMA utilisation per kernel from a rocprofv3 --pmc pass (SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE):
 
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d out -- python3 bench.py ...
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d out -- python3 bench.py --full ...
     python tools/mfma_util.py out/*/*counter_collection.csv [out.json]
 
 util = MFMA-busy cycles summed over the chip's 1024 SIMDs / (1024 x GPU-active cycles of the dispatch).  rocprofv3

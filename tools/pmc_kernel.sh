@@ -11,7 +11,7 @@ for pmc in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum" \
            "GRBM_GUI_ACTIVE GRBM_COUNT"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $pmc --output-format csv -d $O/pmc$i -- python3 $R/bench.py --steps 4 --warmup 2 --passes 1 --spin-up 20 --no-cpu-baseline --no-fp32 --no-pixel --no-configs --tune 2=0 $args > $O/pmc$i.log 2>&1 || { echo "pass $i failed"; tail -3 $O/pmc$i.log; continue; }
+  timeout -k 10 300 rocprofv3 --pmc $pmc --output-format csv -d $O/pmc$i -- python3 $R/bench.py --full --steps 4 --warmup 2 --passes 1 --spin-up 20 --no-cpu-baseline --no-fp32 --no-pixel --no-configs --tune 2=0 $args > $O/pmc$i.log 2>&1 || { echo "pass $i failed"; tail -3 $O/pmc$i.log; continue; }
   python3 - "$(ls $O/pmc$i/*/*counter_collection.csv)" "$K" <<'PY'
 import csv,sys,collections
 vals=collections.defaultdict(lambda: collections.defaultdict(float))
