@@ -2344,6 +2344,58 @@ int dppo_gaussian_ppo_loss_fwd_bwd_obs(const dppo_net_desc* actor, const dppo_ne
                          workspace, workspace_bytes, stream, io);
 }
 
+// ---- Gaussian behaviour cloning (GaussianModel.loss): the training buffers of one trunk, no critic ----------------------------
+int64_t dppo_gaussian_bc_workspace_bytes(const dppo_net_desc* actor, int prec, int64_t N) {
+  if (check_net(actor) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  Carver c{nullptr, 0, 0};
+  double *m, *sc, *pa;
+  if (prec == DPPO_PREC_F32) {
+    MlpBufs<F32> A, Cb;
+    return (int64_t)carve_gauss<F32>(c, *actor, nullptr, N, true, A, Cb, m, sc, pa);
+  }
+  MlpBufs<BF16> A, Cb;
+  return (int64_t)carve_gauss<BF16>(c, *actor, nullptr, N, true, A, Cb, m, sc, pa);
+}
+template <class P>
+static int gauss_bc_impl(const dppo_net_desc& a, const float* ap, const char* ak, const dppo_gaussian_cfg& cfg,
+                         const float* logvar, const float* obs, const float* actions, int64_t N, double ent_coef, float* agrad,
+                         float* lvgrad, double* out, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  MlpBufs<P> A, Cb;
+  double *moments, *scratch, *partial;
+  const size_t need = carve_gauss<P>(c, a, nullptr, N, true, A, Cb, moments, scratch, partial);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout LA = pack_layout<P>(a, 0);
+  launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, a.cond_dim, N, A.in, LA.Kp0, s);
+  mlp_forward<P>(a, ap, ak, LA, N, A, true, s);
+  GaussArgs g;
+  memset(&g, 0, sizeof(g));
+  g.cfg = cfg, g.mean_pre = A.out, g.ldm = A.ldout, g.logvar = logvar, g.actions = actions, g.N = N, g.AF = a.out_dim;
+  g.d_mean = A.d_out, g.lddm = LA.Kpo, g.partial = partial, g.logvar_grad = lvgrad, g.ent_coef = ent_coef, g.bc_out = out;
+  launch_gauss_nll<P>(g, s);
+  mlp_backward<P>(a, ap, ak, LA, N, A, agrad, nullptr, nullptr, 0, s, false, 1);
+  return check_launch();
+}
+int dppo_gaussian_bc_loss_fwd_bwd(const dppo_net_desc* actor, int prec, const float* params, const void* packed,
+                                  const dppo_gaussian_cfg* cfg, const float* logvar, const float* obs, const float* actions,
+                                  int64_t N, double ent_coef, float* grad, float* logvar_grad, double* loss_entropy,
+                                  void* workspace, int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_gauss(actor, cfg, logvar)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!params || !packed || !obs || !actions || !grad || !loss_entropy || !workspace) return fail(-1, "null pointer");
+  if (cfg->std_mode == 1 && !logvar_grad) return fail(-1, "std_mode 1 needs logvar_grad");
+  if (cfg->deterministic) return fail(-1, "the behaviour-cloning loss is not defined for deterministic = 1");
+  if (cfg->std_mode == 1 && actor->out_dim > 768)
+    return fail(-1, "Ta * Da above 768 with a learned std (the logvar terms of one block live in shared memory)");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+#define CALL(P)                                                                                                              \
+  gauss_bc_impl<P>(*actor, params, (const char*)packed, *cfg, logvar, obs, actions, N, ent_coef, grad, logvar_grad, loss_entropy, \
+                   workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
 // ---- mixture-of-Gaussians policy PPO (gmm.hip) ---------------------------------------------------------------------------
 static int check_gmm(const dppo_net_desc* mean, const dppo_net_desc* wts, const dppo_gmm_cfg* cfg, const float* logvar) {
   if (int e = check_net(mean)) return e;
@@ -2495,6 +2547,73 @@ int dppo_gmm_ppo_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* we
   gmm_ppo_impl<P>(*mean, *weights, *critic, mean_params, (const char*)mean_packed, weights_params, (const char*)weights_packed,        \
                   critic_params, (const char*)critic_packed, *cfg, logvar, obs, actions, returns, oldvalues, adv, oldlogp, N,          \
                   global_moments, mean_grad, weights_grad, critic_grad, logvar_grad, stats, workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+// ---- GMM behaviour cloning (GMMModel.loss): the training buffers of the two trunks, no critic -----------------------------------
+int64_t dppo_gmm_bc_workspace_bytes(const dppo_net_desc* mean, const dppo_net_desc* weights, int prec, int64_t N) {
+  if (check_net(mean) || check_net(weights) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  Carver c{nullptr, 0, 0};
+  double *m, *sc, *pa;
+  const int K = GMM_MAX_MODES * 64;
+  if (prec == DPPO_PREC_F32) {
+    MlpBufs<F32> Am, Aw, Cb;
+    return (int64_t)carve_gmm<F32>(c, *mean, *weights, nullptr, N, K, true, Am, Aw, Cb, m, sc, pa);
+  }
+  MlpBufs<BF16> Am, Aw, Cb;
+  return (int64_t)carve_gmm<BF16>(c, *mean, *weights, nullptr, N, K, true, Am, Aw, Cb, m, sc, pa);
+}
+template <class P>
+static int gmm_bc_impl(const dppo_net_desc& am, const dppo_net_desc& aw, const float* mp, const char* mk, const float* wp,
+                       const char* wk, const dppo_gmm_cfg& cfg, const float* logvar, const float* obs, const float* actions,
+                       int64_t N, float* mgrad, float* wgrad, float* lvgrad, double* out, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  MlpBufs<P> Am, Aw, Cb;
+  double *moments, *scratch, *partial;
+  const size_t need = carve_gmm<P>(c, am, aw, nullptr, N, GMM_MAX_MODES * 64, true, Am, Aw, Cb, moments, scratch, partial);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout LM = pack_layout<P>(am, 0), LW = pack_layout<P>(aw, 0);
+  hipStream_t s2 = fork_side(s);  // the weights trunk beside the mean trunk, forward and backward
+  launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, aw.cond_dim, N, Aw.in, LW.Kp0, s2);
+  mlp_forward<P>(aw, wp, wk, LW, N, Aw, true, s2);
+  launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, am.cond_dim, N, Am.in, LM.Kp0, s);
+  mlp_forward<P>(am, mp, mk, LM, N, Am, true, s);
+  if (s2 != s) join_side(s, s2);  // the loss reads both outputs
+  GmmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.cfg = cfg, g.mean_pre = Am.out, g.ldm = Am.ldout, g.logits = Aw.out, g.ldl = Aw.ldout, g.logvar = logvar, g.actions = actions;
+  g.N = N, g.AF = cfg.horizon_steps * cfg.action_dim, g.d_mean = Am.d_out, g.lddm = LM.Kpo, g.d_logits = Aw.d_out, g.lddl = LW.Kpo;
+  g.partial = partial, g.logvar_grad = lvgrad, g.bc_out = out;
+  launch_gmm_nll<P>(g, s);
+  s2 = fork_side(s);
+  mlp_backward<P>(aw, wp, wk, LW, N, Aw, wgrad, nullptr, nullptr, 0, s2, false, -1);
+  mlp_backward<P>(am, mp, mk, LM, N, Am, mgrad, nullptr, nullptr, 0, s, false, 1);
+  if (s2 != s) join_side(s, s2);
+  return check_launch();
+}
+int dppo_gmm_bc_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* weights, int prec, const float* mean_params,
+                             const void* mean_packed, const float* weights_params, const void* weights_packed,
+                             const dppo_gmm_cfg* cfg, const float* logvar, const float* obs, const float* actions, int64_t N,
+                             float* mean_grad, float* weights_grad, float* logvar_grad, double* loss_entropy, void* workspace,
+                             int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_gmm(mean, weights, cfg, logvar)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!mean_params || !mean_packed || !weights_params || !weights_packed || !obs || !actions || !mean_grad || !weights_grad ||
+      !loss_entropy || !workspace)
+    return fail(-1, "null pointer");
+  if (cfg->std_mode == 1 && !logvar_grad) return fail(-1, "std_mode 1 needs logvar_grad");
+  if (cfg->std_mode == 0 && !(cfg->fixed_std > 0)) return fail(-1, "fixed_std must be positive");
+  if (cfg->deterministic) return fail(-1, "the behaviour-cloning loss is not defined for deterministic = 1");
+  if (cfg->action_dim > 64) return fail(-1, "action_dim above 64 (the logvar partials hold %d x 64 columns)", GMM_MAX_MODES);
+  if ((int64_t)cfg->num_modes * cfg->horizon_steps * cfg->action_dim > 3072)
+    return fail(-1, "num_modes * Ta * Da above 3072 (the logvar terms of one block live in shared memory)");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+#define CALL(P)                                                                                                                   \
+  gmm_bc_impl<P>(*mean, *weights, mean_params, (const char*)mean_packed, weights_params, (const char*)weights_packed, *cfg, logvar, \
+                 obs, actions, N, mean_grad, weights_grad, logvar_grad, loss_entropy, workspace, workspace_bytes,                 \
+                 (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }

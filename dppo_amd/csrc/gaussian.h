@@ -33,11 +33,18 @@ struct GaussArgs {
   double* stats;          // [DPPO_STAT_COUNT]
   float* logvar_grad;     // [Da]: d pg_loss / d logvar (std_mode 1)
   double* adv_moments_out;  // local moments workspace [3 + 2 * blocks']
+  // behaviour-cloning loss (launch_gauss_nll)
+  double ent_coef;          // loss = mean NLL - ent_coef * entropy
+  double* bc_out;           // [2]: {loss, entropy}
 };
 
 int gauss_blocks(int64_t N);
 template <class P>
 void launch_gauss_loss(const GaussArgs& a, hipStream_t s);  // loss + d_mean + d_v + per-block partials, then the finalize
+// GaussianModel.loss (model/common/gaussian.py:49-65): mean over N*AF of -log N(a; mu, sigma) - ent_coef * entropy, d_mean,
+// per-block partials ([8 + Da] doubles each, as above), then the finalize ({loss, entropy} -> bc_out, logvar_grad)
+template <class P>
+void launch_gauss_nll(const GaussArgs& a, hipStream_t s);
 void launch_gauss_sample(const GaussArgs& a, hipStream_t s);
 void launch_gauss_logprob(const GaussArgs& a, hipStream_t s);
 void launch_gauss_moments(const float* adv, int64_t N, double* moments, double* scratch, hipStream_t s);

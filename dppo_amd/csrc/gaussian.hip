@@ -253,4 +253,94 @@ void launch_gauss_loss(const GaussArgs& a, hipStream_t s) {
 template void launch_gauss_loss<F32>(const GaussArgs&, hipStream_t);
 template void launch_gauss_loss<BF16>(const GaussArgs&, hipStream_t);
 
+// ---- GaussianModel.loss (gaussian.py:49-65): behaviour cloning, -log N(a; mu, sigma) averaged over the N * AF ELEMENTS (a plain
+// Normal, no Independent) minus ent_coef * mean element entropy; its gradient w.r.t. the trunk output and logvar ------------------
+template <class P>
+__global__ __launch_bounds__(256) void gauss_nll_kernel(const GaussArgs a) {
+  typedef typename P::elem_t E;
+  extern __shared__ float lds[];  // [GAUSS_SPB][AF] per-element d loss / d logvar contributions (std_mode 1)
+  __shared__ double red[GAUSS_SPB];
+  const dppo_gaussian_cfg& c = a.cfg;
+  const int AF = a.AF, Da = c.action_dim;
+  const float inv = 1.f / ((float)a.N * (float)AF);  // d mean(.) / d element
+  const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const int64_t n = (int64_t)blockIdx.x * GAUSS_SPB + grp;
+  const bool live = n < a.N;
+  const int64_t nn = live ? n : a.N - 1;
+  const float* mp = a.mean_pre + nn * a.ldm;
+  const float* ac = a.actions + nn * AF;
+  E* dm = (E*)a.d_mean + (size_t)nn * a.lddm;
+  double sum = 0;
+  for (int j = sub; j < a.lddm; j += 16) {  // the pad columns [AF, lddm) are written as zeros
+    float g = 0.f;
+    if (j < AF) {
+      const float mu = c.tanh_mean ? tanhf(mp[j]) : mp[j];
+      float inside;
+      const float sg = gauss_sigma(c, a.logvar, j % Da, &inside);
+      const float d = ac[j] - mu, var = sg * sg;
+      sum += (double)-(-(d * d) / (2.f * var) - logf(sg) - GAUSS_LOG_SQRT_2PI);
+      g = -(d / var) * (c.tanh_mean ? 1.f - mu * mu : 1.f) * inv;
+      // d nll / d logvar = -0.5 (d^2 / var - 1), through the clamp of logvar
+      if (c.std_mode == 1) lds[grp * AF + j] = live ? -0.5f * ((d * d) / var - 1.f) * inside * inv : 0.f;
+    }
+    if (live) dm[j] = P::from_f32(g);
+  }
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o);
+  if (sub == 0) red[grp] = live ? sum : 0.0;
+  __syncthreads();
+  // per-block partials, fixed order: [nll sum, -, ..., logvar grad (Da) at 8]
+  double* o = a.partial + (size_t)blockIdx.x * (8 + Da);
+  if (threadIdx.x == 0) {
+    double t = 0;
+    for (int g2 = 0; g2 < GAUSS_SPB; ++g2) t += red[g2];
+    o[0] = t;
+  }
+  if (c.std_mode == 1) {
+    for (int jd = threadIdx.x; jd < Da; jd += 256) {
+      double t = 0;
+      for (int g2 = 0; g2 < GAUSS_SPB; ++g2)
+        for (int j = jd; j < AF; j += Da) t += (double)lds[g2 * AF + j];
+      o[8 + jd] = t;
+    }
+  }
+}
+
+// one block; the block partials are added in index order by one thread per column, so the sums do not depend on how a tree
+// would pair them
+__global__ __launch_bounds__(256) void gauss_nll_finalize_kernel(const GaussArgs a, int blocks) {
+  const dppo_gaussian_cfg& c = a.cfg;
+  const int Da = c.action_dim, stride = 8 + Da;
+  for (int k = threadIdx.x; k < 1 + (c.std_mode == 1 ? Da : 0); k += 256) {
+    const int col = k == 0 ? 0 : 8 + (k - 1);
+    double s = 0;
+    for (int b = 0; b < blocks; ++b) s += a.partial[(size_t)b * stride + col];
+    if (k == 0) {
+      // dist.entropy().mean() = 0.5 + 0.5 log(2 pi) + mean_j log sigma_j
+      double ls = 0;
+      for (int jd = 0; jd < Da; ++jd) {
+        float inside;
+        ls += (double)logf(gauss_sigma(c, a.logvar, jd, &inside));
+      }
+      const double ent = (0.5 + 0.5 * 1.8378770664093453) + ls / Da;
+      a.bc_out[0] = s / ((double)a.N * (double)a.AF) - a.ent_coef * ent;
+      a.bc_out[1] = ent;
+    } else {
+      float inside;
+      (void)gauss_sigma(c, a.logvar, k - 1, &inside);
+      a.logvar_grad[k - 1] = (float)(s - a.ent_coef * 0.5 * (double)inside / Da);  // log sigma = 0.5 clamp(logvar)
+    }
+  }
+}
+
+template <class P>
+void launch_gauss_nll(const GaussArgs& a, hipStream_t s) {
+  const int blocks = gauss_blocks(a.N);
+  const size_t lds = a.cfg.std_mode == 1 ? (size_t)GAUSS_SPB * a.AF * sizeof(float) : sizeof(float);
+  hipLaunchKernelGGL((gauss_nll_kernel<P>), dim3(blocks), dim3(256), lds, s, a);
+  hipLaunchKernelGGL(gauss_nll_finalize_kernel, dim3(1), dim3(256), 0, s, a, blocks);
+}
+template void launch_gauss_nll<F32>(const GaussArgs&, hipStream_t);
+template void launch_gauss_nll<BF16>(const GaussArgs&, hipStream_t);
+
 }  // namespace dppo

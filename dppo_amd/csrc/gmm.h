@@ -34,11 +34,16 @@ struct GmmArgs {
   double* partial;     // [blocks][8 + num_modes * Da]
   double* stats;
   float* logvar_grad;  // [num_modes * Da]
+  double* bc_out;      // behaviour-cloning loss (launch_gmm_nll): {loss, entropy}
 };
 
 int gmm_blocks(int64_t N);
 template <class P>
 void launch_gmm_loss(const GmmArgs& a, hipStream_t s);
+// GMMModel.loss (model/common/gmm.py:40-54): -mean_b log p(a_b), d_mean, d_logits, per-block partials, then the finalize
+// ({loss, entropy} -> bc_out, logvar_grad)
+template <class P>
+void launch_gmm_nll(const GmmArgs& a, hipStream_t s);
 void launch_gmm_sample(const GmmArgs& a, hipStream_t s);
 void launch_gmm_logprob(const GmmArgs& a, hipStream_t s);
 

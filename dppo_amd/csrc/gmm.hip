@@ -300,4 +300,111 @@ void launch_gmm_loss(const GmmArgs& a, hipStream_t s) {
 template void launch_gmm_loss<F32>(const GmmArgs&, hipStream_t);
 template void launch_gmm_loss<BF16>(const GmmArgs&, hipStream_t);
 
+// ---- GMMModel.loss (gmm.py:40-54): behaviour cloning, -mean_b log p(a_b), + d loss / d (mean_pre, logits, logvar) ---------------
+// gmm_eval() takes the maximum out before every exp, so the responsibilities stay finite where all component log-densities sit
+// hundreds of nats below zero (fixed_std 0.1 and an action far from every mean).  The entropy is reported, not part of the loss.
+template <class P>
+__global__ __launch_bounds__(256) void gmm_nll_kernel(const GmmArgs a) {
+  typedef typename P::elem_t E;
+  extern __shared__ float lds[];  // [GMM_SPB][num_modes * AF] per-element d loss / d logvar contributions (std_mode 1)
+  __shared__ double red[GMM_SPB][2];
+  const dppo_gmm_cfg& c = a.cfg;
+  const int M = c.num_modes, AF = a.AF, Da = c.action_dim, Ta = AF / Da;
+  const float inv = 1.f / (float)a.N;
+  const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
+  const int64_t n = (int64_t)blockIdx.x * GMM_SPB + grp;
+  const bool live = n < a.N;
+  const int64_t nn = live ? n : a.N - 1;
+  GmmEval ev;
+  gmm_eval(a, nn, lane, ev);
+  // entropy as the reference approximates it: sum_m pi_m H_m, H_m = sum_j (0.5 + 0.5 log 2 pi + log sigma_mj)
+  float Hbar = 0.f;
+  for (int m = 0; m < M; ++m) {
+    float h = 0.f;
+    for (int d = 0; d < Da; ++d) {
+      float inside;
+      h += logf(gmm_sigma(c, a.logvar, m, d, &inside));
+    }
+    Hbar += expf(ev.logpi[m]) * ((float)AF * (0.5f + GMM_LOG_SQRT_2PI) + (float)Ta * h);
+  }
+  const float* mp = a.mean_pre + nn * a.ldm;
+  const float* ac = a.actions + nn * AF;
+  E* dm = (E*)a.d_mean + (size_t)nn * a.lddm;
+  for (int e = lane; e < a.lddm; e += 64) {  // the pad columns [M * AF, lddm) are written as zeros
+    float g = 0.f;
+    if (e < M * AF) {
+      const int m = e / AF, j = e - m * AF;
+      float inside;
+      const float sg = gmm_sigma(c, a.logvar, m, j % Da, &inside);
+      const float mu = tanhf(mp[e]);
+      const float d = ac[j] - mu, var = sg * sg;
+      float rm = 0.f;
+#pragma unroll
+      for (int mm = 0; mm < GMM_MAX_MODES; ++mm) rm = mm == m ? ev.r[mm] : rm;
+      g = -inv * rm * (d / var) * (1.f - mu * mu);
+      if (c.std_mode == 1) lds[grp * M * AF + e] = live ? -inv * rm * 0.5f * ((d * d) / var - 1.f) * inside : 0.f;
+    }
+    if (live) dm[e] = P::from_f32(g);
+  }
+  if (live) {
+    E* dl = (E*)a.d_logits + (size_t)nn * a.lddl;
+    for (int m = lane; m < a.lddl; m += 64) {
+      float g = 0.f;
+      if (m < M) {
+        float rm = 0.f, lpi = 0.f;
+#pragma unroll
+        for (int mm = 0; mm < GMM_MAX_MODES; ++mm)
+          if (mm == m) rm = ev.r[mm], lpi = ev.logpi[mm];
+        g = -inv * (rm - expf(lpi));  // d log p / d logit_m = r_m - pi_m
+      }
+      dl[m] = P::from_f32(g);
+    }
+  }
+  if (lane == 0) {
+    red[grp][0] = live ? -(double)ev.logp : 0.0;
+    red[grp][1] = live ? (double)Hbar : 0.0;
+  }
+  __syncthreads();
+  const int stride = 8 + M * Da;
+  double* o = a.partial + (size_t)blockIdx.x * stride;
+  if (threadIdx.x < 2) {
+    double t = 0;
+    for (int g2 = 0; g2 < GMM_SPB; ++g2) t += red[g2][threadIdx.x];
+    o[threadIdx.x] = t;
+  }
+  if (c.std_mode == 1)  // d / d logvar[m][d] over (sample, chunk step) in fixed order
+    for (int k = threadIdx.x; k < M * Da; k += 256) {
+      const int m = k / Da, d = k % Da;
+      double t = 0;
+      for (int g2 = 0; g2 < GMM_SPB; ++g2)
+        for (int tt = 0; tt < Ta; ++tt) t += (double)lds[g2 * M * AF + m * AF + tt * Da + d];
+      o[8 + k] = t;
+    }
+}
+
+// one block; one thread per column adds the block partials in index order
+__global__ __launch_bounds__(256) void gmm_nll_finalize_kernel(const GmmArgs a, int blocks) {
+  const dppo_gmm_cfg& c = a.cfg;
+  const int K = c.num_modes * c.action_dim, stride = 8 + K;
+  for (int k = threadIdx.x; k < 2 + (c.std_mode == 1 ? K : 0); k += 256) {
+    const int col = k < 2 ? k : 8 + (k - 2);
+    double s = 0;
+    for (int b = 0; b < blocks; ++b) s += a.partial[(size_t)b * stride + col];
+    if (k < 2)
+      a.bc_out[k] = s / (double)a.N;
+    else
+      a.logvar_grad[k - 2] = (float)s;  // already scaled by 1 / N per sample
+  }
+}
+
+template <class P>
+void launch_gmm_nll(const GmmArgs& a, hipStream_t s) {
+  const int blocks = gmm_blocks(a.N);
+  const size_t lds = a.cfg.std_mode == 1 ? (size_t)GMM_SPB * a.cfg.num_modes * a.AF * sizeof(float) : sizeof(float);
+  hipLaunchKernelGGL((gmm_nll_kernel<P>), dim3(blocks), dim3(256), lds, s, a);
+  hipLaunchKernelGGL(gmm_nll_finalize_kernel, dim3(1), dim3(256), 0, s, a, blocks);
+}
+template void launch_gmm_nll<F32>(const GmmArgs&, hipStream_t);
+template void launch_gmm_nll<BF16>(const GmmArgs&, hipStream_t);
+
 }  // namespace dppo

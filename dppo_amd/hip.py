@@ -144,6 +144,12 @@ SYMBOLS = {
     "dppo_gmm_logprob": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(GmmCfg), _P, _P, _P, _L, _P, _P, _L, _P]),
     "dppo_gmm_ppo_loss_fwd_bwd": (_I, [_ND, _ND, _ND, _I, _P, _P, _P, _P, _P, _P, C.POINTER(GmmCfg), _P, _P, _P, _P, _P, _P, _P,
                                        _L, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    # behaviour-cloning pre-training of the Gaussian / mixture policies (GaussianModel.loss, GMMModel.loss)
+    "dppo_gaussian_bc_workspace_bytes": (_L, [_ND, _I, _L]),
+    "dppo_gaussian_bc_loss_fwd_bwd": (_I, [_ND, _I, _P, _P, C.POINTER(GaussianCfg), _P, _P, _P, _L, _D, _P, _P, _P, _P, _L, _P]),
+    "dppo_gmm_bc_workspace_bytes": (_L, [_ND, _ND, _I, _L]),
+    "dppo_gmm_bc_loss_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(GmmCfg), _P, _P, _P, _L, _P, _P, _P, _P, _P, _L,
+                                      _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

@@ -1,5 +1,6 @@
 """Gaussian policy parameterisation.  Mirrors ``dppo/model/common/gaussian.py:14-121`` (reference ``GaussianModel``):
-constructor surface, checkpoint loading, ``forward`` (sampling with the draw clipped to +-randn_clip_value sigma).
+constructor surface, checkpoint loading, ``loss`` (behaviour cloning: one ``dppo_gaussian_bc_loss_fwd_bwd`` call), ``forward``
+(sampling with the draw clipped to +-randn_clip_value sigma).
 Sampling is one trunk forward + one epilogue kernel (``dppo_gaussian_sample``); noise is drawn in the kernel (Philox keyed
 from torch's CPU generator) unless a recorded tensor is passed (parity tests)."""
 from __future__ import annotations
@@ -10,6 +11,7 @@ import logging
 import torch
 
 from dppo_amd import hip
+from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss  # (value, gradient views, *parameters) -> scalar with a backward
 
 log = logging.getLogger(__name__)
 
@@ -31,9 +33,47 @@ class GaussianModel(torch.nn.Module):
         self.tanh_output = tanh_output
         self.prec = hip.PREC_BY_NAME[precision] if precision is not None else network.prec
         object.__setattr__(self, "_ws_g", hip.Workspace())
+        object.__setattr__(self, "_ws_bc", hip.Workspace())
 
     def loss(self, true_action, cond, ent_coef):
-        raise NotImplementedError("dppo_amd: supervised Gaussian pre-training (-log p - ent_coef * entropy) is out of scope")
+        """Behaviour cloning (reference :49-65): mean over the B*Ta*Da elements of -log N(a; mu, sigma) minus ``ent_coef`` times
+        the mean element entropy -> (loss, {"entropy": entropy}), device scalars, no host sync.  Value and every gradient
+        come from one library call (``dppo_gaussian_bc_loss_fwd_bwd``); the returned scalar carries them into
+        ``.backward()``, and the flat d loss / d trunk parameters stays in ``last_loss_grad`` (d loss / d logvar in
+        ``last_logvar_grad``) for callers that step a flat optimiser."""
+        state = cond["state"]
+        hip.require_gpu(state, type(self).__name__ + ".loss")
+        net = self.network
+        if getattr(net, "is_vision", False):
+            raise NotImplementedError("dppo_amd: supervised pre-training of the pixel Gaussian policy is not built")
+        B, dev = len(true_action), state.device
+        AF = net.action_dim * net.horizon_steps
+        obs = state.reshape(B, -1).contiguous().float()
+        act = true_action.reshape(B, AF).contiguous().float()
+        lib, d = hip.load(), net.net_desc()
+        cfg = net.gaussian_cfg(randn_clip=self.randn_clip_value)
+        flat = net.flat_params()
+        grad = torch.empty_like(flat)
+        lv_grad = torch.empty(net.action_dim, device=dev) if net.learn_fixed_std else None
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        wsb = lib.dppo_gaussian_bc_workspace_bytes(C.byref(d), self.prec, B)
+        if wsb < 0:
+            hip.check(int(wsb), "dppo_gaussian_bc_workspace_bytes")
+        ws = self._ws_bc.get(wsb, dev)
+        hip.check(lib.dppo_gaussian_bc_loss_fwd_bwd(
+            C.byref(d), self.prec, flat.data_ptr(), net.packed(self.prec, 0).data_ptr(), C.byref(cfg), net.logvar_ptr(),
+            obs.data_ptr(), act.data_ptr(), B, float(ent_coef), grad.data_ptr(), hip.ptr(lv_grad), out.data_ptr(), ws.data_ptr(),
+            ws.numel(), hip.stream()), "dppo_gaussian_bc_loss_fwd_bwd")
+        object.__setattr__(self, "last_loss_grad", grad)
+        object.__setattr__(self, "last_logvar_grad", lv_grad)
+        params = net.trunk_parameters()  # the flat image is their concatenation in this order
+        views, off = [], 0
+        for p in params:
+            views.append(grad[off:off + p.numel()].view(p.shape))
+            off += p.numel()
+        if lv_grad is not None:
+            params, views = params + [net.logvar], views + [lv_grad]
+        return _FusedDenoiseLoss.apply(out[0], views, *params), {"entropy": out[1].float()}
 
     @torch.no_grad()
     def _sample(self, net, cond, deterministic, noise=None, want_mean=False):

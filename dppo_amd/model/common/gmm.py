@@ -1,5 +1,5 @@
 """Mixture-of-Gaussians policy parameterisation.  Mirrors ``dppo/model/common/gmm.py:14-97`` (reference ``GMMModel``): constructor
-surface, checkpoint loading, ``forward`` (draw a component from Categorical(logits), then the action from that component).  One
+surface, checkpoint loading, ``loss`` (behaviour cloning: one ``dppo_gmm_bc_loss_fwd_bwd`` call), ``forward`` (draw a component from Categorical(logits), then the action from that component).  One
 library call per sampling step (``dppo_gmm_sample``: both trunks + the epilogue); the draws are made in the kernel (Philox keyed
 from torch's CPU generator) unless recorded ones are passed (parity tests)."""
 from __future__ import annotations
@@ -10,6 +10,7 @@ import logging
 import torch
 
 from dppo_amd import hip
+from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss  # (value, gradient views, *parameters) -> scalar with a backward
 
 log = logging.getLogger(__name__)
 
@@ -27,9 +28,46 @@ class GMMModel(torch.nn.Module):
         self.horizon_steps = horizon_steps
         self.prec = hip.PREC_BY_NAME[precision] if precision is not None else network.prec
         object.__setattr__(self, "_ws_g", hip.Workspace())
+        object.__setattr__(self, "_ws_bc", hip.Workspace())
 
     def loss(self, true_action, cond, **kwargs):
-        raise NotImplementedError("dppo_amd: supervised GMM pre-training (-log p) is out of scope")
+        """Behaviour cloning (reference :40-54): -mean_b log p(a_b) under the mixture -> (loss, {"entropy": entropy}), device
+        scalars, no host sync (the entropy, mean_b sum_m pi_bm H_m, is reported only).  One library call
+        (``dppo_gmm_bc_loss_fwd_bwd``: both trunks forward, the loss epilogue, both backward passes); the returned scalar
+        carries the gradients into ``.backward()``, and the flat d loss / d [mlp_mean | mlp_weights] stays in
+        ``last_loss_grad`` (d loss / d logvar in ``last_logvar_grad``) for callers that step a flat optimiser."""
+        state = cond["state"]
+        hip.require_gpu(state, type(self).__name__ + ".loss")
+        net = self.network
+        B, dev = len(true_action), state.device
+        AF = net.action_dim * net.horizon_steps
+        obs = state.reshape(B, -1).contiguous().float()
+        act = true_action.reshape(B, AF).contiguous().float()
+        lib = hip.load()
+        m, w = net.mean_net, net.weights_net
+        grad = torch.empty_like(net.flat_params())
+        n_mean = m.flat_params().numel()
+        lv_grad = torch.empty(net.action_dim * net.num_modes, device=dev) if net.learn_fixed_std else None
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        wsb = lib.dppo_gmm_bc_workspace_bytes(C.byref(m.net_desc()), C.byref(w.net_desc()), self.prec, B)
+        if wsb < 0:
+            hip.check(int(wsb), "dppo_gmm_bc_workspace_bytes")
+        ws = self._ws_bc.get(wsb, dev)
+        cfg = net.gmm_cfg()
+        hip.check(lib.dppo_gmm_bc_loss_fwd_bwd(
+            *self._net_args(net), C.byref(cfg), net.logvar_ptr(), obs.data_ptr(), act.data_ptr(), B, grad.data_ptr(),
+            grad.data_ptr() + 4 * n_mean, hip.ptr(lv_grad), out.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()),
+            "dppo_gmm_bc_loss_fwd_bwd")
+        object.__setattr__(self, "last_loss_grad", grad)
+        object.__setattr__(self, "last_logvar_grad", lv_grad)
+        params = net.trunk_parameters()  # the flat image is their concatenation in this order
+        views, off = [], 0
+        for p in params:
+            views.append(grad[off:off + p.numel()].view(p.shape))
+            off += p.numel()
+        if lv_grad is not None:
+            params, views = params + [net.logvar], views + [lv_grad]
+        return _FusedDenoiseLoss.apply(out[0], views, *params), {"entropy": out[1].float()}
 
     def _net_args(self, net):
         m, w = net.mean_net, net.weights_net

@@ -43,6 +43,16 @@ class Gaussian_MLP(HipNet):
         self.use_fixed_std, self.fixed_std, self.learn_fixed_std = True, fixed_std, learn_fixed_std
         self.tanh_output = tanh_output
         self.prec = hip.PREC_BY_NAME[precision]
+        self._cache_clamp_bounds()
+
+    def _cache_clamp_bounds(self):
+        """The clamp bounds as Python floats for the per-call cfg struct: they are constants, and reading them from the
+        (device) parameters on every call would be two host synchronisations per step."""
+        object.__setattr__(self, "_lv_bounds", (float(self.logvar_min), float(self.logvar_max)))
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self._cache_clamp_bounds()  # a checkpoint carries logvar_min / logvar_max
 
     def trunk_parameters(self):
         return list(self.mlp_mean.parameters())
@@ -61,7 +71,7 @@ class Gaussian_MLP(HipNet):
         return hip.GaussianCfg(
             horizon_steps=self.horizon_steps, action_dim=self.action_dim, tanh_mean=int(bool(self.tanh_output)),
             std_mode=1 if self.learn_fixed_std else 0, norm_adv=1, has_vclip=0, deterministic=int(bool(deterministic)), pad=0,
-            fixed_std=float(self.fixed_std), logvar_min=float(self.logvar_min), logvar_max=float(self.logvar_max),
+            fixed_std=float(self.fixed_std), logvar_min=self._lv_bounds[0], logvar_max=self._lv_bounds[1],
             randn_clip=float(randn_clip), clip_ploss_coef=0.0, clip_vloss_coef=0.0, seed_lo=0, seed_hi=0)
 
     def logvar_ptr(self):

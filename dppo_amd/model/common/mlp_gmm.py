@@ -64,6 +64,16 @@ class GMM_MLP(HipNet):
         self.mlp_weights = model([cond_dim] + list(mlp_dims) + [num_modes], activation_type=activation_type,
                                  out_activation_type="Identity", use_layernorm=use_layernorm)
         self.prec = hip.PREC_BY_NAME[precision]
+        self._cache_clamp_bounds()
+
+    def _cache_clamp_bounds(self):
+        """The clamp bounds as Python floats for the per-call cfg struct: they are constants, and reading them from the
+        (device) parameters on every call would be two host synchronisations per step."""
+        object.__setattr__(self, "_lv_bounds", (float(self.logvar_min), float(self.logvar_max)))
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self._cache_clamp_bounds()  # a checkpoint carries logvar_min / logvar_max
 
     # ---- the flat buffer covers [mlp_mean | mlp_weights]; the two trunk views live inside it
     def trunk_parameters(self):
@@ -112,7 +122,7 @@ class GMM_MLP(HipNet):
     def gmm_cfg(self, deterministic=False, ent_coef=0.0) -> hip.GmmCfg:
         return hip.GmmCfg(horizon_steps=self.horizon_steps, action_dim=self.action_dim, num_modes=self.num_modes,
                           std_mode=1 if self.learn_fixed_std else 0, norm_adv=1, has_vclip=0, deterministic=int(bool(deterministic)),
-                          pad=0, fixed_std=float(self.fixed_std), logvar_min=float(self.logvar_min), logvar_max=float(self.logvar_max),
+                          pad=0, fixed_std=float(self.fixed_std), logvar_min=self._lv_bounds[0], logvar_max=self._lv_bounds[1],
                           ent_coef=float(ent_coef), clip_ploss_coef=0.0, clip_vloss_coef=0.0, seed_lo=0, seed_hi=0)
 
     def logvar_ptr(self):

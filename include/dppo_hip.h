@@ -326,6 +326,20 @@ int dppo_gaussian_ppo_loss_fwd_bwd(const dppo_net_desc* actor, const dppo_net_de
                                    const double* global_moments, float* actor_grad, float* critic_grad,
                                    float* logvar_grad, double* stats, void* workspace, int64_t workspace_bytes,
                                    dppo_stream_t stream);
+/* Behaviour-cloning pre-training of the Gaussian policy.  Replaces model/common/gaussian.py:49-65 (GaussianModel.loss) and
+ * the loss.backward() of agent/pretrain/train_gaussian_agent.py:38-42:
+ *   loss = mean over the N*Ta*Da ELEMENTS of -log N(a; mean, sigma)  -  ent_coef * entropy,
+ *   entropy = mean over the elements of 0.5 + 0.5 log(2 pi) + log sigma  (a plain Normal: no sum over Ta*Da).
+ * One call: row builder -> trunk forward -> loss epilogue + finalize (two launches) -> trunk backward; no host sync.
+ * obs (N,cond), actions (N,Ta*Da).  grad <- d loss / d actor params; logvar_grad (Da; std_mode 1 only, may be NULL
+ * otherwise) <- d loss / d logvar; loss_entropy[2] <- {loss, entropy} (device doubles).  The workspace holds the training
+ * buffers of the trunk without a critic (dppo_gaussian_workspace_bytes(actor, NULL, ..) sizes inference only).  Built for
+ * Ta*Da <= 768 when the std is learned. */
+int64_t dppo_gaussian_bc_workspace_bytes(const dppo_net_desc* actor, int prec, int64_t N);
+int dppo_gaussian_bc_loss_fwd_bwd(const dppo_net_desc* actor, int prec, const float* params, const void* packed,
+                                  const dppo_gaussian_cfg* cfg, const float* logvar, const float* obs, const float* actions,
+                                  int64_t N, double ent_coef, float* grad, float* logvar_grad, double* loss_entropy,
+                                  void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
 
 /* ---- conv denoiser (Unet1D), inference side ------------------------------------------------------
  * Replaces model/diffusion/unet.py:27-327 (ResidualBlock1D, Unet1D.forward), model/diffusion/modules.py:28-95
@@ -569,6 +583,21 @@ int dppo_gmm_ppo_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* we
                               const float* returns, const float* oldvalues, const float* adv, const float* oldlogp, int64_t N,
                               const double* global_moments, float* mean_grad, float* weights_grad, float* critic_grad,
                               float* logvar_grad, double* stats, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
+/* Behaviour-cloning pre-training of the mixture policy.  Replaces model/common/gmm.py:40-54 (GMMModel.loss) and the
+ * loss.backward() of agent/pretrain/train_gaussian_agent.py:38-42:
+ *   loss = -mean_b log p(a_b)  (log p as above: the sum over Ta*Da is inside, the mean is over the N samples only),
+ *   entropy = mean_b sum_m pi_bm H_m  (reported, not part of the loss).
+ * The component log-densities are combined with their maximum taken out before the exp, so the loss and the responsibilities
+ * stay finite where every component sits hundreds of nats below zero (fixed_std 0.1, an action far from every mean).
+ * mean_grad / weights_grad <- d loss / d trunk params (the weights trunk runs on a library-owned side stream), logvar_grad
+ * (num_modes*Da; std_mode 1 only, may be NULL otherwise), loss_entropy[2] <- {loss, entropy} (device doubles).  Built for
+ * action_dim <= 64 and num_modes*Ta*Da <= 3072. */
+int64_t dppo_gmm_bc_workspace_bytes(const dppo_net_desc* mean, const dppo_net_desc* weights, int prec, int64_t N);
+int dppo_gmm_bc_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* weights, int prec, const float* mean_params,
+                             const void* mean_packed, const float* weights_params, const void* weights_packed,
+                             const dppo_gmm_cfg* cfg, const float* logvar, const float* obs, const float* actions, int64_t N,
+                             float* mean_grad, float* weights_grad, float* logvar_grad, double* loss_entropy, void* workspace,
+                             int64_t workspace_bytes, dppo_stream_t stream);
 
 /* ---- loss entries that also return d loss / d observation (a visual encoder sits in front of the trunk) ------------
  * Same arguments as the entry without the suffix, in pre-gathered mode (one observation row per sample, `kinds` given), plus:
