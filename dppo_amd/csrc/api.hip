@@ -388,25 +388,7 @@ struct MlpBufs {  // activations of one network for M rows
   size_t slab_used;   // floats handed out since the last flush
   SlabJobs slab_jobs; // reductions pending on the pool (flush_slabs)
   GemmTNGroup tn_group;  // weight-gradient GEMMs pending on the pool: launched together by flush_slabs
-  // K-major fragment mode (gemm.h GemmTNFrag; frag_ok()): the four tensors only the weight-gradient GEMMs read are written
-  // as MFMA operand fragments by the one-block fused kernels -- into the SAME buffers a1[0], a2[0], dz1_all[0], dh_all[0]
-  // (carved with rows rounded up to whole tiles) -- and the two small operands get fragment copies
-  // Folded tail (gemm.h: GemmTN::red_cnt, GemmTNExtra; knob 35): the slab reductions happen inside the GEMM launch (last
-  // workgroup to arrive at an output tile) and the bias sums / loss statistics ride in it, so no reduction launch follows
-  bool fold;          // set by the caller between carve and backward: red_cnt was zeroed in this call (row builder)
-  unsigned* red_cnt;  // [RED_CNT] tile arrival counters, right behind post_counter (zeroed with it, left zero)
   bool dw0;         // set by the caller between carve and the backward (dw0_ok()): the backward keeps dW0 on chip, dh_0 is never stored
-  // riders of the next weight-gradient GEMM launch (knob 40; filled by mlp_backward, consumed by flush_slabs)
-  bool ride;
-  TailReduce ride_t;     // slab jobs (the backward kernel's dW0 slabs), bias-sum slots, loss statistics
-  PostReduce ride_q;     // the time-embedding part (G == null: none)
-  bool allow_frag;  // set by the caller between carve and forward: the whole pass (forward, backward, GEMMs) may run in it
-  bool frag;        // decided by the forward (allow_frag && merged), obeyed by the backward
-  u32x4* doutf;     // [ks][dof_nt][64]
-  u32x4* xf;        // [ks][Kp0 / 16][64]
-  int dof_nt;
-  int64_t mpad;     // rows rounded up to the fused kernels' tile height
-  GemmTNFragGroup tnf_group;
   // side streams to join into the flushing stream right behind the GEMM launch: the barrier packets (~10 us each even when
   // the event fired long ago) are then processed while the GEMMs run instead of at the end of the call
   hipStream_t join_s[2];
@@ -415,13 +397,14 @@ struct MlpBufs {  // activations of one network for M rows
   float* lowrank;  // [out_dim][H] T = d_out^T . act(z1) of the top block (see lowrank_dw_kernel)
   float* lowrank_u;  // [out_dim][Kp0] U = d_out^T . x (merged-top networks: dWout is rebuilt from U and T, see PostReduce)
   bool merged;       // this network's forward ran merged (fused_can_merge): h_nb was never stored
-  bool post_zeroed;      // the caller's row builder zeroed post_counter in this call
+  bool post_zeroed;      // the caller's row builder zeroed post_counter and tail_counter in this call
   double* post_counter;  // 8 zeroed bytes: arrival counter of post_reduce_kernel (zeroed by the row builder, left zero)
+  unsigned* tail_counter;  // the 8 bytes right behind it (zeroed with it): arrival counter of tail_post_kernel's thin reductions
   size_t slab_floats, part_floats;
 };
 
 constexpr int REDUCE_BLOCKS = 256;
-constexpr int RED_CNT = 192;  // tile counters of the folded slab reduction: with post_counter 97 doubles, one row-builder zero array
+constexpr int POST_COUNTER_DOUBLES = 2;  // post_counter and tail_counter: one row-builder zero array
 
 static bool lowrank_top(const dppo_net_desc& d, int64_t M);
 // the one-block backward kernel writes no dh_nb tensor: it needs the low-rank dW2
@@ -442,13 +425,12 @@ static void carve_mlp(Carver& c, const dppo_net_desc& d, int64_t M, bool keep, b
   float* hbuf[MAX_BLOCKS + 1];
   for (int i = 0; i < nh; ++i) hbuf[i] = (float*)c.take((size_t)M * H * 4);
   for (int b = 0; b <= nb; ++b) B.h[b] = keep ? hbuf[b] : hbuf[b & 1];
-  const size_t Mp = (size_t)round_up((int)M, 128);  // (fragment mode writes whole tiles of up to 128 rows)
   void* a1s = nullptr;
   void* a2s = nullptr;
   for (int b = 0; b < nb; ++b) {
     if (keep || b == 0) {
-      a1s = c.take(Mp * H * ES);
-      a2s = c.take(Mp * H * ES);
+      a1s = c.take((size_t)M * H * ES);
+      a2s = c.take((size_t)M * H * ES);
     }
     B.a1[b] = a1s;
     B.a2[b] = a2s;
@@ -472,14 +454,12 @@ static void carve_mlp(Carver& c, const dppo_net_desc& d, int64_t M, bool keep, b
   if (bwd) {
     B.d_out = c.take((size_t)M * Kpo * ES);
     B.dh = c.take((size_t)M * H * ES);
-    B.dz1 = c.take(Mp * H * ES);
+    B.dz1 = c.take((size_t)M * H * ES);
     B.dh_all[nb] = B.dh;
     for (int b = 0; b < nb; ++b) {
-      B.dh_all[b] = c.take(Mp * H * ES);
+      B.dh_all[b] = c.take((size_t)M * H * ES);
       B.dz1_all[b] = b == 0 ? B.dz1 : c.take((size_t)M * H * ES);
     }
-    B.doutf = (u32x4*)c.take(Mp * 64 * 2);  // up to four feature tiles of d_out
-    B.xf = (u32x4*)c.take(Mp * Kp0 * 2);
     const int mt = d.plain || d.out_dim > 128 ? 0 : fused_rows_per_tile<P>(d, bwd_one<P>(d, M));
     B.tiles = mt > 0 ? (int)((M + mt - 1) / mt) : 0;
     B.tile_colsum = (float*)c.take((size_t)(2 * nb + 2 + (d.use_layernorm ? 4 * nb : 0)) * (B.tiles > 0 ? B.tiles : 1) * H * 4);
@@ -497,8 +477,8 @@ static void carve_mlp(Carver& c, const dppo_net_desc& d, int64_t M, bool keep, b
     B.part = (float*)c.take(B.part_floats * 4);
     B.lowrank = (float*)c.take((size_t)round_up(d.out_dim, 16) * H * 4);
     B.lowrank_u = (float*)c.take((size_t)round_up(d.out_dim, 16) * Kp0 * 4);
-    B.post_counter = (double*)c.take(8 + RED_CNT * 4);
-    B.red_cnt = (unsigned*)(B.post_counter + 1);
+    B.post_counter = (double*)c.take(POST_COUNTER_DOUBLES * 8);
+    B.tail_counter = (unsigned*)(B.post_counter + 1);
     B.post_zeroed = false;
     B.w0T = c.take((size_t)round_up(d.cond_dim > 0 ? d.cond_dim : 1, 16) * H * ES);
     B.dobs = (float*)c.take((size_t)M * round_up(d.cond_dim > 0 ? d.cond_dim : 1, 16) * 4);
@@ -537,8 +517,7 @@ static void cond_encode(const dppo_net_desc& d, const float* prm, const char* pk
 
 template <class P>
 static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
-                        MlpBufs<P>& B, bool keep, hipStream_t s, const LossArgs* fuse_loss = nullptr) {
-  // fuse_loss: the policy half of the PPO loss in the forward kernel's epilogue (fuse_loss_ok() held: the merged fused kernel runs)
+                        MlpBufs<P>& B, bool keep, hipStream_t s) {
   const ParamLayout pl = param_layout(d);
   const int H = d.hidden, nb = d.n_blocks;
   if (fused_ok<P>(d)) {
@@ -568,21 +547,7 @@ static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk
       f.ostream0 = (const u32x4*)(pk + L.ostream0), f.ostream2 = (const u32x4*)(pk + L.ostream2);
       f.cbias2 = (const float*)(pk + L.cbias2);
     }
-    B.frag = keep && B.allow_frag && B.merged;
-    if (B.frag) {  // act(h_0), act(z1) as K-major fragments, in place of the row-major tensors (frag_ok())
-      const int mt = fused_rows_per_tile<P>(d, true);
-      B.mpad = (M + mt - 1) / mt * mt;
-      f.a1f = (u32x4*)B.a1[0], f.a2f = (u32x4*)B.a2[0];
-    }
-    if (fuse_loss != nullptr && (!B.merged || B.frag)) {
-      g_fused_fault = -8;  // (fuse_loss_ok() and this function disagree)
-      return;
-    }
-    g_fused_fault = launch_fused_forward<P>(d, f, s, fuse_loss);
-    return;
-  }
-  if (fuse_loss != nullptr) {
-    g_fused_fault = -8;
+    g_fused_fault = launch_fused_forward<P>(d, f, s);
     return;
   }
   if (d.plain) {  // x -> act(W0 x) -> act(W_b .) ... -> Wout .   (pre-activations kept for the backward: hpre[0], z1[b])
@@ -638,11 +603,9 @@ static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk
 // through events: legal under stream capture too.  Tuning knob 2 turns it off (one stream, for per-kernel timing).
 //   side 0: the critic pipeline of a PPO update;  side 1: the bias / time-embedding gradient tail of the actor
 static int g_overlap = 1;
-static int g_gate_critic = 0;  // tuning knob 10: measured 77 -> 74 M samples/s when on (letting the critic run ahead alone is better)
-static int g_side_low_priority = 0;  // read when a side stream is first created
 struct SideStream {
   hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr, gate = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
   bool ok = false;
 };
 static SideStream* side_stream(int idx) {
@@ -651,19 +614,9 @@ static SideStream* side_stream(int idx) {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   SideStream& t = tab[dev][idx];
   if (!t.ok) {
-    // tuning knob 9 = 1 creates the side streams at the lowest priority, so that the caller's stream (the actor pipeline,
-    // the longer one) would never wait for CUs.  Measured: 77 -> 46 M samples/s -- a low-priority queue is starved far
-    // beyond the intent, so the default is equal priority and first come, first served.
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (g_side_low_priority) {
-      if (hipStreamCreateWithPriority(&t.s, hipStreamNonBlocking, least) != hipSuccess) return nullptr;
-    } else if (hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking) != hipSuccess) {
-      return nullptr;
-    }
+    if (hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
     if (hipEventCreateWithFlags(&t.fork, hipEventDisableTiming) != hipSuccess) return nullptr;
     if (hipEventCreateWithFlags(&t.join, hipEventDisableTiming) != hipSuccess) return nullptr;
-    if (hipEventCreateWithFlags(&t.gate, hipEventDisableTiming) != hipSuccess) return nullptr;
     t.ok = true;
   }
   return &t;
@@ -677,13 +630,6 @@ static hipStream_t fork_side(hipStream_t main, int idx = 0) {  // returns the st
   (void)hipEventRecord(t->fork, main);
   (void)hipStreamWaitEvent(t->s, t->fork, 0);
   return t->s;
-}
-// the side stream's next kernel does not start before everything enqueued on `main` so far has finished
-static void gate_side(hipStream_t main, hipStream_t sidestream, int idx = 0) {
-  if (sidestream == main) return;
-  SideStream* t = side_stream(idx);
-  (void)hipEventRecord(t->gate, main);
-  (void)hipStreamWaitEvent(sidestream, t->gate, 0);
 }
 static void join_side(hipStream_t main, hipStream_t sidestream, int idx = 0) {
   if (sidestream == main) return;
@@ -706,17 +652,6 @@ static int g_lowrank_ratio = 100;
 static bool lowrank_top(const dppo_net_desc& d, int64_t M) {
   return g_lowrank_top && d.n_blocks >= 1 && M >= (int64_t)g_lowrank_ratio * d.out_dim;
 }
-// tuning knob 31: K-major fragment operands for the weight-gradient GEMMs of one-block bf16 networks.  OFF by default: parity
-// green (tests/test_hip_parity.py, knob 31 cases) but not faster yet -- 114-118 us for the step's two launches against 107 with
-// the transposing kernel (DESIGN.md section 13 has the knock-out measurements: 43 us skeleton + 52 us HBM stream + 23 us ring,
-// adding up instead of overlapping)
-static int g_frag = 0;
-// tuning knob 35: slab reductions folded into the grouped weight-gradient GEMM launch (no tail_reduce launch).  OFF by default:
-// correct (160 parity tests with it on) but slower -- the launch goes from 107 to 200 us per step (both networks): a tile's LAST
-// workgroup sums splits x 64 KB alone (1 MB for an H x H tile, 16 such workgroups at the very end of the launch, each at one
-// CU's ~25 GB/s), where tail_reduce_kernel puts the whole chip on the same 22 MB for 17 us.  (With release / acquire fences
-// instead of sc1 stores it was 589 us: buffer_wbl2 flushes the XCD's whole L2 once per wave.)
-static int g_fold = 0;
 static int g_mom_rider = 0;  // tuning knob 36: the minibatch's advantage moments as riders of the row builder (1: always, 2: never) or a launch
                               // of their own.  0 (default): riders for minibatches of at most MOM_RIDER_MAX_N samples -- at N = 50,000 the
                               // launch already hides under the critic's forward on the side stream (the riders save 3.5 us only in the
@@ -733,21 +668,6 @@ static int temb_onehot_col(const dppo_net_desc& d, const PackLayout& L, int Kft,
   if (d.cond_out > 0 && d.cond_out % 16) return -1;  // the encoder's epilogue zero-fills up to a multiple of 16 columns
   if (L.Kp0 - d.in_dim < Kft || (size_t)(d.hidden + d.time_dim) * Kft > B.part_floats) return -1;
   return d.in_dim;
-}
-// May this network's whole training pass run in fragment mode?  Everything the forward, the backward and the GEMM group
-// will decide later must already hold: merged forward, one-block backward (hence the low-rank dW2), grouped GEMM launch, the
-// time-embedding gradient through the one-hot columns (the row-major dh_0 has no other reader then), no cond_mlp encoder
-// (its backward reads dh_0 row-major), the caller wants no d loss / d observation, and the backward's LDS holds the extras.
-template <class P>
-static bool frag_ok(const dppo_net_desc& d, int64_t M, const PackLayout& L, int Kft, const MlpBufs<P>& B, bool wants_dobs) {
-  if (!g_frag || P::ESIZE != 2 || wants_dobs || d.cond_hidden > 0 || !fused_frag_shape(d) || !g_tn_group) return false;
-  if (!fused_ok<P>(d) || B.tiles <= 0 || !fused_can_merge<P>(d) || !bwd_one<P>(d, M)) return false;
-  if (d.kind == 0 && temb_onehot_col<P>(d, L, Kft, B) < 0) return false;
-  const int mt = fused_rows_per_tile<P>(d, true);
-  const FusedGeom fg = fused_geom<P>(d);
-  if (L.Kp0 % 16 || L.Kp0 > 128) return false;
-  return (size_t)mt * ((size_t)fg.KpB0 * 2 + (size_t)L.Kp0 * 2) + (size_t)SAMPLER_WAVES * 32 * 32 * (d.hidden / 128) <=
-         (size_t)mt * d.hidden * 2;
 }
 // In-kernel first-layer weight gradient (tuning knob 37; fused.h, FusedBwdArgs::dw0_slab).  dh_0 -- a third of the bytes the
 // weight-gradient GEMMs read, for a 512 x 64 output -- is then neither stored nor read back: the one-block backward multiplies each
@@ -766,38 +686,10 @@ static int g_dw0 = 1;
 // under the GEMM launch, with the bias sums and the loss statistics, and only the GEMMs' own slabs, the low-rank dW2 and dWout
 // stay behind the GEMMs on the caller's stream.
 static int g_side_tail = 1;
-// Tuning knob 40: ... and instead of a side stream (whose fork is an event record between the backward kernel and the GEMM launch
-// on the caller's stream: ~8 us of idle time there, profiles/r03_dw0_ab.txt) the same work RIDES in the actor's GEMM launch as extra
-// workgroups in front of the GEMM tiles (gemm.h, GemmTNExtra): producers (slab reductions, bias sums, loss statistics) first, then
-// the time-embedding blocks, which wait for the producers on an arrival counter (post_blocks.h).  No stream, no event, no launch.
-// OFF by default: parity green on the first run, but the actor's GEMM launch goes from 68 to 94 us (serial) and the step from 0.350
-// to 0.381 ms -- the riders' dependent chain (reduce, G, the time MLP's backward: latency-bound steps) runs under the GEMM's memory
-// load, every step of it several times slower than alone, and the launch cannot end before it does; on its own stream the same chain
-// is as slow but nobody waits for it (profiles/r03_dw0_ab.txt).
-static int g_tail_riders = 0;
 // Tuning knob 41: with knob 38, what is left behind the actor's GEMMs -- their slab reductions, then the low-rank dW2 / dWout / db2,
 // which read only the two THIN products -- is ONE launch (tail_post_kernel: the thin products' reduce blocks first, the dependent
 // blocks poll their arrival, the big slabs are reduced beside them) instead of two.
 static int g_tail_post = 1;
-// Tuning knob 39: the policy half of the PPO loss in the epilogue of the actor's fused forward (loss_dev.h; fused.hip, LOSSF): no
-// loss launch between the actor's forward and backward, the forward's eps tile never goes to HBM.  bf16 one-block actor on the
-// merged forward with 64-row tiles (hidden 512), a head of at most 16 outputs whose reward-horizon part is a multiple of 4 wide,
-// the two pipelines on two streams (the value half stays a launch on the critic's), the row builder's loss table, no riders.
-// OFF by default: parity green (ratio == 1 bit for bit, tests/test_hip_parity.py knob 39), step time EQUAL to the separate launch's.
-// At first it was 16 us slower: the variant allocated 235 VGPRs where the plain forward has 223, two waves of it left a SIMD 32 free
-// registers instead of 64, and the critic's value-loss launch could no longer slip a wave in beside the actor's persistent
-// workgroups (13 -> 80 us: its whole pipeline started that much later).  Capped at 224 (`amdgpu_num_vgpr(112)`: hipcc doubles the
-// request on the unified register file; eight cold values go to scratch) that is gone -- and what remains is a wash: the forward's
-// epilogue (one wave walks the tile's 64 samples, seven wait) costs what the launch cost (profiles/r03_fused_loss_ab.txt).
-static int g_fuse_loss = 0;
-template <class P>
-static bool fuse_loss_ok(const dppo_net_desc& d, const LossArgs& la, const MlpBufs<P>& B, bool two_streams, bool mom_rider) {
-  if (!g_fuse_loss || P::ESIZE != 2 || !two_streams || mom_rider || B.allow_frag || !fused_ok<P>(d) || !fused_loss_shape(d)) return false;
-  const dppo_ppo_cfg& pc = la.pcfg;
-  const int rh = pc.reward_horizon < pc.horizon_steps ? pc.reward_horizon : pc.horizon_steps, cnt = rh * pc.action_dim;
-  if (la.tab == nullptr || pc.ft_denoising_steps > 64 || cnt > 16 || cnt <= 0) return false;
-  return ((la.AF | cnt) & 3) == 0 && la.AF <= 16 && la.ldde % 8 == 0 && la.ldde >= 16;
-}
 static int dw0_cols(const dppo_net_desc& d) { return d.kind == 0 ? d.act_flat + d.cond_dim : d.in_dim; }
 static int dw0_nhot(const dppo_net_desc& d, int Kft) {  // one-hot columns that fit behind the data columns
   const int room = 32 - dw0_cols(d);
@@ -821,8 +713,7 @@ static void flush_slabs(MlpBufs<P>& B, hipStream_t s, const SlotOuts* slots = nu
                         const LossArgs* fin = nullptr, bool defer_reduce = false) {
   // defer_reduce: launch the GEMMs (and join the side streams) but leave the slab jobs to the caller (tail_post_kernel)
   // slots / fin: the fused backward's per-tile column sums and the loss statistics ride in the reduction launch (see
-  // tail_reduce_kernel) -- or, with the folded tail, in the GEMM launch itself, and there is no reduction launch
-  bool folded = false;
+  // tail_reduce_kernel)
   if (B.tn_group.n > 0) {
     GemmTNGroup& gr = B.tn_group;
     for (int i = 1; i < gr.n; ++i)  // longest row ranges first (insertion sort: the short jobs fill the last round)
@@ -831,81 +722,11 @@ static void flush_slabs(MlpBufs<P>& B, hipStream_t s, const SlotOuts* slots = nu
         gr.j[k] = gr.j[k - 1], gr.j[k - 1] = t;
       }
     gr.base[0] = 0;
-    int tiles_total = 0;
     for (int i = 0; i < gr.n; ++i) {
       const int tiles = ((gr.j[i].N1 + 127) / 128) * ((gr.j[i].N2 + 127) / 128);
       gr.base[i + 1] = gr.base[i] + gr.j[i].splits * tiles;
-      tiles_total += tiles;
     }
-    memset(&gr.ex, 0, sizeof(gr.ex));
-    // Folded tail: possible when this flush reduces exactly this group's slabs (no GEMM was launched outside the group since
-    // the last flush) and the caller's row builder zeroed the tile counters
-    int n_group_slabs = 0;
-    for (int i = 0; i < gr.n; ++i) n_group_slabs += gr.j[i].red_n2a >= 0 ? 2 : 1;
-    folded = g_fold && B.fold && (slots != nullptr || fin != nullptr) && tiles_total <= RED_CNT &&
-             n_group_slabs == B.slab_jobs.n && !(g_dbg & 28) && (slots == nullptr || slots->n_slots <= TN_MAX_SLOTS);
-    if (folded) {
-      int cnt0 = 0;
-      for (int i = 0; i < gr.n; ++i) {
-        gr.j[i].red_cnt = B.red_cnt + cnt0;
-        cnt0 += ((gr.j[i].N1 + 127) / 128) * ((gr.j[i].N2 + 127) / 128);
-      }
-      GemmTNExtra& e = gr.ex;
-      if (slots != nullptr && slots->n_slots > 0) {
-        e.colsum = B.tile_colsum, e.tiles = B.tiles, e.width = slot_width, e.n_slots = slots->n_slots;
-        e.slot_bx = (slot_width + 15) / 16, e.n_slot_blocks = e.n_slots * e.slot_bx;
-        for (int i = 0; i < slots->n_slots; ++i) e.slot_out[i] = slots->out[i], e.slot_n[i] = slots->n[i];
-      }
-      if (fin != nullptr && fin->N > 0) {
-        e.fin_partial = fin->partial, e.fin_blocks = loss_blocks(fin->N), e.fin_moments = fin->moments, e.fin_stats = fin->stats;
-        e.fin_part = fin->part, e.fin_n_count = fin->n_count;
-      }
-      e.n_blocks = (e.n_slot_blocks + (e.fin_stats != nullptr ? 1 : 0) + 7) / 8 * 8;  // (keeps the GEMM tiles' block id = XCD map)
-    } else {
-      for (int i = 0; i < gr.n; ++i) gr.j[i].red_cnt = nullptr;
-      if (B.ride) {  // the backward kernel's own reductions and the time-embedding gradient as riders (knob 40)
-        GemmTNExtra& e = gr.ex;
-        const TailReduce& t = B.ride_t;
-        e.colsum = t.colsum, e.tiles = t.tiles, e.width = t.width, e.n_slots = t.slots.n_slots;
-        e.slot_bx = (t.width + 15) / 16, e.n_slot_blocks = e.n_slots * e.slot_bx;
-        for (int i = 0; i < e.n_slots; ++i) e.slot_out[i] = t.slots.out[i], e.slot_n[i] = t.slots.n[i];
-        if (t.fin_stats != nullptr) {
-          e.fin_partial = t.fin_partial, e.fin_blocks = t.fin_blocks, e.fin_moments = t.fin_moments, e.fin_stats = t.fin_stats;
-          e.fin_part = t.fin_part, e.fin_n_count = t.fin_n_count;
-        }
-        int n_prod = e.n_slot_blocks + 1;
-        e.n_rjobs = t.jobs.n;
-        for (int i = 0; i < t.jobs.n; ++i) {
-          e.rjob[i] = t.jobs.j[i];
-          e.rjob_blocks[i] = (int)(((size_t)t.jobs.j[i].rows * t.jobs.j[i].cols + 15) / 16);  // (16 elements per block: slab_job_rider)
-          n_prod += e.rjob_blocks[i];
-        }
-        e.post = B.ride_q;
-        int n_cons = 0;
-        if (e.post.G != nullptr) {
-          e.arrive_cnt = B.red_cnt + RED_CNT - 1;  // (zeroed by the row builder with the post-reduce counter: B.post_zeroed)
-          e.post.wait_cnt = e.arrive_cnt, e.post.wait_need = n_prod;
-          e.post.n_temb = (e.post.Kft * e.post.td + 3) / 4, e.post.n_dw0t = (e.post.H * e.post.td + 255) / 256;
-          e.post.n_lowrank = e.post.n_wout = 0;
-          n_cons = e.post.n_temb + e.post.n_dw0t;
-        }
-        e.n_blocks = (n_prod + n_cons + 7) / 8 * 8;
-      }
-    }
-    B.ride = false;
     launch_gemm_tn_group<P>(gr, s);
-    gr.n = 0;
-  }
-  if (B.tnf_group.n > 0) {  // fragment-operand jobs (weight_grad_frag): same order rule, same single launch
-    GemmTNFragGroup& gr = B.tnf_group;
-    for (int i = 1; i < gr.n; ++i)
-      for (int k = i; k > 0 && (int64_t)gr.j[k].ks_per_split * gr.j[k].tb > (int64_t)gr.j[k - 1].ks_per_split * gr.j[k - 1].tb; --k) {
-        const GemmTNFrag t = gr.j[k];
-        gr.j[k] = gr.j[k - 1], gr.j[k - 1] = t;
-      }
-    gr.base[0] = 0;
-    for (int i = 0; i < gr.n; ++i) gr.base[i + 1] = gr.base[i] + gemm_tn_frag_blocks(gr.j[i]);
-    launch_gemm_tn_frag_group(gr, B.mpad, s);
     gr.n = 0;
   }
   // One wait on the caller's stream however many side streams there are: the earlier ones are joined into the LAST one (their
@@ -914,10 +735,8 @@ static void flush_slabs(MlpBufs<P>& B, hipStream_t s, const SlotOuts* slots = nu
   for (int i = 0; i + 1 < B.n_join; ++i) join_side(B.join_s[B.n_join - 1], B.join_s[i], B.join_idx[i]);
   if (B.n_join > 0) join_side(s, B.join_s[B.n_join - 1], B.join_idx[B.n_join - 1]);
   B.n_join = 0;
-  if (defer_reduce && !folded) return;
-  if (folded) {
-    // everything a reduction launch would do has been done by the GEMM launch
-  } else if (slots != nullptr || fin != nullptr) {
+  if (defer_reduce) return;
+  if (slots != nullptr || fin != nullptr) {
     TailReduce t;
     memset(&t, 0, sizeof(t));
     t.jobs = B.slab_jobs;
@@ -947,7 +766,7 @@ static void weight_grad(const void* A, int lda, int N1, const void* Bm, int ldb,
   }
   const bool group = defer && g_tn_group;  // launched with the caller's other GEMMs, 128 x 128 tiles throughout
   const bool thin = !group && gemm_tn_thin(N1, N2);
-  const size_t N1s = (size_t)round_up(N1, 4);  // (the folded reduction's transposed slabs pad N1 to whole 16-byte pieces)
+  const size_t N1s = (size_t)round_up(N1, 4);  // (every sub-slab of the pool starts on a 16-byte boundary)
   const size_t tiles = thin ? (size_t)((N1 + 511) / 512) : (size_t)((N1 + 127) / 128) * ((N2 + 127) / 128);
   int64_t splits = (g_tn_target + tiles - 1) / tiles;
   const int64_t max_splits = (M + 63) / 64;
@@ -968,9 +787,6 @@ static void weight_grad(const void* A, int lda, int N1, const void* Bm, int ldb,
   float* sub = B.slab + B.slab_used;
   B.slab_used += (size_t)splits * N1s * N2;
   t.slab = sub, t.ldc = N2, t.splits = (int)splits, t.rows_per_split = (int)rps;
-  // (the folded reduction of flush_slabs(): where this product goes -- exactly what the SlabJob(s) below say)
-  t.red_out = gw, t.red_ldo = ldgw, t.red_transpose = swap ? 1 : 0, t.red_n2a = (n2a >= 0 && !swap) ? n2a : -1;
-  t.red_out2 = gw2, t.red_ldo2 = ldgw2;
   if (group)
     B.tn_group.j[B.tn_group.n++] = t;
   else
@@ -985,54 +801,6 @@ static void weight_grad(const void* A, int lda, int N1, const void* Bm, int ldb,
     j2.out = gw2, j2.ldo = ldgw2, j2.c0 = n2a, j2.cols = N2 - n2a;
   }
   if (!defer) flush_slabs(B, s);  // deferred: the caller flushes once after its last GEMM (same stream)
-}
-
-// The same contraction from K-major fragment operands (gemm.h, GemmTNFrag): gw[N1][N2] = FA^T . FB over the batch rows,
-// FA / FB with nta / ntb feature tiles per k-step; always deferred to the caller's flush.  transpose: gw receives the
-// transposed result (the thin side of a thin product is passed as B, the wide one as A: a wave's tile is 64 x 16 tb).
-template <class P>
-static void weight_grad_frag(const u32x4* FA, int nta, int N1, const u32x4* FB, int ntb, int N2, MlpBufs<P>& B, float* gw,
-                             int ldgw, hipStream_t s, bool transpose = false, int n2a = -1, float* gw2 = nullptr,
-                             int ldgw2 = 0) {
-  GemmTNFrag t;
-  memset(&t, 0, sizeof(t));
-  t.A = FA, t.B = FB, t.nta = nta, t.ntb = ntb, t.N1 = N1, t.N2 = N2;
-  if (!gemm_tn_frag_prepare(t)) {  // (frag_ok() admits only shapes the kernel covers: H <= 512, Kp0 <= 128)
-    g_fused_fault = -6;
-    return;
-  }
-  const int nba = (N1 + 63) / 64, nbb = (N2 + 16 * t.tb - 1) / (16 * t.tb);
-  const int64_t wg_tiles = (int64_t)((nba + t.wga - 1) / t.wga) * ((nbb + t.wgb - 1) / t.wgb);
-  t.ks_total = (int)(B.mpad / 32);
-  // workgroups a job aims for: the chip's CUs for the H x H class, half that for the thin ones (their waves carry a
-  // quarter of the MFMAs per k-step and each split costs a slab)
-  const int64_t target = (int64_t)N1 * N2 >= 128 * 128 ? g_tn_target : g_tn_target / 2;
-  int64_t splits = (target + wg_tiles - 1) / wg_tiles;
-  const int64_t max_splits = t.ks_total >= 2 ? t.ks_total / 2 : 1;
-  if (splits > max_splits) splits = max_splits;
-  if (splits > g_tn_max_splits) splits = g_tn_max_splits;
-  if (splits < 1) splits = 1;
-  if ((size_t)splits * N1 * N2 > B.slab_floats - B.slab_used || B.slab_jobs.n + 2 > MAX_SLAB_JOBS ||
-      B.tnf_group.n >= MAX_TN_JOBS)
-    flush_slabs(B, s);
-  while (splits > 1 && (size_t)splits * N1 * N2 > B.slab_floats) --splits;
-  if (splits >= 8) splits = splits / 8 * 8;  // a multiple of the XCD count keeps one split's tiles on one XCD
-  int64_t kps = (t.ks_total + splits - 1) / splits;
-  const int64_t need = (t.ks_total + kps - 1) / kps;
-  if (need < splits) splits = need >= 8 ? (need + 7) / 8 * 8 : need;  // surplus splits see no k-steps and store zeros
-  float* sub = B.slab + B.slab_used;
-  B.slab_used += (size_t)splits * N1 * N2;
-  t.slab = sub, t.ldc = N2, t.splits = (int)splits, t.ks_per_split = (int)kps;
-  B.tnf_group.j[B.tnf_group.n++] = t;
-  SlabJob& j = B.slab_jobs.j[B.slab_jobs.n++];
-  j.slab = sub, j.out = gw, j.splits = (int)splits, j.rows = N1, j.cols = N2, j.lds = N2, j.ldo = ldgw, j.transpose = transpose ? 1 : 0;
-  j.c0 = 0, j.wide = 0;
-  if (n2a >= 0 && !transpose) {
-    j.cols = n2a;
-    SlabJob& j2 = B.slab_jobs.j[B.slab_jobs.n++];
-    j2 = j;
-    j2.out = gw2, j2.ldo = ldgw2, j2.c0 = n2a, j2.cols = N2 - n2a;
-  }
 }
 
 // d temb = dh0 . W0[:, temb columns]; summed per fine-tuned step; back through the tiny time MLP
@@ -1114,18 +882,8 @@ static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* p
     if (g_dbg & 32) f.dh[0] = nullptr;  // timing experiment: dh_0 is not stored (bound of the in-kernel dW0)
     if (g_dbg & 2)  // timing experiment: no derivative-source fetch
       for (int b = 0; b < nb; ++b) f.m1[b] = f.m0[b] = nullptr;
-    const bool frag = B.frag;
-    if (frag) {  // (frag_ok() held when the forward ran: one-block kernel, one-hot time columns, ...)
-      if (!one || !B.merged || !lowrank) {
-        g_fused_fault = -5;
-        return;
-      }
-      B.dof_nt = d.out_dim <= 16 ? 1 : (d.out_dim <= 32 ? 2 : 4);
-      f.dz1f = (u32x4*)B.dz1_all[0], f.dh0f = (u32x4*)B.dh_all[0], f.doutf = B.doutf, f.dof_nt = B.dof_nt;
-      f.x = B.in, f.ld_x = L.Kp0, f.xf = B.xf;
-    }
     // in-kernel dW0 (dw0_ok() held when the rows were built): a slab per workgroup out of the pool, reduced with the GEMMs' slabs
-    const bool dw0 = B.dw0 && one && !frag && !(g_dbg & 33);
+    const bool dw0 = B.dw0 && one && !(g_dbg & 33);
     const int dw0_nh = dw0 ? dw0_nhot(d, Kft) : 0;
     float* dw0_slab = nullptr;
     int dw0_grid = 0;
@@ -1181,19 +939,6 @@ static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* p
                              B.post_zeroed && !(g_dbg & 28);
       TailReduce side_t;
       memset(&side_t, 0, sizeof(side_t));
-      if (frag) {  // the same four products from fragment operands (one block, merged, low-rank: see frag_ok())
-        const int ntx = L.Kp0 / 16, nth = H / 16;
-        // U^T = x^T . d_out  [in_dim][out_dim] -> lowrank_u [out_dim][Kp0]
-        weight_grad_frag<P>(B.xf, ntx, d.in_dim, B.doutf, B.dof_nt, d.out_dim, B, B.lowrank_u, L.Kp0, s, true);
-        // T^T = act(z1)^T . d_out  [H][out_dim] -> lowrank [out_dim][H]
-        weight_grad_frag<P>((const u32x4*)B.a2[0], nth, H, B.doutf, B.dof_nt, d.out_dim, B, B.lowrank, H, s, true);
-        weight_grad_frag<P>((const u32x4*)B.dz1_all[0], nth, H, (const u32x4*)B.a1[0], nth, H, B, grad + pl.l1w[0], H, s);
-        if (oh >= 0)
-          weight_grad_frag<P>((const u32x4*)B.dh_all[0], nth, H, B.xf, ntx, d.in_dim + Kft, B, grad + pl.W0, d.in_dim, s, false,
-                              d.in_dim, B.part, Kft);
-        else
-          weight_grad_frag<P>((const u32x4*)B.dh_all[0], nth, H, B.xf, ntx, d.in_dim, B, grad + pl.W0, d.in_dim, s);
-      } else {
       if (merged)
         weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.in, L.Kp0, d.in_dim, M, B, B.lowrank_u, L.Kp0, s, true);
       else
@@ -1224,24 +969,12 @@ static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* p
                        Kft);
       else
         weight_grad<P>(B.dh_all[0], H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s, true);
-      }
-      // ... as riders of the GEMM launch (knob 40): needs the grouped launch to exist and take them (three wide jobs, the time MLP's
-      // LDS within the GEMM's own, no folded reduction), else the side stream
-      const bool riders = side_tail && g_tail_riders && !g_fold && B.tn_group.n > 0 && side_t.jobs.n <= 3 && so.n_slots <= TN_MAX_SLOTS &&
-                          time_backward_lds_bytes(Kft, d.time_dim) <= 32 * 1024;
       if (side_tail) {
         // what the backward kernel alone feeds: its dW0 slabs, the bias sums, the loss statistics, then the time-embedding
         // gradient -- queued on the side stream here, BEHIND the kernel and BESIDE the GEMM launch that follows on s
-        hipStream_t st = riders ? s : fork_side(s, aux_idx);
+        hipStream_t st = fork_side(s, aux_idx);
         side_t.colsum = B.tile_colsum, side_t.tiles = B.tiles, side_t.width = H, side_t.slots = so;
-        if (riders) {
-          if (fin != nullptr && fin->N > 0) {
-            side_t.fin_partial = fin->partial, side_t.fin_blocks = loss_blocks(fin->N), side_t.fin_moments = fin->moments;
-            side_t.fin_stats = fin->stats, side_t.fin_part = fin->part, side_t.fin_n_count = fin->n_count;
-          }
-        } else {
-          launch_tail_reduce(side_t, fin, st);
-        }
+        launch_tail_reduce(side_t, fin, st);
         PostReduce qs;
         memset(&qs, 0, sizeof(qs));
         qs.H = H, qs.out_dim = d.out_dim;
@@ -1250,15 +983,11 @@ static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* p
         qs.ksteps = ksteps, qs.gw1 = grad + pl.te1_w, qs.gb1 = grad + pl.te1_b, qs.gw2 = grad + pl.te2_w, qs.gb2 = grad + pl.te2_b;
         qs.S_rest = s_rest, qs.dW0t = grad + pl.W0, qs.temb = (const float*)(pk + L.temb), qs.temb_bf16 = P::ESIZE == 2 ? 1 : 0;
         qs.counter = (unsigned*)B.post_counter;
-        if (riders) {
-          B.ride = true, B.ride_t = side_t, B.ride_q = qs;  // (flush_slabs hands them to the group launch)
-        } else {
-          launch_post_reduce(qs, st);
-          B.join_s[B.n_join] = st, B.join_idx[B.n_join++] = aux_idx;  // (joined right behind the GEMM launch: flush_slabs)
-        }
+        launch_post_reduce(qs, st);
+        B.join_s[B.n_join] = st, B.join_idx[B.n_join++] = aux_idx;  // (joined right behind the GEMM launch: flush_slabs)
       }
       if (aux != s && g_early_join) B.join_s[B.n_join] = aux, B.join_idx[B.n_join++] = aux_idx;
-      const bool tail_post = side_tail && g_tail_post && !g_fold && (lowrank || merged || one);
+      const bool tail_post = side_tail && g_tail_post && (lowrank || merged || one);
       if (tail_post)
         flush_slabs(B, s, nullptr, 0, nullptr, true);  // the GEMMs; their slabs are reduced with the post-reduce parts below
       else if (side_tail)
@@ -1298,7 +1027,7 @@ static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* p
               if (thin && pass == 0) ++tp.n_first_jobs;
             }
           tp.q = q;
-          tp.q.wait_cnt = B.red_cnt + RED_CNT - 2;  // (zeroed by the row builder: B.post_zeroed)
+          tp.q.wait_cnt = B.tail_counter;  // (zeroed by the row builder: B.post_zeroed)
           launch_tail_post(tp, s);
           B.slab_jobs.n = 0, B.slab_used = 0;
         } else {
@@ -1312,7 +1041,7 @@ static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* p
                                          d.act_flat, H, B.part + (size_t)H * Kft, ksteps, Kft, d.time_dim, grad + pl.te1_w,
                                          grad + pl.te1_b, grad + pl.te2_w, grad + pl.te2_b, s);
       }
-      B.dh0_final = frag || dw0 ? nullptr : B.dh_all[0];  // (fragment mode / in-kernel dW0: no row-major dh_0 exists; frag_ok() / dw0_ok() made sure nobody asks)
+      B.dh0_final = dw0 ? nullptr : B.dh_all[0];  // (in-kernel dW0: no dh_0 exists; dw0_ok() made sure nobody asks)
       return;
     }
   }
@@ -1987,8 +1716,6 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
   const PackLayout LA = pack_layout<P>(a, 0), LC = pack_layout<P>(cr, 0);
   const int Kft = pcfg.ft_denoising_steps;
-  W.A.allow_frag = frag_ok<P>(a, N, LA, Kft, W.A, oio && oio->d_obs_actor);
-  W.C.allow_frag = frag_ok<P>(cr, N, LC, Kft, W.C, oio && oio->d_obs_critic);
   // The critic pipeline (rows -> forward -> value loss -> backward -> weight gradients) and the actor pipeline (rows ->
   // advantage moments -> forward -> policy loss -> ...) share nothing but the call's inputs: one fork at entry, one join
   // at the end.  A cross-stream event hop costs 10-17 us of device idle time; at entry it hides behind the actor's row
@@ -1999,11 +1726,11 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   BuildRows br;
   memset(&br, 0, sizeof(br));
   br.zero_b = W.moments, br.n_zero_b = 32;  // zeroed by the row builder (every statistic has one owner launch that writes it)
-  // post_reduce_kernel's arrival counter and, behind it, the tile counters of the folded slab reduction (both networks')
-  br.zero_a = W.A.post_counter, br.n_zero_a = 1 + RED_CNT / 2, W.A.post_zeroed = true, W.A.fold = true;
-  br.zero_c = W.C.post_counter, br.n_zero_c = 1 + RED_CNT / 2, W.C.fold = true;
-  W.A.dw0 = !W.A.allow_frag && dw0_ok<P>(a, N, LA, Kft, W.A, oio && oio->d_obs_actor);
-  W.C.dw0 = !W.C.allow_frag && dw0_ok<P>(cr, N, LC, Kft, W.C, oio && oio->d_obs_critic);
+  // post_reduce_kernel's arrival counter and, behind it, tail_post_kernel's (both networks')
+  br.zero_a = W.A.post_counter, br.n_zero_a = POST_COUNTER_DOUBLES, W.A.post_zeroed = true;
+  br.zero_c = W.C.post_counter, br.n_zero_c = POST_COUNTER_DOUBLES;
+  W.A.dw0 = dw0_ok<P>(a, N, LA, Kft, W.A, oio && oio->d_obs_actor);
+  W.C.dw0 = dw0_ok<P>(cr, N, LC, Kft, W.C, oio && oio->d_obs_critic);
   if (Kft <= 1024) br.loss_tab = W.loss_tab, br.pcfg = pcfg;
   br.inds = inds, br.kinds = kinds, br.chains = chains_k, br.obs = obs_k, br.temb = (const float*)(ak + LA.temb);
   br.ksteps = ksteps;
@@ -2042,19 +1769,7 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   la.d_eps = W.A.d_out, la.ldde = LA.Kpo, la.d_v = W.C.d_out, la.lddv = LC.Kpo, la.stats = stats;
   const bool fuse_bout = false;  // out-layer bias gradients come from the fused backward's d_out column sums
   const bool two_streams = s2 != s;
-  // critic half.  (Knob 10 gates its first persistent kernel so that it becomes eligible together with the actor's instead
-  // of starting alone and taking every CU first; measured worse, off.)
-  const bool actor_first = split && g_gate_critic == 2;  // experiment: the critic's forward waits for the actor's
-  // the policy half of the loss in the actor forward's epilogue (knob 39): its arguments as the policy launch would get them
-  LossArgs lpol = la;
-  lpol.part = 1, lpol.partial = W.loss_partial;
-  const bool fuse_loss = fuse_loss_ok<P>(a, lpol, W.A, two_streams, mom_rider);
-  if (actor_first) {
-    mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s, fuse_loss ? &lpol : nullptr);
-    gate_side(s, s2);
-  } else if (split && g_gate_critic) {
-    gate_side(s, s2);
-  }
+  // critic half
   mlp_forward<P>(cr, cp, ck, LC, N, W.C, true, s2);
   if (two_streams) {
     la.part = 2, la.partial = W.loss_partial_v;
@@ -2072,9 +1787,9 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
     if (hook && hook->critic_grads_enqueued) hook->critic_grads_enqueued(hook->user, (dppo_stream_t)s2);
   }
   // actor half
-  if (!actor_first) mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s, fuse_loss ? &lpol : nullptr);
+  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
   la.part = two_streams ? 1 : 3, la.partial = W.loss_partial;
-  if (!fuse_loss) launch_ppo_loss<P>(la, s);
+  launch_ppo_loss<P>(la, s);
   if (!two_streams) {
     mlp_backward<P>(cr, cp, ck, LC, N, W.C, cgrad, nullptr, nullptr, 0, s, fuse_bout, -1);
     if (oio && oio->d_obs_critic) obs_grad<P>(cr, cp, N, W.C, oio->d_obs_critic, s);
@@ -2904,166 +2619,57 @@ int dppo_probe_collect_bytes(double* total_ms_host, int* launches_host, double* 
 }
 
 // ---- tuning / micro-benchmark hooks -------------------------------------------------------------------
+// experiments that were measured, lost and removed with their code: setting one is an error, not a no-op
+static int retired_knob(int knob) {
+  return fail(-1, "tuning knob %d is retired: the code it selected was removed (DESIGN.md section 13)", knob);
+}
 int dppo_tune_set(int knob, int value) {
-  if (knob == 0) {
-    set_gemm_nt_variant(value);
-    return 0;
-  }
-  if (knob == 1) {
-    g_use_fused = value;
-    return 0;
-  }
-  if (knob == 2) {
-    g_overlap = value;
-    return 0;
-  }
-  if (knob == 3 && value >= 1) {
-    g_tn_target = value;
-    return 0;
-  }
-  if (knob == 4 && value >= 1) {
-    g_tn_max_splits = value;
-    return 0;
-  }
-  if (knob == 5) {
-    set_gemm_tn_variant(value);
-    return 0;
-  }
-  if (knob == 6) {
-    set_gemm_tn_thin(value);
-    return 0;
-  }
-  if (knob == 7) {
-    set_fused_short_tiles(value);
-    return 0;
-  }
-  if (knob == 8) {
-    g_dbg = value;
-    return 0;
-  }
-  if (knob == 9) {
-    g_side_low_priority = value;
-    return 0;
-  }
-  if (knob == 10) {
-    g_gate_critic = value;
-    return 0;
-  }
-  if (knob == 11) {
-    g_temb_onehot = value;
-    return 0;
-  }
-  if (knob == 12) {
-    g_tn_group = value;
-    return 0;
-  }
-  if (knob == 13) {
-    g_pack_one = value;
-    return 0;
-  }
-  if (knob == 14) {
-    g_early_join = value;
-    return 0;
-  }
-  if (knob == 15) {
-    set_sampler_l0_lds(value);
-    return 0;
-  }
-  if (knob == 16) {
-    g_lowrank_top = value;
-    return 0;
-  }
-  if (knob == 17) {
-    g_merge_top = value;
-    return 0;
-  }
-  if (knob == 18) {
-    g_post_one = value;
-    return 0;
-  }
-  if (knob == 27) {  // sampler: one 16-row tile over eight workgroups for small env batches (1, default) or one (0)
-    set_sampler_split(value);
-    return 0;
-  }
-  if (knob == 28) {  // split sampler: 64-cycle sleep periods between a member's exchange store and its first sweep (default 4)
-    set_sampler_split_pre_sweep(value);
-    return 0;
-  }
-  if (knob == 31) {  // weight-gradient GEMMs of one-block bf16 networks from K-major fragment operands (1, default) or row-major (0)
-    g_frag = value;
-    return 0;
-  }
-  if (knob == 32) {  // fragment GEMM: 0 (default) LDS-ring kernel; 2..4 register-only kernel with that lookahead
-    set_gemm_tn_frag_depth(value);
-    return 0;
-  }
-  if (knob == 36) {  // advantage moments: partial sums by the row builder's last blocks, added up by the loss kernel (1, default) or adv_moments_kernel (0)
-    g_mom_rider = value;
-    return 0;
-  }
-  if (knob == 37) {  // in-kernel first-layer weight gradient of the one-block backward (1, default) or dh_0 stored and a GEMM of its own (0)
-    g_dw0 = value;
-    return 0;
-  }
-  if (knob == 38) {  // with knob 37: the reductions the backward kernel alone feeds and the time-embedding gradient on a side stream under the GEMMs (1, default)
-    g_side_tail = value;
-    return 0;
-  }
-  if (knob == 40) {  // with knob 38: that work as riders of the actor's weight-gradient GEMM launch (1) or on a side stream (0, default)
-    g_tail_riders = value;
-    return 0;
-  }
-  if (knob == 41) {  // with knob 38: the GEMMs' slab reductions and the post-reduce parts behind them in one launch (1, default) or two (0)
-    g_tail_post = value;
-    return 0;
-  }
-  if (knob == 39) {  // the policy half of the PPO loss in the epilogue of the actor's fused forward (1) or a launch of its own (0, default)
-    g_fuse_loss = value;
-    return 0;
-  }
-  if (knob == 35) {  // the reductions behind the weight-gradient GEMMs inside their launch (1, default) or as a launch of their own (0)
-    g_fold = value;
-    return 0;
-  }
-  if (knob == 34) {  // fragment GEMM, timing experiments (results are wrong while set): 1 no MFMAs, 2 no ring loads, 4 no prefetch
-    set_gemm_tn_frag_dbg(value);
-    return 0;
-  }
-  if (knob == 33) {  // fragment GEMM: k-steps its L2 prefetch runs ahead of the ring's own loads (default 12; 0: none ahead)
-    set_gemm_tn_frag_pfd(value);
-    return 0;
-  }
-  if (knob == 30 && value >= 1) {  // low-rank dW2 (knob 16) and with it the one-block backward: on for M >= value x out_dim (default 100)
-    g_lowrank_ratio = value;
-    return 0;
-  }
-  if (knob == 29) {  // split sampler: sweeps a member waits before giving up (tests force a time-out with 1; <= 0: default 2^20)
-    set_sampler_split_spin_limit(value);
-    return 0;
-  }
-  if (knob == 26) {  // grouped weight-gradient GEMM: LDS stages (1, default: three workgroups per CU; 2)
-    set_gemm_tn_nbuf(value);
-    return 0;
-  }
-  if (knob == 25) {  // one-block kernels: short layers walked without their padding k-steps (1, default) or padded (0)
-    set_fused_compact(value);
-    return 0;
-  }
-  if (knob == 23) {  // fused backward of one-block networks: the specialised kernel (1, default) or the general one (0)
-    set_fused_bwd_one(value);
-    return 0;
-  }
-  if (knob == 22) {  // fused forward of one-block networks: second layer merged into the out layer (1, default) or not (0);
-    set_fused_merge_fwd(value);  // takes effect at the next pack (the images of both forms are always packed)
-    return 0;
-  }
-  if (knob == 21) {  // gemm_nt: small tiles for small problems (1, default) or the 128 x 128 / 64 x 128 / 16 x 256 shapes only (0)
-    set_gemm_nt_small(value);
-    return 0;
-  }
-  if (knob == 20) {  // visual encoder: attention on the matrix cores (1, default) or the scalar kernels (0)
-    dppo::set_vis_mfma_attn(value);
-    return 0;
+  switch (knob) {
+    case 0: set_gemm_nt_variant(value); return 0;   // gemm_nt operand staging: LDS-DMA where legal (1, default) or through registers (0)
+    case 1: g_use_fused = value; return 0;          // big-batch MLP path: fused row-tile kernels (1, default) or the layered gemm_nt chain (0)
+    case 2: g_overlap = value; return 0;            // side streams: all (1, default), none (0), else a bit mask over them shifted by one
+    case 3:                                         // weight-gradient GEMMs: workgroups aimed for (default 256)
+      if (value < 1) break;
+      g_tn_target = value;
+      return 0;
+    case 4:                                         // ... and the cap on their row splits (default 128)
+      if (value < 1) break;
+      g_tn_max_splits = value;
+      return 0;
+    case 5: set_gemm_tn_variant(value); return 0;   // ungrouped gemm_tn: register-staged (0, default), an LDS-DMA ring (1..8), by shape (-1)
+    case 6: set_gemm_tn_thin(value); return 0;      // ungrouped gemm_tn: the 512 x 64 tile for thin outputs (1, default) or not (0)
+    case 7: set_fused_short_tiles(value); return 0; // fused kernels: bit mask of short-tile variants (default 0: none)
+    case 8: g_dbg = value; return 0;                // timing experiments, results are wrong while set (default 0)
+    case 9: case 10: return retired_knob(knob);
+    case 11: g_temb_onehot = value; return 0;       // time-embedding gradient through one-hot step columns of the input rows (1, default) or a pass of its own (0)
+    case 12: g_tn_group = value; return 0;          // weight-gradient GEMMs of a backward pass in one grouped launch (1, default) or one launch each (0)
+    case 13: g_pack_one = value; return 0;          // dppo_pack_net: one launch per network (1, default) or per image (0)
+    case 14: g_early_join = value; return 0;        // side streams joined right behind the weight-gradient launch (1, default) or at the call's end (0)
+    case 15: set_sampler_l0_lds(value); return 0;   // sampler: layer-0 weight fragments resident in LDS when they fit (1, default) or not (0)
+    case 16: g_lowrank_top = value; return 0;       // top block's dW2 from the rank-out_dim factorisation (1, default) or an H x H GEMM (0)
+    case 17: g_merge_top = value; return 0;         // sampler: top block's second layer merged into the out layer (1, default) or run (0)
+    case 18: g_post_one = value; return 0;          // what follows the slab reduction of a backward pass in one launch (1, default) or several (0)
+    case 20: dppo::set_vis_mfma_attn(value); return 0;  // visual encoder: attention on the matrix cores (1, default) or the scalar kernels (0)
+    case 21: set_gemm_nt_small(value); return 0;    // gemm_nt: small tiles for small problems (1, default) or the 128 x 128 / 64 x 128 / 16 x 256 shapes only (0)
+    case 22: set_fused_merge_fwd(value); return 0;  // fused forward of one-block networks: second layer merged into the out layer (1, default), not (0),
+                                                    // heads of up to 16 outputs only (3); takes effect at the next pack (both forms are always packed)
+    case 23: set_fused_bwd_one(value); return 0;    // fused backward of one-block networks: the specialised kernel (1, default) or the general one (0)
+    case 25: set_fused_compact(value); return 0;    // one-block kernels: short layers walked without their padding k-steps (1, default) or padded (0)
+    case 26: set_gemm_tn_nbuf(value); return 0;     // grouped weight-gradient GEMM, LDS stages: by the group's size (0, default), 1 or 2
+    case 27: set_sampler_split(value); return 0;    // sampler: one 16-row tile over eight workgroups for small env batches (1, default) or one (0)
+    case 28: set_sampler_split_pre_sweep(value); return 0;  // split sampler: 64-cycle sleep periods between a member's exchange store and its first sweep (default 4)
+    case 29: set_sampler_split_spin_limit(value); return 0;  // split sampler: sweeps a member waits before giving up (default 2^20; <= 0 restores it)
+    case 30:                                        // low-rank dW2 (knob 16) and the one-block backward: on for M >= value x out_dim (default 100)
+      if (value < 1) break;
+      g_lowrank_ratio = value;
+      return 0;
+    case 31: case 32: case 33: case 34: case 35: return retired_knob(knob);
+    case 36: g_mom_rider = value; return 0;         // advantage moments as riders of the row builder: up to 16,384 samples (0, default), always (1), never (2)
+    case 37: g_dw0 = value; return 0;               // in-kernel first-layer weight gradient of the one-block backward (1, default) or dh_0 stored and a GEMM (0)
+    case 38: g_side_tail = value; return 0;         // with knob 37: what the backward kernel alone feeds runs on a side stream under the GEMMs (1, default) or behind them (0)
+    case 39: case 40: return retired_knob(knob);
+    case 41: g_tail_post = value; return 0;         // with knob 38: the GEMMs' slab reductions and the post-reduce parts behind them in one launch (1, default) or two (0)
+    default: break;
   }
   return fail(-1, "unknown tuning knob %d", knob);
 }

@@ -51,11 +51,6 @@ struct FusedFwdArgs {
   const u32x4* ostream0;    // fragments of Wout W0, [ks][to][lane]
   const u32x4* ostream2;    // fragments of Wout W2, [ks][to][lane]
   const float* cbias2;      // [out_dim] bout + Wout (b0 + b2)
-  // K-major fragment stores (gemm.h, GemmTNFrag; merged kernel, bf16, training): act(h_0) and act(z1) -- read by nothing
-  // but the weight-gradient GEMMs -- are written as the MFMA operand fragments those want instead of row-major; a1[0] /
-  // a2[0] are then not written.  [k-step][H / 16][64 lanes] u32x4 each, k-steps of 32 rows, whole tiles.
-  u32x4* a1f;
-  u32x4* a2f;
 };
 
 struct FusedBwdArgs {
@@ -84,16 +79,6 @@ struct FusedBwdArgs {
   int dout_slot;
   int dbg;  // timing experiments only (tuning knob 8): bit 1 = do not fetch the derivative sources (wrong results)
   int one_block;  // fused_backward_one_kernel (fused_bwd_one_block(), nb == 1): dh[1] and column-sum slot 0 are not produced
-  // K-major fragment stores (gemm.h, GemmTNFrag; one-block kernel, bf16): dz1 and dh_0 as fragments instead of row-major
-  // (dz1[0] / dh[0] are then not written), plus fragment copies of the two small operands the GEMMs contract them with: the
-  // d_out tile (first dof_nt feature tiles of it) and the network's input rows x ([M][ld_x] elem, x_nt = ld_x / 16 tiles)
-  u32x4* dz1f;
-  u32x4* dh0f;
-  u32x4* doutf;
-  int dof_nt;
-  const void* x;
-  int ld_x;
-  u32x4* xf;
   // In-kernel first-layer weight gradient (one-block kernel, bf16; fused_dw0_shape()): dh_0 is never stored.  Every persistent
   // workgroup keeps dW0_part[H][32] = sum over ITS tiles of bf16(dh_0)^T . x' in LDS and writes it once, at the end, to
   // dw0_slab[blockIdx.x][H][32] (f32); the caller reduces the gridDim.x slabs.  x' = 32 columns of the input rows xc
@@ -109,12 +94,8 @@ template <class P>
 int fused_bwd_one_grid(const dppo_net_desc& d, int64_t M);
 bool fused_dw0_shape(const dppo_net_desc& d);
 
-struct LossArgs;
-// loss != null (fused_loss_shape(), merged forward, training): the policy half of the PPO loss runs in the kernel's epilogue
-// (loss_dev.h): a.out is not written, loss->d_eps and loss->partial are
 template <class P>
-int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStream_t s, const LossArgs* loss = nullptr);   // <0: shape not covered
-bool fused_loss_shape(const dppo_net_desc& d);
+int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStream_t s);   // <0: shape not covered
 template <class P>
 int launch_fused_backward(const dppo_net_desc& d, const FusedBwdArgs& a, hipStream_t s);
 void set_fused_short_tiles(int v);  // tuning knob 7
@@ -126,7 +107,6 @@ int fused_rows_per_tile(const dppo_net_desc& d, bool one_block = false);  // row
 template <class P>
 bool fused_bwd_one_block(const dppo_net_desc& d);  // shape covered by fused_backward_one_kernel (the caller adds: low-rank dW2 on)
 void set_fused_bwd_one(int v);  // tuning knob 23
-bool fused_frag_shape(const dppo_net_desc& d);  // the fragment-output kernel variants (FusedFwdArgs::a1f, FusedBwdArgs::dz1f) exist for it
 void set_fused_compact(int v);  // tuning knob 25
 
 // Fragment packing of a whole stream in ONE launch: layer l occupies positions [pos0, pos0 + KS); element

@@ -5,7 +5,6 @@
 #include "gemm.h"
 #include "tile_ln.h"
 #include "pack_dev.h"
-#include "loss_dev.h"
 
 #ifndef DPPO_BWD_LATE
 #define DPPO_BWD_LATE 1
@@ -257,9 +256,6 @@ struct CEngine {
     }
   }
   // acc += (H-wide layer) . src^T, with the flag waits of Engine::run (KSH / 8 k-steps per producer wave)
-  // TAIL_REFILL = false: the last four steps multiply without fetching what follows the wide segment -- the ring's registers are
-  // dead from here to reprime() at the tile's end (the fused-loss forward: its epilogue needs them)
-  template <bool TAIL_REFILL = true>
   __device__ __forceinline__ void wide(f32x4 (&acc)[TPW][MR], const char* src, int rb, int km, int r, int g,
                                        lds_u32* flags = nullptr, uint32_t need = 0) {
     uint32_t ready = 0xffu;
@@ -292,24 +288,10 @@ struct CEngine {
     }
     constexpr int KL = KSH - PD;  // the last four: their refills reach the third segment, the holes or the next tile
     wait_group(KL);
-    if constexpr (TAIL_REFILL) {
-      step_ct<(S1 + 0) % PD, S1 + KL + 0>(acc, src, rb, km, KL + 0, r, g);
-      step_ct<(S1 + 1) % PD, S1 + KL + 1>(acc, src, rb, km, KL + 1, r, g);
-      step_ct<(S1 + 2) % PD, S1 + KL + 2>(acc, src, rb, km, KL + 2, r, g);
-      step_ct<(S1 + 3) % PD, S1 + KL + 3>(acc, src, rb, km, KL + 3, r, g);
-    } else {
-      static_assert(TAIL_REFILL || S2 == 0, "without a third segment only");
-      mult((S1 + 0) % PD, acc, ring[(S1 + 0) % PD], src, rb, km, KL + 0, r, g);
-      mult((S1 + 1) % PD, acc, ring[(S1 + 1) % PD], src, rb, km, KL + 1, r, g);
-      mult((S1 + 2) % PD, acc, ring[(S1 + 2) % PD], src, rb, km, KL + 2, r, g);
-      mult((S1 + 3) % PD, acc, ring[(S1 + 3) % PD], src, rb, km, KL + 3, r, g);
-    }
-  }
-  __device__ __forceinline__ void reprime() {  // the next tile's first four positions (a tile starts at slot 0)
-    fetch_ct<0, 0>();
-    fetch_ct<1, 1>();
-    fetch_ct<2, 2>();
-    fetch_ct<3, 3>();
+    step_ct<(S1 + 0) % PD, S1 + KL + 0>(acc, src, rb, km, KL + 0, r, g);
+    step_ct<(S1 + 1) % PD, S1 + KL + 1>(acc, src, rb, km, KL + 1, r, g);
+    step_ct<(S1 + 2) % PD, S1 + KL + 2>(acc, src, rb, km, KL + 2, r, g);
+    step_ct<(S1 + 3) % PD, S1 + KL + 3>(acc, src, rb, km, KL + 3, r, g);
   }
   // acc += (last short layer) . src^T : k-steps 0 .. S2-1 of src
   __device__ __forceinline__ void short2(f32x4 (&acc)[TPW][MR], const char* src, int rb, int km, int r, int g) {
@@ -347,89 +329,19 @@ struct CEngine {
   }
 };
 
-// ---- K-major fragment stores (gemm.h, GemmTNFrag): bf16 only -------------------------------------------------------------
 // A 16-lane group reading a 4-row x 16-column block of bf16 with ds_read_b64_tr_b16 gets it transposed: lane i ends with
-// column i of the 4 rows.  Two reads (rows 8 kg + 0..3 and + 4..7 of a 32-row k-step) are one lane's 16 bytes of the
-// fragment: feature 16 ft + i, rows 32 ks + 8 kg + s.
+// column i of the 4 rows.  Two reads (rows 8 kg + 0..3 and + 4..7 of a 32-row k-step) are one lane's 16 bytes of an MFMA operand
+// fragment whose K index is the batch row: feature 16 ft + i, rows 32 ks + 8 kg + s.
 typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
 __device__ __forceinline__ u32x2 lds_tr16(const char* p) {
   return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)p));
-}
-// this wave's 16 TPW features of a swizzled [16 MR][H] bf16 LDS image (as written by emit(): 16-byte chunk c of row R sits
-// at chunk c ^ (R & 15)) -> out[ks'][ft][lane], ks' = 0 .. MR/2 - 1 the tile's k-steps, NT feature tiles per k-step.
-// A wave reads back only what it wrote itself (LDS executes a wave's instructions in order): no barrier.
-template <int TPW, int MR>
-__device__ __forceinline__ void frag_store_image(const char* img, int HRB, int wid, int lane, u32x4* out, int NT) {
-  static_assert(MR % 2 == 0, "a k-step is two row sub-tiles");
-  const int i = lane & 15, kg = lane >> 4, q = i >> 2, p = i & 3;
-#pragma unroll
-  for (int ks = 0; ks < MR / 2; ++ks) {
-    const int row0 = 32 * ks + 8 * kg + q, row1 = row0 + 4;
-#pragma unroll
-    for (int t = 0; t < TPW; ++t) {
-      const int ft = wid * TPW + t, c = 2 * ft + (p >> 1);
-      const u32x2 u0 = lds_tr16(img + row0 * HRB + ((c ^ (row0 & 15)) << 4) + (p & 1) * 8);
-      const u32x2 u1 = lds_tr16(img + row1 * HRB + ((c ^ (row1 & 15)) << 4) + (p & 1) * 8);
-      out[((size_t)ks * NT + ft) * 64 + lane] = (u32x4){u0.x, u0.y, u1.x, u1.y};
-    }
-  }
-}
-// the same for a narrow tile every wave can read (the d_out tile, the input rows: [16 MR][rb bytes], chunk swizzle by
-// row & km, load_tile()): the (k-step, feature tile) pairs are dealt to the eight waves; behind the barrier that made the
-// tile visible.  nt_src: feature tiles to copy (<= rb / 32), NT: tiles per k-step of the destination
-template <int MR>
-__device__ __forceinline__ void frag_store_tile(const char* img, int rb, int km, int nt_src, int wid, int lane, u32x4* out, int NT) {
-  const int i = lane & 15, kg = lane >> 4, q = i >> 2, p = i & 3;
-  for (int item = wid; item < (MR / 2) * nt_src; item += SAMPLER_WAVES) {
-    const int ks = item / nt_src, ft = item - ks * nt_src;
-    const int row0 = 32 * ks + 8 * kg + q, row1 = row0 + 4, c = 2 * ft + (p >> 1);
-    const u32x2 u0 = lds_tr16(img + row0 * rb + ((c ^ (row0 & km)) << 4) + (p & 1) * 8);
-    const u32x2 u1 = lds_tr16(img + row1 * rb + ((c ^ (row1 & km)) << 4) + (p & 1) * 8);
-    out[((size_t)ks * NT + ft) * 64 + lane] = (u32x4){u0.x, u0.y, u1.x, u1.y};
-  }
-}
-// accumulators v[tp][m] (features wbase + feat_off(g, tp) + e of rows 16 m + r) that go to NO LDS image (dh_0 of the one-block
-// backward): staged k-step by k-step through a private [32 rows][16 TPW features] bf16 region of this wave, chunk c of row
-// R at c ^ (R & (2 TPW - 1)), and read back transposed.  stage: this wave's 32 * 32 * TPW bytes.
-template <int TPW, int MR>
-__device__ __forceinline__ void frag_store_acc(const f32x4 (&v)[TPW][MR], char* stage, int wid, int lane, u32x4* out, int NT) {
-  static_assert(MR % 2 == 0 && TPW % 2 == 0, "bf16 chunk = two MFMA tiles; a k-step = two row sub-tiles");
-  constexpr int RS = 32 * TPW, CM = 2 * TPW - 1;  // row bytes, chunk mask
-  const int r = lane & 15, g = lane >> 4;
-  const int i = r, kg = g, q = i >> 2, p = i & 3;
-#pragma unroll
-  for (int ks = 0; ks < MR / 2; ++ks) {
-#pragma unroll
-    for (int mm = 0; mm < 2; ++mm) {
-      const int m = 2 * ks + mm, row = 16 * mm + r;
-#pragma unroll
-      for (int tp = 0; tp < TPW; tp += 2) {
-        u32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float lo = v[tp + (2 * e) / 4][m][(2 * e) % 4], hi = v[tp + (2 * e + 1) / 4][m][(2 * e + 1) % 4];
-          o[e] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
-        }
-        const int c = (feat_off<BF16>(g, tp) * 2) >> 4;  // chunk of the wave's slice: 4 (tp / 2) + g
-        *(u32x4*)(stage + row * RS + ((c ^ (row & CM)) << 4)) = o;
-      }
-    }
-    const int row0 = 8 * kg + q, row1 = row0 + 4;
-#pragma unroll
-    for (int t = 0; t < TPW; ++t) {
-      const int c = 2 * t + (p >> 1);
-      const u32x2 u0 = lds_tr16(stage + row0 * RS + ((c ^ (row0 & CM)) << 4) + (p & 1) * 8);
-      const u32x2 u1 = lds_tr16(stage + row1 * RS + ((c ^ (row1 & CM)) << 4) + (p & 1) * 8);
-      out[((size_t)ks * NT + wid * TPW + t) * 64 + lane] = (u32x4){u0.x, u0.y, u1.x, u1.y};
-    }
-  }
 }
 
 // In-kernel first-layer weight gradient (FusedBwdArgs::dw0_slab): C[feature][col] += sum over the tile's rows of
 // bf16(v[row][feature]) * x[row][col'] for this wave's 16 TPW features and 32 columns col of the input rows.  The accumulators v
 // (feature 4g + e of MFMA tile tp at row 16 m + r: the contraction index sits in the LANE) are staged pair of tiles by pair,
 // k-step by k-step, through a private [32 rows][32 features] bf16 region (chunk c of row R at c ^ (R & 3)) and read back
-// transposed as MFMA A fragments (frag_store_acc's path); the B fragments come from the input-row tile `xw` ([16 MR][128 bytes],
+// transposed as MFMA A fragments (lds_tr16); the B fragments come from the input-row tile `xw` ([16 MR][128 bytes],
 // chunk swizzle by row & 7, load_tile()) the same way, four columns per lane address: column block b of the 32 is the row's
 // columns 4 b .. 4 b + 3, moved up by `skip` columns from column `af` on (a denoiser's rows are [x_k | temb | obs | one-hot]: the
 // time-embedding columns are skipped; af and skip are multiples of 4).  C lives in LDS between tiles -- cacc[(tile t of the wave's
@@ -874,17 +786,8 @@ __global__ __launch_bounds__(512, 2 * OCC) void fused_forward_kernel(const Fused
 // The weight-gradient side (api.hip, mlp_backward): dWout = d_out^T h_1 is rebuilt from U = d_out^T x and T = d_out^T act(z1).
 // S1 > 0 (ring depth 4): the input tile's layer is walked as its S1 = ks0v <= 2 k-steps that hold data instead of the
 // padded four (CEngine); S1 = 0: the padded walk.
-// FRAG (bf16, OT = 1, S1 = 1 or 2 only): act(h_0) / act(z1) leave as K-major fragments (a.a1f / a.a2f) instead of row-major.  A
-// template parameter, not a run-time test: compiled into every variant, the fragment code cost the variants that never use it
-// 8-24 spilled registers.
-// LOSSF (bf16, OT = 1, not FRAG; training): the policy half of the PPO loss runs in the tile's epilogue (loss_dev.h) -- the tile's
-// eps never goes to HBM, there is no loss launch between the actor's forward and backward.  A row's chain pair, old log-probs and
-// advantage are requested behind the H-wide k-loop (their row / step indices were staged with the input tile), land in the dead
-// half of buffer A behind the next barrier, and wave 0 then walks one sample per lane exactly as ppo_loss_kernel does: d loss / d eps
-// rows to HBM, the tile's five statistics -- a tile is 64 samples, the loss kernel's block -- to la.partial[tile].
-template <class P, int TPW, int MR, int OT, int ACT, int S1, bool FRAG, bool LOSSF>
-__device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a, const LossArgs& la) {
-  static_assert(!LOSSF || (OT == 1 && !FRAG && MR == 4 && P::ESIZE == 2), "fused policy loss: bf16, one out tile, 64-row tiles");
+template <class P, int TPW, int MR, int OT, int ACT, int S1>
+__device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a) {
   constexpr int PD = ring_depth<TPW, MR>(), ES = P::ESIZE, KB = P::KB;
   static_assert(S1 == 0 || PD == 4, "the compact walk is written for a ring of four positions");
   constexpr int H = 128 * TPW, KSH = H / KB, HRB = H * ES, MT = 16 * MR;
@@ -918,12 +821,6 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a,
   // the first pass runs late, in the second pass's phase (a partial result carried through the H-wide k-loop is 8-16 more
   // live registers in a kernel that has none to spare: 24-56 spilled), so the tile gets its own [MT][ks0v * 64 B] region
   char* xin = WIDE ? (char*)(w0cL + ks0v * OT * 64) : bufB;
-  // LOSSF: [MT] (row, step) of the tile's samples, then the loss's per-step table [2 Kft + 2]; in buffer A behind the out-layer
-  // partials (dead from the barrier behind the second emit on): eps tile [MT][16] f32 at +16 KB, gathered inputs [MT][64] f32 at +24 KB
-  long long* metaL = (long long*)(w0cL + ks0v * OT * 64);  // per row: element offsets of its chain pair and of its old log-probs, then (sample's rollout row, step)
-  float* tabL = (float*)(metaL + 3 * MT);
-  float* epsL = (float*)(bufA + 16 * 1024);
-  float* recL = (float*)(bufA + 24 * 1024);  // [MT][3 AF + 1] f32, rounded up to whole 512-dword DMA rounds (<= 16 KB)
   const int wbase = wid * 16 * TPW;
   const int to_w = wid % OT, kh_w = wid / OT;  // WIDE: this wave's out tile and K slice
   for (int idx = tid; idx < 2 * H; idx += 512) biasL[idx] = a.params[a.bias_off[idx / H] + idx % H];
@@ -931,17 +828,6 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a,
   if constexpr (!WIDE)
     for (int idx = tid; idx < KSH * OT * 64; idx += 512) woutL[idx] = a.ostream2[idx];
   for (int idx = tid; idx < ks0v * OT * 64; idx += 512) w0cL[idx] = a.ostream0[idx];
-  if constexpr (LOSSF) {  // ppo_loss_kernel's prologue: the per-step table, the advantage moments
-    const int Kft = la.pcfg.ft_denoising_steps;
-    for (int k = tid; k < 2 * Kft; k += 512) tabL[k] = la.tab[k];
-    for (int k = tid; k < Kft; k += 512) tabL[2 * Kft + 2 + k] = la.tab[2 * Kft + k];  // log std_k (build_rows_kernel)
-    if (tid == 0) {
-      const double Nm = la.moments[2], mean = la.moments[0] / Nm;
-      const double varu = (la.moments[1] - Nm * mean * mean) / (Nm - 1.0);  // unbiased (torch.std)
-      tabL[2 * Kft] = (float)mean;
-      tabL[2 * Kft + 1] = (float)sqrt(varu > 0 ? varu : 0);
-    }
-  }
   if (tid < 16) flags[tid] = 0;
   uint32_t seq = 0;
   // (visible after the first tile's barrier)
@@ -959,35 +845,8 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a,
     const int row0 = tile * MT;
     STAMP(0);
     load_tile<MT>(xin, in_rb, in_km, (const char*)a.in, a.ld_in * ES, row0, M);
-    if constexpr (LOSSF) {
-      int t_ = tid;
-      asm volatile("" : "+v"(t_));
-      if (t_ < MT) {
-        const int n = row0 + t_, Kft = la.pcfg.ft_denoising_steps, AF = la.AF;
-        const long long b = n < M ? la.brow[n] : 0, k = n < M ? la.krow[n] : 0;
-        metaL[3 * t_] = la.gathered ? b * 2 * AF : (b * (Kft + 1) + k) * AF;
-        metaL[3 * t_ + 1] = la.gathered ? b * AF : (b * Kft + k) * AF;
-        metaL[3 * t_ + 2] = (b << 32) | k;
-      }
-    }
     __syncthreads();
     STAMP(1);
-    // LOSSF: touch the cache lines of the tile's loss inputs now (five dwords per row: both ends of the chain pair and of the old
-    // log-probs, the advantage), a whole tile ahead of their LDS-DMA: gathered cold behind the second emit they cost every wave
-    // 3-5 us of waiting per tile (the fused forward ran 114 us against 86 + a 30 us loss launch)
-    uint32_t warm = 0;
-    if constexpr (LOSSF) {
-      int t_ = tid;
-      asm volatile("" : "+v"(t_));
-      const int row = t_ / 5, part = t_ - row * 5;
-      if (row < MT && row0 + row < M) {
-        const int AF = la.AF;
-        const float* src = part < 2   ? la.chains + lds_load(metaL + 3 * row) + (part ? 2 * AF - 1 : 0)
-                           : part < 4 ? la.logprobs_k + lds_load(metaL + 3 * row + 1) + (part == 3 ? AF - 1 : 0)
-                                      : la.adv_k + (int)(lds_load(metaL + 3 * row + 2) >> 32);
-        warm = *(const uint32_t*)src;
-      }
-    }
     f32x4 acc[TPW][MR];
     auto bias_init = [&](int layer) {
 #pragma unroll
@@ -1020,56 +879,26 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a,
         }
       }
     }
-    emit<P, TPW, MR>(acc, ACT, bufA, FRAG ? nullptr : a.a1[0], H, wbase, g, r, row0, M, a.hpre[0]);  // hpre[0] <- act'(h_0) (Mish) / sign words
+    emit<P, TPW, MR>(acc, ACT, bufA, a.a1[0], H, wbase, g, r, row0, M, a.hpre[0]);  // hpre[0] <- act'(h_0) (Mish) / sign words
     STAMP(3);
     if constexpr (FLAGS)
       hand_over(flags, wid, lane, ++seq);
     else
       __syncthreads();
-    if constexpr (FRAG)  // act(h_0) as K-major fragments: read back from the image this wave has just written
-      frag_store_image<TPW, MR>(bufA, HRB, wid, lane, a.a1f + (size_t)tile * (MR / 2) * (H / 16) * 64, H / 16);
     STAMP(4);
     // ---- the block's first layer
     bias_init(1);
     if constexpr (S1 > 0) {
-      eng.template wide<!LOSSF>(acc, bufA, HRB, 15, r, g, FLAGS ? flags : nullptr, seq);
-      if constexpr (!WIDE && !LOSSF) eng.end_tile();  // (WIDE: the third segment comes first, below; LOSSF: reprime() at the tile's end)
+      eng.wide(acc, bufA, HRB, 15, r, g, FLAGS ? flags : nullptr, seq);
+      if constexpr (!WIDE) eng.end_tile();  // (WIDE: the third segment comes first, below)
     } else {
       eng.run(acc, bufA, HRB, 15, KSH, r, g, FLAGS ? flags : nullptr, seq);
     }
     STAMP(5);
-    emit<P, TPW, MR>(acc, ACT, bufB, FRAG ? nullptr : a.a2[0], H, wbase, g, r, row0, M, a.z1[0]);  // z1[0] <- act'(z1) (Mish) / sign words
-    if constexpr (FRAG) frag_store_image<TPW, MR>(bufB, HRB, wid, lane, a.a2f + (size_t)tile * (MR / 2) * (H / 16) * 64, H / 16);
+    emit<P, TPW, MR>(acc, ACT, bufB, a.a2[0], H, wbase, g, r, row0, M, a.z1[0]);  // z1[0] <- act'(z1) (Mish) / sign words
     STAMP(6);
     __syncthreads();  // the out layer's work items read every wave's features
     STAMP(7);
-    // LOSSF: request the tile's loss inputs now, behind the second emit: per row its AF-element x_k, x_k+1 (adjacent in memory),
-    // old log-probs and its advantage, one dword per slot (slot = row * DPR + element, DPR = 3 AF + 1), by LDS-DMA straight into the
-    // dead part of buffer A -- no registers (held in registers across the emit they pushed the kernel from 223 to 237 VGPRs, and the
-    // critic's value-loss launch could no longer slip a wave in beside these workgroups: 13 -> 80 us, step +16 us).  They travel
-    // under the out layer's second pass.
-    if constexpr (LOSSF) {
-      asm volatile("" ::"v"(warm));  // (the touches have landed long ago: their register is free from here)
-      typedef __attribute__((address_space(3))) void* lds_ptr;
-      typedef const __attribute__((address_space(1))) void* glb_ptr;
-      const int AF = la.AF, DPR = 3 * AF + 1, total = MT * DPR;
-      int t_ = tid;
-      asm volatile("" : "+v"(t_));
-      for (int s0 = 0; s0 < total; s0 += 512) {
-        const int sl = s0 + t_;
-        int row = sl / DPR;
-        const int d = sl - row * DPR;
-        row = row < MT && row0 + row < M ? row : 0;  // (a DMA has no mask: slots past the tile fetch row 0's, nobody reads them)
-        const float* src;
-        if (d < 2 * AF)
-          src = la.chains + lds_load(metaL + 3 * row) + d;
-        else if (d < 3 * AF)
-          src = la.logprobs_k + lds_load(metaL + 3 * row + 1) + (d - 2 * AF);
-        else
-          src = la.adv_k + (int)(lds_load(metaL + 3 * row + 2) >> 32);
-        __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)(recL + s0 + (t_ & ~63)), 4, 0, 0);
-      }
-    }
     // ---- out layer, second pass: (Wout W2) on act(z1)
     int r_ = r, g_ = g, lane_ = lane;
     asm volatile("" : "+v"(r_), "+v"(g_), "+v"(lane_));  // (see fused_forward_kernel: addresses recomputed, not spilled)
@@ -1127,60 +956,18 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a,
       float s = biasL[2 * H + j];
 #pragma unroll
       for (int kh = 0; kh < KSPLIT; ++kh) s += part[(((kh * MR + m) * OT + to) * 16 + jj) * 16 + rr];
-      if constexpr (LOSSF)
-        epsL[row * 16 + j] = s;
-      else if (row0 + row < M)
+      if (row0 + row < M)
         a.out[(size_t)(row0 + row) * a.ldout + j] = s;
     }
     STAMP(13);
-    if constexpr (LOSSF) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the gathered inputs has landed
-      __syncthreads();  // the eps tile and the gathered inputs are in place
-      if (wid == 0) {   // one sample per lane, as in ppo_loss_kernel (64 samples per block there: this tile)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int n = row0 + ln;
-        const int cnt = (la.pcfg.reward_horizon < la.pcfg.horizon_steps ? la.pcfg.reward_horizon : la.pcfg.horizon_steps) * la.pcfg.action_dim;
-        const double Nn = la.n_count > 0 ? la.n_count : la.moments[2];
-        double s4[4] = {0, 0, 0, 0};
-        if (n < M) {
-          const int AF = la.AF;
-          const float* rr = recL + ln * (3 * AF + 1);
-          const float adv = lds_load(rr + 3 * AF);
-          const int k = (int)(lds_load(metaL + 3 * ln + 2) & 0xffffffffll);
-          policy_loss_row_nc<P>(la, tabL, k, adv, rr, rr + AF, rr + 2 * AF, epsL + ln * 16, cnt, Nn,
-                                (typename P::elem_t*)la.d_eps + (size_t)n * la.ldde, s4);
-        }
-        // the tile's partial sums by the loss kernel's shuffle tree (v_loss belongs to the value half's launch)
-        double v5[5] = {s4[0], 0.0, s4[1], s4[2], s4[3]};
-#pragma unroll
-        for (int q = 0; q < 5; ++q)
-          for (int off = 32; off > 0; off >>= 1) v5[q] += __shfl_down(v5[q], off);
-        if (ln == 0) {
-          double* po = la.partial + (size_t)tile * 8;
-          po[DPPO_STAT_PG_LOSS] = v5[0], po[DPPO_STAT_V_LOSS] = v5[1], po[DPPO_STAT_APPROX_KL] = v5[2];
-          po[DPPO_STAT_CLIPFRAC] = v5[3], po[DPPO_STAT_RATIO] = v5[4];
-        }
-      }
-    }
-    if constexpr (LOSSF && S1 > 0) eng.reprime();  // (their latency hides under the next tile's input load and barrier)
     __syncthreads();  // the next tile's input lands in buffer B; its layer-0 emit in buffer A, where the partials were read
     STAMP(14);
   }
 }
 
-template <class P, int TPW, int MR, int OT, int ACT, int S1, bool FRAG = false, bool LOSSF = false>
-__global__ __launch_bounds__(512, 2) void fused_forward_merged_kernel(const FusedFwdArgs a, const LossArgs la) {
-  fused_forward_merged_body<P, TPW, MR, OT, ACT, S1, FRAG, LOSSF>(a, la);
-}
-// The LOSSF variant under a register cap: left alone it allocates 235 VGPRs, two of its waves leave a SIMD 32 free registers and
-// the critic's launches can no longer slip a wave in beside them.  amdgpu_num_vgpr(112): on gfx90a+ the compiler
-// DOUBLES the request (unified VGPR + AGPR file), so this is the plain kernel's 224; the allocator then spills eight cold values
-// (hoisted tile-loop invariants, reloaded once per tile) to scratch, none inside the H-wide k-loop.
-template <class P, int TPW, int MR, int ACT, int S1>
-__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(112))) void fused_forward_merged_loss_kernel(const FusedFwdArgs a,
-                                                                                                              const LossArgs la) {
-  fused_forward_merged_body<P, TPW, MR, 1, ACT, S1, false, true>(a, la);
+template <class P, int TPW, int MR, int OT, int ACT, int S1>
+__global__ __launch_bounds__(512, 2) void fused_forward_merged_kernel(const FusedFwdArgs a) {
+  fused_forward_merged_body<P, TPW, MR, OT, ACT, S1>(a);
 }
 
 // =================================================================================================
@@ -1409,12 +1196,11 @@ __global__ __launch_bounds__(512, 2 * OCC) void fused_backward_kernel(const Fuse
 // of a tile anyway.  Needs the low-rank dW2 (no dh_1 tensor is written).
 // COMPACT (out_dim <= one k-step, ring depth 4): the two layers on the d_out tile are walked as ONE k-step each instead of
 // their padded four (CEngine).
-// FRAG (bf16, COMPACT only): dz1 / dh_0 leave as K-major fragments, with fragment copies of the d_out tile and the input rows.
 // DW0 (bf16, COMPACT only; 1, or 2 = FusedBwdArgs::dw0_round): dh_0 is not stored at all -- its product with the input rows is
 // accumulated in LDS (dw0_accumulate, FusedBwdArgs::dw0_slab) and buffer B shrinks to the d_out tile.
-template <class P, int TPW, int MR, int ACT, bool COMPACT, bool FRAG = false, int DW0 = 0>
+template <class P, int TPW, int MR, int ACT, bool COMPACT, int DW0 = 0>
 __global__ __launch_bounds__(512, 2) void fused_backward_one_kernel(const FusedBwdArgs a) {
-  static_assert(!DW0 || (COMPACT && !FRAG && P::ESIZE == 2), "in-kernel dW0: bf16, compact walk, row-major dz1");
+  static_assert(!DW0 || (COMPACT && P::ESIZE == 2), "in-kernel dW0: bf16, compact walk");
   constexpr int ES = P::ESIZE, KB = P::KB, PD = ring_depth<TPW, MR>();
   static_assert(!COMPACT || PD == 4, "the compact walk is written for a ring of four positions");
   constexpr int H = 128 * TPW, KSH = H / KB, HRB = H * ES, MT = 16 * MR;
@@ -1438,11 +1224,6 @@ __global__ __launch_bounds__(512, 2) void fused_backward_one_kernel(const FusedB
   char* xw = (char*)(dred + SAMPLER_WAVES * DRED_COLS);
   char* stage_w = xw + MT * 128 + wid * 2048;
   f32x4* cacc = (f32x4*)(xw + MT * 128 + SAMPLER_WAVES * 2048) + (size_t)wid * TPW * 2 * 64;
-  // fragment mode (a.dz1f): buffer B beyond the d_out tile (at most MT x 256 bytes of its MT x HRB) also holds the input-row
-  // tile [MT][ld_x] and each wave's private staging region for dh_0 (frag_store_acc): 16 + 16 + 32 KB of 64 at H = 512
-  // (the launcher checked MT (in_rb + ld_x ES) + 8 x 32 x 32 TPW <= MT HRB: fused_frag_fits())
-  char* xt = bufB + MT * in_rb;
-  char* stage = xt + MT * a.ld_x * ES + wid * (32 * 32 * TPW);
   const int wbase = wid * 16 * TPW;
   const int ntiles = (M + MT - 1) / MT;
 
@@ -1533,17 +1314,7 @@ __global__ __launch_bounds__(512, 2) void fused_backward_one_kernel(const FusedB
       load_tile<MT>(xin, in_rb, in_km, (const char*)a.d_out, a.ld_dout * ES, row0, M);
       if constexpr (DW0) load_tile<MT>(xw, 128, 7, (const char*)a.xc, a.ld_xc * ES, row0, M);  // (the rows' first 64 columns)
     }
-    if constexpr (FRAG) {
-      const int x_rb = a.ld_x * ES, x_km = kmask16(x_rb);
-      load_tile<MT>(xt, x_rb, x_km, (const char*)a.x, x_rb, row0, M);
-      __syncthreads();
-      // fragment copies of the two small GEMM operands (rows past M are zero: load_tile)
-      const size_t kbase = (size_t)tile * (MR / 2);
-      frag_store_tile<MR>(xin, in_rb, in_km, a.dof_nt, wid, lane, a.doutf + kbase * a.dof_nt * 64, a.dof_nt);
-      frag_store_tile<MR>(xt, x_rb, x_km, a.ld_x / 16, wid, lane, a.xf + kbase * (a.ld_x / 16) * 64, a.ld_x / 16);
-    } else {
-      __syncthreads();
-    }
+    __syncthreads();
     STAMP(17);
     if (a.dout_slot >= 0) {  // out-layer bias gradient: column sums of the d_out tile (rows past M are zero), part 1
       typedef typename P::elem_t E;
@@ -1578,7 +1349,7 @@ __global__ __launch_bounds__(512, 2) void fused_backward_one_kernel(const FusedB
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[tp][m][e] *= grad_at<P, ACT>(d, tp, m, e);
     STAMP(20);
-    emit<P, TPW, MR>(acc, ACT_NONE, bufA, FRAG ? nullptr : a.dz1[0], H, wbase, g, r, row0, M);
+    emit<P, TPW, MR>(acc, ACT_NONE, bufA, a.dz1[0], H, wbase, g, r, row0, M);
     STAMP(23);
     colsum(acc, 2, tile);
     STAMP(24);
@@ -1586,7 +1357,6 @@ __global__ __launch_bounds__(512, 2) void fused_backward_one_kernel(const FusedB
       hand_over(flags, wid, lane, ++seq);
     else
       __syncthreads();
-    if constexpr (FRAG) frag_store_image<TPW, MR>(bufA, HRB, wid, lane, a.dz1f + (size_t)tile * (MR / 2) * (H / 16) * 64, H / 16);
     STAMP(25);
     // ---- dh_0 = (dz1 . W1) o act'(h_0) + d_out . Wout
     fetch<P, ACT == ACT_RELU, TPW>(d, a.m0[0], H, wbase, g, r, row0, M);
@@ -1623,10 +1393,9 @@ __global__ __launch_bounds__(512, 2) void fused_backward_one_kernel(const FusedB
     }
     if constexpr (DW0) {  // (rows past M: d_out is zero there, hence dh_0 too; the xc tile is zero there as well)
       dw0_accumulate<TPW, MR, DW0 == 2>(acc, stage_w, xw, cacc, lane, a.xc_af, a.xc_skip);
-    } else if constexpr (FRAG)
-      frag_store_acc<TPW, MR>(acc, stage, wid, lane, a.dh0f + (size_t)tile * (MR / 2) * (H / 16) * 64, H / 16);
-    else
+    } else {
       emit<P, TPW, MR>(acc, ACT_NONE, nullptr, a.dh[0], H, wbase, g, r, row0, M);
+    }
     STAMP(27);
     colsum(acc, 1, tile);
     STAMP(28);
@@ -1771,50 +1540,25 @@ bool fused_can_merge(const dppo_net_desc& d) {
   }
   return d.hidden <= 512 && merged_lds<P>(d.hidden, 1, ks0v) <= 160 * 1024;
 }
-// shapes the fragment-output variants are built for: bf16, head of one out tile, at most two input k-steps, compact walks on
-bool fused_frag_shape(const dppo_net_desc& d) {
-  return fused_compact_on() && d.out_dim <= 16 && d.in_dim <= 2 * BF16::KB && (d.hidden == 512 || d.hidden == 256) && fused_can_merge<BF16>(d);
-}
 template bool fused_can_merge<F32>(const dppo_net_desc&);
 template bool fused_can_merge<BF16>(const dppo_net_desc&);
 
-// shapes the fused policy loss covers (the caller adds its own conditions on the loss's arguments: fused_loss_shape())
-constexpr int FUSED_LOSS_MAX_KFT = 64;
-static size_t fused_loss_lds(int Kft) { return (size_t)3 * 64 * 8 + ((size_t)(3 * Kft + 2) * 4 + 15) / 16 * 16; }
-template <class P, int TPW, int MR, int ACT, int S1, int OT = 1, bool FRAG = false, bool LOSSF = false>
-static int launch_fwd_merged_cfg2(const FusedFwdArgs& a, hipStream_t s, const LossArgs* loss = nullptr) {
+template <class P, int TPW, int MR, int ACT, int S1, int OT = 1>
+static int launch_fwd_merged_cfg2(const FusedFwdArgs& a, hipStream_t s) {
   constexpr int MT = 16 * MR, H = 128 * TPW;
-  const size_t lds = merged_lds<P>(H, OT, a.ks0v) + (LOSSF ? fused_loss_lds(loss->pcfg.ft_denoising_steps) : 0);
+  const size_t lds = merged_lds<P>(H, OT, a.ks0v);
   if (lds > 160 * 1024 || a.Kp0 > H || a.nb != 1) return -2;
-  if (FRAG != (a.a1f != nullptr) || FRAG != (a.a2f != nullptr)) return -4;  // (fragment outputs: both or none, and a variant built for them)
-  if (LOSSF != (loss != nullptr)) return -4;
   static DevLatch attr;
   const int ntiles = (a.M + MT - 1) / MT;
-  static const LossArgs no_loss = {};
-  if constexpr (LOSSF) {  // (its own kernel symbol: the same body under a register cap)
-    raise_lds(fused_forward_merged_loss_kernel<P, TPW, MR, ACT, S1>, attr);
-    const bool probe = probe_begin(PROBE_FUSED_FWD, s);
-    hipLaunchKernelGGL((fused_forward_merged_loss_kernel<P, TPW, MR, ACT, S1>), dim3(ntiles < NUM_CUS ? ntiles : NUM_CUS), dim3(512), lds, s,
-                       a, *loss);
-    if (probe) probe_end(s, 2.0 * a.M * ((double)a.in_valid * H + 2.0 * a.nb * H * H + (double)H * a.out_dim));
-    return 0;
-  }
-  raise_lds(fused_forward_merged_kernel<P, TPW, MR, OT, ACT, S1, FRAG, LOSSF>, attr);
+  raise_lds(fused_forward_merged_kernel<P, TPW, MR, OT, ACT, S1>, attr);
   const bool probe = probe_begin(PROBE_FUSED_FWD, s);
-  hipLaunchKernelGGL((fused_forward_merged_kernel<P, TPW, MR, OT, ACT, S1, FRAG, LOSSF>), dim3(ntiles < NUM_CUS ? ntiles : NUM_CUS), dim3(512),
-                     lds, s, a, loss != nullptr ? *loss : no_loss);
+  hipLaunchKernelGGL((fused_forward_merged_kernel<P, TPW, MR, OT, ACT, S1>), dim3(ntiles < NUM_CUS ? ntiles : NUM_CUS), dim3(512),
+                     lds, s, a);
   if (probe) probe_end(s, 2.0 * a.M * ((double)a.in_valid * H + 2.0 * a.nb * H * H + (double)H * a.out_dim));
   return 0;
 }
 template <class P, int TPW, int MR, int ACT>
-static int launch_fwd_merged_cfg(const FusedFwdArgs& a, hipStream_t s, const LossArgs* loss) {
-  if (loss != nullptr) {  // the policy loss in the epilogue: bf16 64-row tiles, one out tile, compact walk (fused_loss_shape())
-    if constexpr (P::ESIZE == 2 && MR == 4 && ring_depth<TPW, MR>() == 4) {
-      if (a.out_dim <= 16 && a.a1f == nullptr && fused_compact_on() && a.ks0v == 1) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 1, 1, false, true>(a, s, loss);
-      if (a.out_dim <= 16 && a.a1f == nullptr && fused_compact_on() && a.ks0v == 2) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 2, 1, false, true>(a, s, loss);
-    }
-    return -4;
-  }
+static int launch_fwd_merged_cfg(const FusedFwdArgs& a, hipStream_t s) {
   if (a.out_dim > 16) {  // the wide head (fused_can_merge admitted it: hidden 512, compact walk, ks0v <= 3)
     if constexpr (TPW == 4) {
       if (a.ks0v == 1) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 1, 4>(a, s);
@@ -1824,32 +1568,21 @@ static int launch_fwd_merged_cfg(const FusedFwdArgs& a, hipStream_t s, const Los
     return -1;
   }
   if constexpr (ring_depth<TPW, MR>() == 4) {
-    if constexpr (P::ESIZE == 2) {  // fragment outputs: built for the compact narrow-head variants only (fused_frag_shape())
-      if (a.a1f != nullptr) {
-        if (fused_compact_on() && a.ks0v == 1) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 1, 1, true>(a, s);
-        if (fused_compact_on() && a.ks0v == 2) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 2, 1, true>(a, s);
-        return -4;
-      }
-    }
     if (fused_compact_on() && a.ks0v == 1) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 1>(a, s);
     if (fused_compact_on() && a.ks0v == 2) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 2>(a, s);
   }
   return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 0>(a, s);
 }
 
-// the fused policy loss exists for: bf16, hidden 512 (64-row tiles), a head of at most 16 outputs, at most two input k-steps
-bool fused_loss_shape(const dppo_net_desc& d) {
-  return fused_compact_on() && d.hidden == 512 && d.out_dim <= 16 && d.in_dim <= 2 * BF16::KB && fused_can_merge<BF16>(d);
-}
 template <class P>
-int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStream_t s, const LossArgs* loss) {
+int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStream_t s) {
   const int tpw = d.hidden / 128, mr = pick_mr<P>(d.hidden);
   const int nt = (d.out_dim + 15) / 16, ot = nt <= 1 ? 1 : (nt <= 4 ? 4 : (nt <= 8 ? 8 : 0));
   if (mr == 0 || ot == 0 || a.M <= 0) return -1;
   const bool relu = a.act == ACT_RELU;  // check_net admits ReLU and Mish only
   if (a.merge_top) {  // (the caller asked fused_can_merge() first)
 #define DPPO_FWDM(T, R) \
-  if (tpw == T && mr == R) return relu ? launch_fwd_merged_cfg<P, T, R, ACT_RELU>(a, s, loss) : launch_fwd_merged_cfg<P, T, R, ACT_MISH>(a, s, loss);
+  if (tpw == T && mr == R) return relu ? launch_fwd_merged_cfg<P, T, R, ACT_RELU>(a, s) : launch_fwd_merged_cfg<P, T, R, ACT_MISH>(a, s);
     if constexpr (P::ESIZE == 2) {
       DPPO_FWDM(2, 8) DPPO_FWDM(4, 4)
     } else {
@@ -1858,7 +1591,6 @@ int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStrea
 #undef DPPO_FWDM
     return -1;
   }
-  if (loss != nullptr) return -4;
   if constexpr (P::ESIZE == 2) {
     if (short_tiles<P>(d.hidden, a.use_ln, 1) && ot == 1)
       return relu ? launch_fwd_cfg<P, 4, 2, 1, false, ACT_RELU, 2>(a, s) : launch_fwd_cfg<P, 4, 2, 1, false, ACT_MISH, 2>(a, s);
@@ -1881,8 +1613,8 @@ int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStrea
 #undef DPPO_FWD
   return -1;
 }
-template int launch_fused_forward<F32>(const dppo_net_desc&, const FusedFwdArgs&, hipStream_t, const LossArgs*);
-template int launch_fused_forward<BF16>(const dppo_net_desc&, const FusedFwdArgs&, hipStream_t, const LossArgs*);
+template int launch_fused_forward<F32>(const dppo_net_desc&, const FusedFwdArgs&, hipStream_t);
+template int launch_fused_forward<BF16>(const dppo_net_desc&, const FusedFwdArgs&, hipStream_t);
 
 template <class P, int TPW, int MR, bool LN, int ACT, int OCC = 1>
 static int launch_bwd_cfg(const FusedBwdArgs& a, hipStream_t s) {
@@ -1907,26 +1639,20 @@ static size_t bwd_one_dw0_lds(int MT, int H) {
   return (size_t)MT * H * 2 + (size_t)MT * 64 + 64 + SAMPLER_WAVES * 32 * 4 + (size_t)MT * 128 + SAMPLER_WAVES * 2048 +
          (size_t)SAMPLER_WAVES * (H / 128) * 2 * 64 * 16;
 }
-template <class P, int TPW, int MR, int ACT, bool COMPACT, bool FRAG = false, int DW0 = 0>
+template <class P, int TPW, int MR, int ACT, bool COMPACT, int DW0 = 0>
 static int launch_bwd_one_cfg2(const FusedBwdArgs& a, hipStream_t s) {
   constexpr int ES = P::ESIZE, MT = 16 * MR, H = 128 * TPW;
   const size_t lds = DW0 ? bwd_one_dw0_lds(MT, H) : 2 * (size_t)MT * H * ES + 64 + SAMPLER_WAVES * 128 * 4;
   if (lds > 160 * 1024 || a.KpB0 > H || a.KpB0 > 128 || a.nb != 1) return -2;
-  if (FRAG != (a.dz1f != nullptr)) return -4;
   if ((DW0 != 0) != (a.dw0_slab != nullptr) || (DW0 == 2) != (a.dw0_round != 0)) return -4;
   if (DW0 && (a.xc == nullptr || a.ld_xc < 64 || a.ld_xc % 8 || a.xc_af % 4 || a.xc_skip % 4 || a.xc_skip < 0 || a.dh[0] != nullptr ||
               32 + a.xc_skip > 64 || a.out_valid > 32))
     return -4;
-  if (a.dz1f != nullptr || a.dh0f != nullptr || a.xf != nullptr || a.doutf != nullptr) {  // fragment mode: all four or none
-    if (ES != 2 || !a.dz1f || !a.dh0f || !a.xf || !a.doutf || !a.x || a.ld_x % 16 || a.dof_nt < 1 || a.dof_nt * 16 > a.KpB0 ||
-        (size_t)MT * ((size_t)a.KpB0 * ES + (size_t)a.ld_x * ES) + (size_t)SAMPLER_WAVES * 32 * 32 * TPW > (size_t)MT * H * ES)
-      return -4;
-  }
   static DevLatch attr;
-  raise_lds(fused_backward_one_kernel<P, TPW, MR, ACT, COMPACT, FRAG, DW0>, attr);
+  raise_lds(fused_backward_one_kernel<P, TPW, MR, ACT, COMPACT, DW0>, attr);
   const int ntiles = (a.M + MT - 1) / MT;
   const bool probe = probe_begin(PROBE_FUSED_BWD, s);
-  hipLaunchKernelGGL((fused_backward_one_kernel<P, TPW, MR, ACT, COMPACT, FRAG, DW0>), dim3(ntiles < NUM_CUS ? ntiles : NUM_CUS),
+  hipLaunchKernelGGL((fused_backward_one_kernel<P, TPW, MR, ACT, COMPACT, DW0>), dim3(ntiles < NUM_CUS ? ntiles : NUM_CUS),
                      dim3(512), lds, s, a);
   if (probe) probe_end(s, 2.0 * a.M * ((double)a.out_valid * H + 2.0 * a.nb * H * H));
   return 0;
@@ -1935,11 +1661,10 @@ template <class P, int TPW, int MR, int ACT>
 static int launch_bwd_one_cfg(const FusedBwdArgs& a, hipStream_t s) {
   if constexpr (ring_depth<TPW, MR>() == 4) {
     if constexpr (P::ESIZE == 2) {
-      if (a.dz1f != nullptr) return g_compact && a.out_valid <= P::KB ? launch_bwd_one_cfg2<P, TPW, MR, ACT, true, true>(a, s) : -4;
       if (a.dw0_slab != nullptr)
         return !(g_compact && a.out_valid <= P::KB) ? -4
-               : a.dw0_round                        ? launch_bwd_one_cfg2<P, TPW, MR, ACT, true, false, 2>(a, s)
-                                                    : launch_bwd_one_cfg2<P, TPW, MR, ACT, true, false, 1>(a, s);
+               : a.dw0_round                        ? launch_bwd_one_cfg2<P, TPW, MR, ACT, true, 2>(a, s)
+                                                    : launch_bwd_one_cfg2<P, TPW, MR, ACT, true, 1>(a, s);
     }
     if (a.dw0_slab != nullptr) return -4;
     if (g_compact && a.out_valid <= P::KB) return launch_bwd_one_cfg2<P, TPW, MR, ACT, true>(a, s);

@@ -1,7 +1,5 @@
 // See gemm.h.  gfx950 only.
 #include "gemm.h"
-#include "tail_blocks.h"
-#include "post_blocks.h"
 
 namespace dppo {
 
@@ -462,28 +460,6 @@ __device__ __forceinline__ void tn_tile(const GemmTN& a, const int split, const 
     __syncthreads();
   }
 
-  if (a.red_cnt != nullptr) {
-    // Folded reduction: the slab is stored TRANSPOSED, [split][n2][n1] with N1 padded to N1p = round_up(N1, 4): a lane's four
-    // values (rows 4g .. 4g+3 of C, one column) are then 16 contiguous bytes, the four lanes g of a column 64 -- and they go
-    // out as write-through (sc1) 16-byte stores, which the tile's last workgroup reads back with sc1 loads: no L2
-    // write-back / invalidate on either side (a release fence per wave here made the launch 5x longer: buffer_wbl2 flushes
-    // the whole XCD's L2 every time).
-    const int N1p = (a.N1 + 3) & ~3;
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.slab, 0, (int)((size_t)a.splits * a.N2 * N1p * 4), 0x00020000);
-#pragma unroll
-    for (int i = 0; i < TA; ++i) {
-      const int n1 = fa0 + wa * TA * 16 + i * 16 + 4 * g;
-      if (n1 >= N1p) continue;
-#pragma unroll
-      for (int j = 0; j < TB; ++j) {
-        const int n2 = fb0 + wb * TB * 16 + j * 16 + r;
-        if (n2 < a.N2)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rsrc,
-                                                 (int)((((size_t)split * a.N2 + n2) * N1p + n1) * 4), 0, 16);  // aux 16 = sc1
-      }
-    }
-    return;
-  }
   float* out = a.slab + (size_t)split * a.N1 * a.ldc;
 #pragma unroll
   for (int i = 0; i < TA; ++i)
@@ -511,42 +487,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmTN a) {
 // XCD, as above).  No inter-kernel gaps, and the last round of one GEMM is filled by the first of the next.
 template <class P, int NBUF>
 __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gemm_tn_group_kernel(const GemmTNGroup gr) {
-  if ((int)blockIdx.x < gr.ex.n_blocks) {  // riders: nothing here depends on this launch's GEMM tiles (gemm.h, GemmTNExtra)
-    extern __shared__ __attribute__((aligned(16))) char rider_smem[];
-    const GemmTNExtra& e = gr.ex;
-    int b = blockIdx.x;
-    const bool wt = e.arrive_cnt != nullptr;
-    const int n_prod = e.n_slot_blocks + 1 + (e.n_rjobs > 0 ? e.rjob_blocks[0] : 0) + (e.n_rjobs > 1 ? e.rjob_blocks[1] : 0) +
-                       (e.n_rjobs > 2 ? e.rjob_blocks[2] : 0);
-    if (b < n_prod) {  // producers
-      if (b < e.n_slot_blocks) {
-        const int slot = b / e.slot_bx, x = b - slot * e.slot_bx;
-        if (slot < e.n_slots)
-          slot_reduce_block256(e.colsum + (size_t)slot * e.tiles * e.width, e.tiles, e.width, e.slot_n[slot], e.slot_out[slot], x, wt);
-      } else if (b == e.n_slot_blocks) {
-        if (e.fin_stats != nullptr) loss_finalize_block256(e.fin_partial, e.fin_blocks, e.fin_moments, e.fin_stats, e.fin_part, e.fin_n_count);
-      } else {
-        b -= e.n_slot_blocks + 1;
-        int j = 0;
-        while (j + 1 < e.n_rjobs && b >= e.rjob_blocks[j]) b -= e.rjob_blocks[j], ++j;
-        // (slab_job_block_wide strides by gridDim.x: give it this job's own block index and count)
-        slab_job_rider<true>(e.rjob[j], b, e.rjob_blocks[j]);
-      }
-      if (wt) post_arrive(e.arrive_cnt);
-      return;
-    }
-    b -= n_prod;
-    if (e.post.G != nullptr) {  // consumers
-      if (b < e.post.n_temb) {
-        temb_g_block(e.post, b, (float*)rider_smem);
-      } else if (b < e.post.n_temb + e.post.n_dw0t) {
-        post_wait(e.post);
-        dw0_temb_block(e.post, b - e.post.n_temb);
-      }
-    }
-    return;
-  }
-  const int bid = blockIdx.x - gr.ex.n_blocks;
+  const int bid = blockIdx.x;
   int j = 0;
 #pragma unroll
   for (int i = 1; i < MAX_TN_JOBS; ++i)
@@ -557,49 +498,6 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gemm_tn_group_kernel(c
   const int tb = (a.N2 + 127) / 128;
   const int fa0 = (tile / tb) * 128, fb0 = (tile % tb) * 128;
   tn_tile<P, 2, 2, 4, 4, NBUF>(a, split, fa0, fb0);
-  if (a.red_cnt == nullptr) return;
-  // ---- folded slab reduction (guide section 6, guideline 16: every handed-off byte an sc1 store drained before ONE relaxed
-  // agent-scope add; the workgroup whose add came last reads with sc1 loads behind its barrier)
-  __shared__ int last_s;
-  DPPO_HANDOVER_DRAIN();
-  __syncthreads();
-  if (threadIdx.x == 0)
-    last_s = __hip_atomic_fetch_add(a.red_cnt + tile, 1u, DPPO_HANDOVER_ARRIVE_ORDER, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)a.splits - 1;
-  __syncthreads();
-  if (!last_s) return;
-  DPPO_HANDOVER_ACQUIRE();
-  if (threadIdx.x == 0) __hip_atomic_store(a.red_cnt + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call
-  const int N1p = (a.N1 + 3) & ~3;
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.slab, 0, (int)((size_t)a.splits * a.N2 * N1p * 4), 0x00020000);
-  const int nr4 = (min(128, N1p - fa0) + 3) / 4, nc = min(128, a.N2 - fb0);  // the tile in units of (4 rows of C, 1 column)
-  const size_t sstride = (size_t)a.N2 * N1p * 4;                             // bytes between two splits' slabs
-  for (int i = threadIdx.x; i < nr4 * nc; i += 256) {
-    const int c = fb0 + i / nr4, r0 = fa0 + (i % nr4) * 4;
-    const size_t off = ((size_t)c * N1p + r0) * 4;
-    f32x4 p[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) p[u] = (f32x4){0.f, 0.f, 0.f, 0.f};  // same summation tree per element as slab_job_block()
-    int k = 0;
-    for (; k + 8 <= a.splits; k += 8) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        p[u] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(off + (k + u) * sstride), 0, 16));  // sc1
-    }
-    for (; k < a.splits; ++k)
-      p[k & 7] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(off + k * sstride), 0, 16));
-    const f32x4 v = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int r = r0 + e;
-      if (r >= a.N1) continue;
-      if (a.red_n2a >= 0 && c >= a.red_n2a)
-        a.red_out2[(size_t)r * a.red_ldo2 + (c - a.red_n2a)] = v[e];
-      else if (a.red_transpose)
-        a.red_out[(size_t)c * a.red_ldo + r] = v[e];
-      else
-        a.red_out[(size_t)r * a.red_ldo + c] = v[e];
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -809,7 +707,7 @@ void launch_gemm_tn_group(const GemmTNGroup& gr, hipStream_t s) {
     bytes += (double)a.M * (a.N1 + a.N2) * ES + 4.0 * a.N1 * a.N2;  // both operands once + the fp32 result
   }
   const bool probe = probe_begin(PROBE_GEMM_TN, s);
-  const dim3 grid(gr.base[gr.n] + gr.ex.n_blocks);
+  const dim3 grid(gr.base[gr.n]);
   const int nbuf = g_tn_nbuf != 0 ? g_tn_nbuf : ((int)grid.x > 3 * 256 && gr.n > 0 && gr.j[0].M >= 32768 ? 2 : 1);
   if (nbuf == 1)
     hipLaunchKernelGGL((gemm_tn_group_kernel<P, 1>), grid, dim3(256), LDS / 2, s, gr);
@@ -819,352 +717,6 @@ void launch_gemm_tn_group(const GemmTNGroup& gr, hipStream_t s) {
 }
 template void launch_gemm_tn_group<F32>(const GemmTNGroup&, hipStream_t);
 template void launch_gemm_tn_group<BF16>(const GemmTNGroup&, hipStream_t);
-
-// ------------------------------------------------------------------------------------------------
-// gemm_tn from K-major fragment operands (gemm.h, GemmTNFrag): one WAVE owns a 64 x (16 TB) tile of C for one row split and
-// walks its k-steps with D of them in flight in registers (4 + TB fragments of 1 KB each per k-step); a workgroup is four such
-// waves on neighbouring tiles (2 x 2, or 4 x 1 for thin outputs) that share operand fragments through L1 -- and nothing else:
-// no LDS, no barrier, no transposed read.  Loads return in issue order and the compiler counts vmcnt from the register
-// dependences, so the loop body is "multiply slot d, refill slot d".
-// Work order inside a job: split index fastest (multiples of 8 => a split's tiles share an XCD and its L2, as in
-// gemm_tn_group_kernel).
-typedef __attribute__((address_space(3))) int lds_int;
-template <int TB, int D>
-__device__ __forceinline__ void tn_frag_wave(const GemmTNFrag& a, const int split, const int ablk, const int bblk, const int lane,
-                                             lds_int* progress) {  // progress: non-null on the wave that paces the prefetcher
-  constexpr int TA = 4;
-  const int r = lane & 15, g = lane >> 4;
-  const int ks0 = split * a.ks_per_split;
-  int ks1 = ks0 + a.ks_per_split;
-  ks1 = ks1 < a.ks_total ? ks1 : a.ks_total;
-  const int fa0 = ablk * TA, fb0 = bblk * TB;  // first feature tiles
-  // tiles past the tensors' widths (N1 not a multiple of 64, ...) are clamped to the last one and never stored
-  int ta[TA], tbv[TB];
-#pragma unroll
-  for (int i = 0; i < TA; ++i) ta[i] = fa0 + i < a.nta ? fa0 + i : a.nta - 1;
-#pragma unroll
-  for (int j = 0; j < TB; ++j) tbv[j] = fb0 + j < a.ntb ? fb0 + j : a.ntb - 1;
-  f32x4 acc[TA][TB];
-#pragma unroll
-  for (int i = 0; i < TA; ++i)
-#pragma unroll
-    for (int j = 0; j < TB; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  u32x4 fa[D][TA], fb[D][TB];
-  const u32x4* Ap = a.A + lane;
-  const u32x4* Bp = a.B + lane;
-  auto fetch = [&](int d, int ks) {
-    ks = ks < ks1 ? ks : ks1 - 1;  // past the end: a harmless reload of the last k-step (never multiplied)
-    const u32x4* pa = Ap + (size_t)ks * a.nta * 64;
-    const u32x4* pb = Bp + (size_t)ks * a.ntb * 64;
-#pragma unroll
-    for (int i = 0; i < TA; ++i) fa[d][i] = pa[ta[i] * 64];
-#pragma unroll
-    for (int j = 0; j < TB; ++j) fb[d][j] = pb[tbv[j] * 64];
-  };
-  if (ks1 > ks0) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) fetch(d, ks0 + d);
-    for (int ks = ks0; ks < ks1; ks += D) {
-      if (progress != nullptr && lane == 0) __hip_atomic_store(progress, ks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        if (ks + d < ks1) {
-#pragma unroll
-          for (int i = 0; i < TA; ++i)
-#pragma unroll
-            for (int j = 0; j < TB; ++j) acc[i][j] = BF16::mma(fa[d][i], fb[d][j], acc[i][j]);
-        }
-        fetch(d, ks + d + D);
-      }
-    }
-  }
-  float* out = a.slab + (size_t)split * a.N1 * a.ldc;
-#pragma unroll
-  for (int i = 0; i < TA; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n1 = (fa0 + i) * 16 + 4 * g + e;
-      if (n1 >= a.N1) continue;
-#pragma unroll
-      for (int j = 0; j < TB; ++j) {
-        const int n2 = (fb0 + j) * 16 + r;
-        if (n2 < a.N2) out[(size_t)n1 * a.ldc + n2] = acc[i][j][e];
-      }
-    }
-}
-
-// The same contraction with the workgroup's fragments shared through an LDS ring, behind a deep L2 PREFETCH by a fifth wave.
-// Measured (rocprofv3 --pmc, gpurun_out/r3g): in every form of this product tried here -- the transposing LDS kernel
-// (gemm_tn_group_kernel, 75 us per actor group), the register-only form below (80 us), a plain LDS ring (80 us) -- the waves
-// spend 60 % of their cycles in s_waitcnt / barriers with the matrix cores at ~15 %: 39 % of the L2 requests miss (every line is
-// wanted by several output tiles at about the same time and the first asker pays the HBM latency), vmcnt is in ISSUE ORDER,
-// and so each k-step of a ring waits for its slowest line: the look-ahead that should hide HBM is spent waiting on it.
-// A prefetch issued by the consuming waves themselves does not help (it sits in the same in-order queue in front of the
-// ring loads: knob 33 had no effect at any distance).  So the roles are split by WAVE:
-//  * waves 0-3 (2 x 2 tiles of 64 x 64, or 4 x 1 for thin outputs) fetch each fragment of the workgroup's tile ONCE per
-//    k-step, by LDS-DMA (1 KB per wave instruction, landed lane-linear), into NST one-k-step stages, and read their 4 + TB
-//    fragments back with conflict-free ds_read_b128;
-//  * wave 4 computes nothing: per k-step it issues this workgroup's share of the split's fragments (the workgroups of one row
-//    split -- same XCD, same L2: split index fastest, splits a multiple of 8 -- divide each k-step's fragments among them)
-//    PFD k-steps ahead, by LDS-DMA into a dump slot nobody reads, never waits for them, and joins the k-step's barrier to
-//    keep pace.  Its vmcnt is its own: HBM latency lands on loads nobody waits for, the ring sees L2 hits.
-template <int WGA, int TB, int NST, int NPW>
-__device__ __forceinline__ void tn_fragl_wg(const GemmTNFrag& a, const int split, const int tile, char* smem) {
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  typedef const __attribute__((address_space(1))) void* glb_ptr;
-  constexpr int TA = 4, WGB = 4 / WGA, FA = WGA * TA, FB = WGB * TB, NF = FA + FB, NLD = (NF + 3) / 4;
-  constexpr int STAGE = NLD * 4 * 1024;  // bytes; slots NF .. 4 NLD - 1 receive dummy loads (same vmcnt count on every wave)
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int wa = wid % WGA, wb = (wid & 3) / WGA;
-  const int nab = ((a.N1 + 63) / 64 + WGA - 1) / WGA;
-  const int nbb = ((a.N2 + 16 * TB - 1) / (16 * TB) + WGB - 1) / WGB;  // workgroup tiles along A, B
-  const int fa0 = (tile / nbb) * FA, fb0 = (tile % nbb) * FB;           // the workgroup's first feature tiles
-  const int ks0 = split * a.ks_per_split;
-  int ks1 = ks0 + a.ks_per_split;
-  ks1 = ks1 < a.ks_total ? ks1 : a.ks_total;
-  const int nks = ks1 - ks0;
-  if (wid == 4) {  // ---- the prefetcher
-    if (nks <= 0) return;
-    const int nAu = min(a.nta, (a.N1 + 15) / 16), nBu = min(a.ntb, (a.N2 + 15) / 16), G = nab * nbb;
-    const u32x4* psrc[NPW];
-    int pstride[NPW];
-#pragma unroll
-    for (int i = 0; i < NPW; ++i) {
-      int f = tile + G * i;
-      f = f < nAu + nBu ? f : nAu + nBu - 1;  // (nothing left for this workgroup: a duplicate -- one issue pattern)
-      const bool isA = f < nAu;
-      psrc[i] = (isA ? a.A + (size_t)f * 64 : a.B + (size_t)(f - nAu) * 64) + lane;
-      pstride[i] = (isA ? a.nta : a.ntb) * 64;
-    }
-    char* dump = smem + NST * STAGE;
-    const int lead = NST - 1 + a.pfd;
-    for (int st = 0; st < nks; ++st) {
-      int kp = ks0 + st + lead;
-      if (kp < ks1 && !(a.dbg & 4)) {
-#pragma unroll
-        for (int i = 0; i < NPW; ++i)
-          __builtin_amdgcn_global_load_lds((glb_ptr)(psrc[i] + (size_t)kp * pstride[i]), (lds_ptr)dump, 16, 0, 0);
-      }
-      __syncthreads();
-    }
-    return;
-  }
-  if (nks <= 0) {  // a surplus split: zeros (whole workgroup: no barrier is left behind)
-    float* out = a.slab + (size_t)split * a.N1 * a.ldc;
-#pragma unroll
-    for (int i = 0; i < TA; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int n1 = (fa0 + wa * TA + i) * 16 + 4 * g + e;
-        if (n1 >= a.N1) continue;
-#pragma unroll
-        for (int j = 0; j < TB; ++j) {
-          const int n2 = (fb0 + wb * TB + j) * 16 + r;
-          if (n2 < a.N2) out[(size_t)n1 * a.ldc + n2] = 0.f;
-        }
-      }
-    return;
-  }
-  // this wave's NLD loads of a stage: slot f = wid + 4 i -> (operand, feature tile), clamped to the tensor's last tile
-  const u32x4* src[NLD];
-  int kstride[NLD];
-#pragma unroll
-  for (int i = 0; i < NLD; ++i) {
-    const int f = wid + 4 * i;
-    const bool isA = f < FA || f >= NF;  // (dummy slots reload an A fragment)
-    int t = f < FA ? fa0 + f : (f < NF ? fb0 + (f - FA) : fa0);
-    const int nt = isA ? a.nta : a.ntb;
-    t = t < nt ? t : nt - 1;
-    src[i] = (isA ? a.A : a.B) + (size_t)t * 64 + lane;
-    kstride[i] = nt * 64;
-  }
-  auto dma = [&](int ks, int buf) {
-    char* st = smem + buf * STAGE;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i)
-      __builtin_amdgcn_global_load_lds((glb_ptr)(src[i] + (size_t)ks * kstride[i]), (lds_ptr)(st + (wid + 4 * i) * 1024), 16, 0, 0);
-  };
-  f32x4 acc[TA][TB];
-#pragma unroll
-  for (int i = 0; i < TA; ++i)
-#pragma unroll
-    for (int j = 0; j < TB; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int p = 0; p < NST - 1; ++p)
-    if (p < nks) dma(ks0 + p, p);
-  for (int st = 0; st < nks; ++st) {
-    // this wave's share of stage st has landed once at most the DMAs of the NST - 2 younger stages are outstanding (vmcnt
-    // counts in issue order); near the end fewer are in flight: wait for all
-    if (st + NST - 2 < nks)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * NLD) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // everyone's share landed, and everyone is done reading the stage refilled next
-    if (st + NST - 1 < nks && !(a.dbg & 2)) dma(ks0 + st + NST - 1, (st + NST - 1) % NST);
-    const char* sb = smem + (st % NST) * STAGE + lane * 16;
-    u32x4 af[TA], bf[TB];
-#pragma unroll
-    for (int i = 0; i < TA; ++i) af[i] = *(const u32x4*)(sb + (wa * TA + i) * 1024);
-#pragma unroll
-    for (int j = 0; j < TB; ++j) bf[j] = *(const u32x4*)(sb + (FA + wb * TB + j) * 1024);
-    if (!(a.dbg & 1)) {
-#pragma unroll
-      for (int i = 0; i < TA; ++i)
-#pragma unroll
-        for (int j = 0; j < TB; ++j) acc[i][j] = BF16::mma(af[i], bf[j], acc[i][j]);
-    } else {  // (timing experiment: keep the LDS reads alive)
-      acc[0][0][0] += __uint_as_float(af[0].x ^ af[1].x ^ af[2].x ^ af[3].x ^ bf[0].x ^ bf[TB - 1].y);
-    }
-  }
-  float* out = a.slab + (size_t)split * a.N1 * a.ldc;
-#pragma unroll
-  for (int i = 0; i < TA; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n1 = (fa0 + wa * TA + i) * 16 + 4 * g + e;
-      if (n1 >= a.N1) continue;
-#pragma unroll
-      for (int j = 0; j < TB; ++j) {
-        const int n2 = (fb0 + wb * TB + j) * 16 + r;
-        if (n2 < a.N2) out[(size_t)n1 * a.ldc + n2] = acc[i][j][e];
-      }
-    }
-}
-// ring stages: 4 x 16 KB (2 x 2 waves) or 3 x 20 KB (4 x 1), + the prefetcher's 1 KB dump slot: 65 KB, two workgroups per CU
-constexpr int TN_FRAGL_LDS = 4 * 16 * 1024 + 1024;
-static_assert(3 * 20 * 1024 + 1024 <= TN_FRAGL_LDS, "thin configuration's ring");
-__global__ __launch_bounds__(320, 2) void gemm_tn_fragl_kernel(const GemmTNFragGroup gr) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int jn = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_TN_JOBS; ++i)
-    if (i < gr.n && (int)blockIdx.x >= gr.base[i]) jn = i;
-  const GemmTNFrag& a = gr.j[jn];
-  const int local = blockIdx.x - gr.base[jn];
-  const int split = local % a.splits, tile = local / a.splits;
-  // (npf: fragments per k-step / workgroups per split, capped at what is instantiated: gemm_tn_frag_prepare)
-  if (a.wga == 2) {
-    if (a.npf <= 4)
-      tn_fragl_wg<2, 4, 4, 4>(a, split, tile, smem);
-    else
-      tn_fragl_wg<2, 4, 4, 8>(a, split, tile, smem);
-  } else if (a.tb == 4) {
-    tn_fragl_wg<4, 4, 3, 8>(a, split, tile, smem);
-  } else if (a.tb == 2) {
-    tn_fragl_wg<4, 2, 3, 8>(a, split, tile, smem);
-  } else {
-    tn_fragl_wg<4, 1, 3, 8>(a, split, tile, smem);
-  }
-}
-
-// ... with a fifth, prefetching wave per workgroup (see gemm_tn_fragl_kernel): it fetches this workgroup's share of the row
-// split's fragments a.pfd k-steps ahead of wave 0's progress (an LDS word), by LDS-DMA into a dump slot, and waits for nothing.
-template <int D>
-__global__ __launch_bounds__(320, 2) void gemm_tn_frag_kernel(const GemmTNFragGroup gr) {
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  typedef const __attribute__((address_space(1))) void* glb_ptr;
-  __shared__ __attribute__((aligned(16))) char dump[1024];
-  __shared__ int prog;
-  int jn = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_TN_JOBS; ++i)
-    if (i < gr.n && (int)blockIdx.x >= gr.base[i]) jn = i;
-  const GemmTNFrag& a = gr.j[jn];
-  const int local = blockIdx.x - gr.base[jn];
-  const int split = local % a.splits, tile = local / a.splits;
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nab = ((a.N1 + 63) / 64 + a.wga - 1) / a.wga;
-  const int nbb = ((a.N2 + 16 * a.tb - 1) / (16 * a.tb) + a.wgb - 1) / a.wgb;  // workgroup tiles along A, B
-  const int ks0 = split * a.ks_per_split;
-  int ks1 = ks0 + a.ks_per_split;
-  ks1 = ks1 < a.ks_total ? ks1 : a.ks_total;
-  if (threadIdx.x == 0) prog = ks0;
-  __syncthreads();
-  if (wid == 4) {  // ---- the prefetcher
-    if (a.pfd <= 0 || (a.dbg & 4)) return;
-    const int nAu = min(a.nta, (a.N1 + 15) / 16), nBu = min(a.ntb, (a.N2 + 15) / 16), G = nab * nbb;
-    constexpr int NPW = 8;
-    const int npw = a.npf < NPW ? a.npf : NPW;
-    for (int kp = ks0 + D; kp < ks1; ++kp) {
-      // stay at most pfd k-steps ahead of wave 0 (which may itself have left already: then run to the end)
-      while (kp - __hip_atomic_load((lds_int*)&prog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > a.pfd + D) __builtin_amdgcn_s_sleep(8);
-      for (int i = 0; i < npw; ++i) {
-        int f = tile + G * i;
-        if (f >= nAu + nBu) break;
-        const bool isA = f < nAu;
-        const u32x4* src = (isA ? a.A + ((size_t)kp * a.nta + f) * 64 : a.B + ((size_t)kp * a.ntb + (f - nAu)) * 64) + lane;
-        __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)dump, 16, 0, 0);
-      }
-    }
-    return;
-  }
-  const int ablk = (tile / nbb) * a.wga + wid % a.wga, bblk = (tile % nbb) * a.wgb + wid / a.wga;
-  if (ablk * 64 >= a.N1 || bblk * 16 * a.tb >= a.N2) {
-    if (wid == 0 && lane == 0) prog = 0x3fffffff;  // (nothing to pace: let the prefetcher run out)
-    return;
-  }
-  lds_int* pp = wid == 0 ? (lds_int*)&prog : nullptr;
-  if (a.tb == 4)
-    tn_frag_wave<4, D>(a, split, ablk, bblk, lane, pp);
-  else if (a.tb == 2)
-    tn_frag_wave<2, D>(a, split, ablk, bblk, lane, pp);
-  else
-    tn_frag_wave<1, D>(a, split, ablk, bblk, lane, pp);
-  if (wid == 0 && lane == 0) __hip_atomic_store((lds_int*)&prog, 0x3fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-int gemm_tn_frag_blocks(const GemmTNFrag& j) {
-  const int nab = ((j.N1 + 63) / 64 + j.wga - 1) / j.wga;
-  const int nbb = ((j.N2 + 16 * j.tb - 1) / (16 * j.tb) + j.wgb - 1) / j.wgb;
-  return nab * nbb * j.splits;
-}
-static int g_tn_frag_dbg = 0;  // tuning knob 34 (timing experiments, results wrong): 1 no MFMAs, 2 no ring loads, 4 no prefetch
-void set_gemm_tn_frag_dbg(int v) { g_tn_frag_dbg = v; }
-static int g_tn_frag_pfd = 12;  // tuning knob 33: k-steps the L2 prefetch runs ahead of the ring's own loads
-void set_gemm_tn_frag_pfd(int v) { g_tn_frag_pfd = v < 0 ? 0 : (v > 64 ? 64 : v); }
-// wave shape of a job's workgroups and its prefetch share; false if the LDS-ring kernel has no configuration for it
-bool gemm_tn_frag_prepare(GemmTNFrag& j) {
-  j.tb = j.N2 <= 16 ? 1 : (j.N2 <= 32 ? 2 : 4);
-  const int nba = (j.N1 + 63) / 64, nbbk = (j.N2 + 16 * j.tb - 1) / (16 * j.tb);
-  j.wgb = nbbk >= 2 ? 2 : 1, j.wga = 4 / j.wgb;
-  const int nab = (nba + j.wga - 1) / j.wga, nbb = (nbbk + j.wgb - 1) / j.wgb;
-  const int nAu = j.nta < (j.N1 + 15) / 16 ? j.nta : (j.N1 + 15) / 16, nBu = j.ntb < (j.N2 + 15) / 16 ? j.ntb : (j.N2 + 15) / 16;
-  j.npf = (nAu + nBu + nab * nbb - 1) / (nab * nbb);  // fragments per k-step and workgroup of a split
-  j.npf = j.npf < 8 ? j.npf : 8;  // what the kernel instantiates (4 or 8 per k-step: the prefetcher's vmcnt holds 63); a job
-                                  // with more prefetches the first ones only
-  j.pfd = g_tn_frag_pfd;
-  j.dbg = g_tn_frag_dbg;
-  return true;
-}
-static int g_tn_frag_depth = 0;  // tuning knob 32: 0 (default) the LDS-ring kernel; 2..4: the register-only kernel at that depth
-void set_gemm_tn_frag_depth(int v) { g_tn_frag_depth = v <= 0 ? 0 : (v < 2 ? 2 : (v > 4 ? 4 : v)); }
-void launch_gemm_tn_frag_group(const GemmTNFragGroup& gr, int64_t M, hipStream_t s) {
-  if (gr.n <= 0) return;
-  double flops = 0, bytes = 0;
-  for (int i = 0; i < gr.n; ++i) {
-    const GemmTNFrag& a = gr.j[i];
-    flops += 2.0 * M * a.N1 * a.N2;
-    bytes += (double)M * (a.N1 + a.N2) * 2 + 4.0 * a.N1 * a.N2;  // both operands once + the fp32 result
-  }
-  const bool probe = probe_begin(PROBE_GEMM_TN, s);
-  const dim3 grid(gr.base[gr.n]);
-  if (g_tn_frag_depth == 0) {
-    static DevLatch attr_set;
-    if (attr_set.need()) {
-      (void)hipFuncSetAttribute((const void*)gemm_tn_fragl_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_FRAGL_LDS);
-      attr_set.done();
-    }
-    hipLaunchKernelGGL(gemm_tn_fragl_kernel, grid, dim3(320), TN_FRAGL_LDS, s, gr);
-  } else if (g_tn_frag_depth == 2)
-    hipLaunchKernelGGL((gemm_tn_frag_kernel<2>), grid, dim3(320), 0, s, gr);
-  else if (g_tn_frag_depth == 4)
-    hipLaunchKernelGGL((gemm_tn_frag_kernel<4>), grid, dim3(320), 0, s, gr);
-  else
-    hipLaunchKernelGGL((gemm_tn_frag_kernel<3>), grid, dim3(320), 0, s, gr);
-  if (probe) probe_end(s, flops, bytes);
-}
 
 static int g_tn_thin = 1;  // tuning knob 6: 0 = no one-tile 512 x 64 configuration for thin outputs
 void set_gemm_tn_thin(int v) { g_tn_thin = v; }

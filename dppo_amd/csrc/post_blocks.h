@@ -1,12 +1,12 @@
-// Device code shared by the reduction / post-reduction launches (ppo.hip: tail_reduce_kernel, post_reduce_kernel) and the
-// riders of the weight-gradient GEMM launch (gemm.hip, GemmTNExtra): the many-slab reduction of the in-kernel dW0, the
-// time-embedding gradient (G = W0_temb^T . S, the time MLP's backward) and the time columns of dW0.
+// Device code of the reduction / post-reduction launches (ppo.hip: tail_reduce_kernel, post_reduce_kernel): the many-slab
+// reduction of the in-kernel dW0, the time-embedding gradient (G = W0_temb^T . S, the time MLP's backward) and the time columns
+// of dW0.
 //
-// Riding (PostReduce::wait_cnt != null, SlabJob results stored with `wt`): producers and consumers are workgroups of ONE launch,
-// dispatched in index order with the producers first.  A producer stores its results write-through (agent-scope relaxed atomic
-// stores = sc1), drains them, and thread 0 adds 1 to the counter; a consumer polls the counter (bounded) and reads the producers'
-// results with agent-scope relaxed loads (sc1) -- the fence-free hand-over of common.h (DPPO_HANDOVER_*), release / acquire on
-// targets where that shortcut is not an ISA property.
+// One-launch tail (PostReduce::wait_cnt != null, SlabJob results stored with `wt`): producers and consumers are workgroups of ONE
+// launch, dispatched in index order with the producers first.  A producer stores its results write-through (agent-scope relaxed
+// atomic stores = sc1), drains them, and thread 0 adds 1 to the counter; a consumer polls the counter (bounded) and reads the
+// producers' results with agent-scope relaxed loads (sc1) -- the fence-free hand-over of common.h (DPPO_HANDOVER_*), release /
+// acquire on targets where that shortcut is not an ISA property.
 #pragma once
 #include "common.h"
 #include "ppo.h"
@@ -21,11 +21,11 @@ __device__ __forceinline__ float sinus_feat(int t, int j, int td) {
   return j < half ? sinf(ang) : cosf(ang);
 }
 
-// a value another workgroup of this launch may have produced (riding) or an earlier launch did (plain load)
+// a value another workgroup of this launch may have produced (one-launch tail) or an earlier launch did (plain load)
 __device__ __forceinline__ float post_in(const PostReduce& q, const float* p) {
   return q.wait_cnt != nullptr ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
 }
-// riding: wait (bounded: a logic error must fail a test, not hang the GPU) until `need` producer workgroups have arrived
+// one-launch tail: wait (bounded: a logic error must fail a test, not hang the GPU) until `need` producer workgroups have arrived
 __device__ __forceinline__ void post_wait(const PostReduce& q) {
   if (q.wait_cnt == nullptr) return;
   if (threadIdx.x == 0) {
@@ -146,7 +146,7 @@ __device__ __forceinline__ void dw0_temb_block(const PostReduce& q, int b) {
 // a thread per element would add 256 values in eight dependent batches on three CUs (measured 44 us for a 256 x 11 output).  Here
 // 64 consecutive elements belong to a block, wave w of it adds slabs w, w + NW, w + 2 NW, ... (NW = waves per block, at most 16
 // loads in flight per lane, one or two memory latencies), and wave 0 adds the NW partial sums in a fixed order.
-template <bool WT = false>  // WT: results stored write-through (riding: read by other workgroups of this launch)
+template <bool WT = false>  // WT: results stored write-through (read by other workgroups of this launch)
 __device__ __forceinline__ void slab_job_block_wide(const SlabJob& J, int bx = -1, int nbx = 0) {  // bx >= 0: block bx of nbx instead of blockIdx.x / gridDim.x
   __shared__ float wred[16][64];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, NW = blockDim.x >> 6;
@@ -181,43 +181,6 @@ __device__ __forceinline__ void slab_job_block_wide(const SlabJob& J, int bx = -
   }
 }
 
-// The same reduction for a 256-thread rider block of a memory-saturated launch: 16 consecutive elements x 16 slab lanes, every lane's
-// loads (splits / 16 of them, at most 16) in flight at once -- under the GEMM's load a dependent batch costs several microseconds,
-// and eight of them in a row (slab_job_block_wide at four waves) made the riders the launch's critical path.  Fixed order: a lane
-// adds its slabs k = q, q + 16, ... in order, then the 16 lanes' partial sums are added in lane order.
-template <bool WT>
-__device__ __forceinline__ void slab_job_rider(const SlabJob& J, int bx, int nbx) {
-  __shared__ float rred[16][17];
-  const int el = threadIdx.x & 15, q = threadIdx.x >> 4;
-  const size_t n = (size_t)J.rows * J.cols, stride = (size_t)J.rows * J.lds;
-  for (size_t e0 = (size_t)bx * 16; e0 < n; e0 += (size_t)nbx * 16) {
-    const size_t i = e0 + el;
-    const bool live = i < n;
-    const int r = live ? (int)(i / J.cols) : 0, c = live ? (int)(i % J.cols) : 0;
-    const float* src = J.slab + (size_t)r * J.lds + J.c0 + c;
-    float t[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) t[u] = live && q + 16 * u < J.splits ? src[(size_t)(q + 16 * u) * stride] : 0.f;
-    float v = 0.f;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) v += t[u];
-    for (int k = q + 256; k < J.splits; k += 16) v += live ? src[(size_t)k * stride] : 0.f;  // (more than 256 slabs: never today)
-    rred[q][el] = v;
-    __syncthreads();
-    if (q == 0 && live) {
-      float sum = 0.f;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) sum += rred[u][el];
-      float* dst = J.transpose ? J.out + (size_t)c * J.ldo + r : J.out + (size_t)r * J.ldo + c;
-      if constexpr (WT)
-        __hip_atomic_store(dst, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else
-        *dst = sum;
-    }
-    __syncthreads();
-  }
-}
-
 // Block tb of the time-embedding part (PostReduce::n_temb blocks of 256 threads): G[k][j] = sum_h W0[h][AF + j] S[h][k], one wave
 // per output, and -- in the last block of the range, once the others have arrived -- the time MLP's backward.  sh: dynamic LDS,
 // time_backward_lds(Kft, td) bytes.
@@ -231,7 +194,7 @@ __device__ __forceinline__ void temb_g_block(const PostReduce& q, int tb, float*
     const bool rest = q.S_rest != nullptr && k == q.Kft - 1;
     float acc = 0.f;
     int h = lane;
-    for (; h + 7 * 64 < q.H; h += 8 * 64) {  // (eight of the other workgroups' values in flight: riding, each is a trip past L2)
+    for (; h + 7 * 64 < q.H; h += 8 * 64) {  // (eight of the other workgroups' values in flight: with wait_cnt each is a trip past L2)
       float sv[8], wv[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {

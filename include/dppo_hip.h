@@ -468,9 +468,9 @@ int dppo_probe_collect_bytes(double* total_ms_host, int* launches_host, double* 
  *         of them pays)
  * knob 8: timing experiments (results are wrong while set): bit 0 / 1 the fused backward without its gradient stores / derivative
  *         fetch, bit 2 / 3 / 4 the reduction launch behind the weight-gradient GEMMs without its slab reductions / bias sums / loss
- *         statistics (tools/tail_reduce_parts.sh); knob 9: side streams at low priority
+ *         statistics (tools/tail_reduce_parts.sh)
  * knob 5: weight-gradient GEMM kernel, 0 = register-staged (default), 1..8 = an LDS-DMA ring configuration, -1 = by shape
- * knob 6: thin (512 x 64) weight-gradient tiles on / off; knob 10: critic side stream gated on the actor's forward (0 off)
+ * knob 6: thin (512 x 64) weight-gradient tiles on (default 1) / off
  * knob 11: time-embedding gradient from a one-hot of the denoising step in the K padding of the actor's input rows, so
  *          the first layer's weight-gradient GEMM also yields the per-step sums of dh0 (default 1); 0 = separate
  *          gemm_nt + segmented sum on the tail stream
@@ -498,12 +498,6 @@ int dppo_probe_collect_bytes(double* total_ms_host, int* launches_host, double* 
  * knob 27: sampler, small env batches of one-block bf16 networks at hidden 512: one 16-row tile over eight workgroups with
  *          the weights resident in registers (default 1; see dppo_sample_chain_workspace_bytes) or over one (0)
  * knob 28: knob 27's kernel: 64-cycle sleep periods between a workgroup's exchange store and its first sweep (default 4)
- * knob 31: weight-gradient GEMMs of one-block bf16 networks (merged forward + one-block backward + one-hot time columns, no
- *          cond_mlp, PPO update without d loss / d obs): act(h_0), act(z1), dz1, dh_0 are written by the fused kernels as
- *          K-major MFMA operand fragments and contracted without any transpose (1), or row-major through the transposing
- *          LDS kernel (0, default: the fragment form is parity-green but not faster yet)
- * knob 32: 0 (default): the fragments of a workgroup's tile are fetched once per k-step by LDS-DMA into a four-stage ring and
- *          read back by its four waves; 2..4: every wave loads its own fragments into registers, that many k-steps ahead
  * knob 36: the minibatch's advantage moments (PPO update, single rank): partial sums by the last 64 blocks of the row builder's
  *          launch, added by every block of the loss kernel (1: always; 0, default: for minibatches of at most 16,384 samples, where
  *          the step is a chain of launches), or a launch of their own between the rows and the actor's forward (2: always; at
@@ -515,25 +509,15 @@ int dppo_probe_collect_bytes(double* total_ms_host, int* launches_host, double* 
  * knob 38: with knob 37, a denoiser's backward: the reductions that the backward kernel alone feeds (its first-layer slabs, the bias
  *          sums, the loss statistics) and the time-embedding gradient behind them run on the library's second side stream under
  *          the weight-gradient GEMM launch (1, default) or behind it with everything else (0)
- * knob 40: knob 38's work as extra workgroups in front of the tiles of the actor's weight-gradient GEMM launch, the time-embedding
- *          blocks waiting for the reductions on an arrival counter (1: no side stream, no event, no launch -- measured slower, the
- *          riders' dependent chain runs under the GEMM's memory load and the launch cannot end before it) or on the side stream
- *          (0, default)
  * knob 41: with knob 38: the slab reductions of the actor's weight-gradient GEMMs and what depends on the two thin products among
  *          them (low-rank dW2, dWout, db2) are one launch -- the dependent workgroups poll the thin reductions' arrival -- (1,
  *          default) or two launches (0)
- * knob 39: PPO update of a bf16 one-block actor at hidden 512 with a head of at most 16 outputs, actor and critic on two streams:
- *          the policy half of the loss (log-probs, ratio, clipped surrogate, d loss / d eps, statistics) runs in the epilogue
- *          of the actor's fused forward kernel (1) or as a launch of its own between forward and backward (0, default: the fused
- *          variant's register footprint costs the overlapped step more than the launch it saves)
- * knob 35: what follows the weight-gradient GEMMs of a backward pass -- slab sums, bias column sums, loss statistics -- inside
- *          the GEMM launch (1: the last workgroup at an output tile sums its slabs, the small reductions ride as extra
- *          workgroups; measured slower, 200 vs 107 + 32 us) or as a launch of its own (0, default)
- * knob 33: k-steps (of 32 batch rows) the fragment GEMM's L2 prefetch runs ahead of its ring loads (default 12)
  * knob 30: minibatch rows per output column from which the top block's weight gradient is taken low-rank (knob 16) and the
  *          one-block backward (knob 23) runs: M >= value x out_dim (default 100)
  * knob 29: knob 27's kernel: sweeps a workgroup waits for its tile before it gives up (default 2^20; tests force a time-out
- *          with 1; <= 0 restores the default) */
+ *          with 1; <= 0 restores the default)
+ * retired (experiments that were measured, lost and removed with their code): 9, 10, 31, 32, 33, 34, 35,
+ *          39, 40 -- setting one of them, like an unknown number, returns an error */
 int dppo_tune_set(int knob, int value);
 /* one bare layer GEMM: out[M][ldo] = act(X[M][Kp] . W[N][Kp]^T + bias) with elem = prec operands;
  * out_f32 and/or out_elem may be NULL; ldo >= round_up(N,16) */

@@ -55,6 +55,14 @@ def test_bad_arguments_are_rejected_with_a_message():
     assert lib.dppo_packed_bytes(C.byref(d), hip.PREC_BF16, 20) == -1
     assert lib.dppo_packed_bytes(C.byref(hopper_desc()), 7, 20) == -1
     assert lib.dppo_gae(None, None, None, None, 1, 1, 0.99, 0.95, 1.0, None, None, None, None, None) == -1
+    # tuning knobs: a retired or unknown number is an error that names it, never a silent no-op
+    for knob in (9, 10, 31, 32, 33, 34, 35, 39, 40):
+        assert lib.dppo_tune_set(knob, 1) != 0
+        msg = lib.dppo_last_error()
+        assert str(knob).encode() in msg and b"retired" in msg
+    assert lib.dppo_tune_set(99, 1) != 0
+    assert b"99" in lib.dppo_last_error() and b"unknown" in lib.dppo_last_error()
+    assert lib.dppo_tune_set(2, 1) == 0  # a live knob set to its default
 
 
 def test_python_layout_matches_c_abi_and_reference_names():

@@ -595,9 +595,9 @@ def test_fused_path_matches_layered_path(prec, tol, sname):
 
 @pytest.mark.parametrize("prec,tol", [("fp32", 2e-5), ("bf16", 2e-2)])
 @pytest.mark.parametrize("sname,knob", [("hopper", 22), ("can", 22), ("halfcheetah", 22), ("can_relu", 22), ("hopper", 23),
-                                        ("can", 23), ("square_like", 23), ("hopper", 25), ("halfcheetah", 25), ("hopper", 31),
-                                        ("halfcheetah", 31), ("can", 31), ("hopper", 36), ("can", 36), ("hopper", 37),
-                                        ("halfcheetah", 37), ("can", 37), ("hopper", 38), ("hopper", 39), ("hopper", 40), ("hopper", 41)])
+                                        ("can", 23), ("square_like", 23), ("hopper", 25), ("halfcheetah", 25), ("hopper", 36),
+                                        ("can", 36), ("hopper", 37), ("halfcheetah", 37), ("can", 37), ("hopper", 38),
+                                        ("hopper", 41)])
 def test_one_block_kernels_match_the_general_ones(prec, tol, sname, knob):
     _one_block_ab(prec, tol, sname, knob)
 
@@ -617,14 +617,12 @@ def _one_block_ab(prec, tol, sname, knob, N=6500, Kft=10):
     Wout W2 fragments ride the weight ring, and the critic).  Knob 23: the backward adds dh_1 = d_out . Wout last instead of carrying it,
     in forward-sized tiles, and the second layer's bias gradient comes from colsum(d_out) . Wout (every one-block network
     once the minibatch is large enough for the low-rank dW2).  Knob 25: both walk their short layers without the weight
-    stream's padding k-steps (bit-identical arithmetic: the skipped k-steps multiply zeros).  Knob 31 (bf16): act(h_0), act(z1),
-    dz1, dh_0 travel to the weight-gradient GEMMs as K-major MFMA fragments written by the fused kernels, contracted by the
-    LDS-free gemm_tn_frag_kernel (same operand bits; only the fp32 summation order over the batch differs).  Knob 36: the
+    stream's padding k-steps (bit-identical arithmetic: the skipped k-steps multiply zeros).  Knob 36: the
     advantage moments as partial sums riding the row builder's launch, added in the loss kernel's prologue.  Knob 37 (bf16): the
     first layer's weight gradient accumulated inside the one-block backward (dh_0 never stored; hopper: actor and critic, the
     others: the critic).  Knob 38: with it, the reductions the backward kernel feeds and the time-embedding gradient on a side
-    stream under the weight-gradient GEMMs.  Knob 39 (bf16): the policy half of the loss in the epilogue of the
-    actor's forward kernel.  Knob 40: knob 38's work as riders of the actor's weight-gradient GEMM launch instead of a side stream.  Knob 41: the GEMMs' slab reductions and the post-reduce parts behind them in one launch.  Same log-probs, values, loss
+    stream under the weight-gradient GEMMs.  Knob 41: the GEMMs' slab reductions and the post-reduce parts behind them in one
+    launch.  Same log-probs, values, loss
     statistics and gradients -- tensor by tensor -- as the general kernels."""
     from dppo_amd import hip
     lib = hip.load()
@@ -633,7 +631,7 @@ def _one_block_ab(prec, tol, sname, knob, N=6500, Kft=10):
     R = max(800, -(-N // Kft) + 16)  # (N >= 100 x out_dim: the low-rank dW2 -- and with it the one-block backward -- is on)
     AF = a.horizon_steps * a.action_dim
     out = {}
-    default = 0 if knob in (31, 36, 39, 40) else 1  # (these ship off: see csrc/api.hip g_frag, g_mom_rider, g_fuse_loss, g_tail_riders)
+    default = 0 if knob == 36 else 1  # (ships at 0 = by minibatch size: see csrc/api.hip g_mom_rider)
     try:
         for merged in (1, 0):
             lib.dppo_tune_set(knob, merged if merged or knob != 36 else 2)  # (knob 36: 0 = by minibatch size, 2 = never)
