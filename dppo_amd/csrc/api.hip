@@ -716,16 +716,7 @@ static void flush_slabs(MlpBufs<P>& B, hipStream_t s, const SlotOuts* slots = nu
   // tail_reduce_kernel)
   if (B.tn_group.n > 0) {
     GemmTNGroup& gr = B.tn_group;
-    for (int i = 1; i < gr.n; ++i)  // longest row ranges first (insertion sort: the short jobs fill the last round)
-      for (int k = i; k > 0 && gr.j[k].rows_per_split > gr.j[k - 1].rows_per_split; --k) {
-        const GemmTN t = gr.j[k];
-        gr.j[k] = gr.j[k - 1], gr.j[k - 1] = t;
-      }
-    gr.base[0] = 0;
-    for (int i = 0; i < gr.n; ++i) {
-      const int tiles = ((gr.j[i].N1 + 127) / 128) * ((gr.j[i].N2 + 127) / 128);
-      gr.base[i + 1] = gr.base[i] + gr.j[i].splits * tiles;
-    }
+    gemm_tn_group_order(gr);  // longest row ranges first, base[]
     launch_gemm_tn_group<P>(gr, s);
     gr.n = 0;
   }
@@ -2697,6 +2688,9 @@ int dppo_gemm_tn_raw(int prec, const void* A, int lda, int N1, const void* B, in
   if (int e = check_prec(prec)) return e;
   if (!A || !B || !slab || !C || M < 1 || M > 0x7fffffff || N1 < 1 || N2 < 1) return fail(-1, "bad argument");
   if (rows_per_split < 64 || rows_per_split % 64) return fail(-1, "rows_per_split must be a multiple of 64");
+  const int es = prec == DPPO_PREC_F32 ? 4 : 2;
+  if (lda < N1 || ldb < N2) return fail(-1, "lda / ldb smaller than N1 / N2");
+  if ((lda * es) % 16 || (ldb * es) % 16) return fail(-1, "lda and ldb must be multiples of %d", 16 / es);
   GemmTN t;
   memset(&t, 0, sizeof(t));
   t.A = A, t.B = B, t.M = (int)M, t.N1 = N1, t.N2 = N2, t.lda = lda, t.ldb = ldb, t.slab = slab, t.ldc = N2;
@@ -2706,5 +2700,92 @@ int dppo_gemm_tn_raw(int prec, const void* A, int lda, int N1, const void* B, in
   else
     launch_gemm_tn<BF16>(t, (hipStream_t)stream);
   launch_slab_reduce_2d(slab, t.splits, N1, N2, N2, C, N2, 1.f, (hipStream_t)stream);
+  return check_launch();
+}
+
+int dppo_gemm_nt_desc_raw(int prec, const dppo_gemm_nt_desc* d, dppo_stream_t stream) {
+  if (int e = check_prec(prec)) return e;
+  if (!d || !d->X || !d->W) return fail(-1, "null pointer");
+  if (!d->out_f32 && !d->out_pre && !d->out_act) return fail(-1, "null pointer: no output");
+  if (d->M < 1 || d->M > 0x7fffffff || d->N < 1) return fail(-1, "bad argument: M / N");
+  const int es = prec == DPPO_PREC_F32 ? 4 : 2;
+  if (d->Kp < 1 || (d->Kp * es) % 128) return fail(-1, "Kp must be a multiple of %d", 128 / es);
+  if (d->ldx < d->Kp || d->ldw < d->Kp) return fail(-1, "ldx / ldw smaller than Kp");
+  if ((d->ldx * es) % 16 || (d->ldw * es) % 16) return fail(-1, "ldx and ldw must be multiples of %d", 16 / es);
+  const int nst = (d->N + 15) & ~15;  // columns of every epilogue operand the kernel touches
+  if (d->dsrc_kind < 0 || d->dsrc_kind > 2) return fail(-1, "dsrc_kind must be 0, 1 or 2");
+  if (d->dsrc_kind != 0 && !d->dsrc) return fail(-1, "null pointer: dsrc");
+  if (d->dsrc_kind != 0 && (d->dsrc_ld < nst || d->dsrc_ld % 4)) return fail(-1, "dsrc_ld too small or not a multiple of 4");
+  if (d->res && (d->ldres < nst || d->ldres % 4)) return fail(-1, "ldres too small or not a multiple of 4");
+  if (d->add && (d->ldadd < nst || d->ldadd % 4)) return fail(-1, "ldadd too small or not a multiple of 4");
+  if (d->out_f32 && (d->ldo32 < nst || d->ldo32 % 4)) return fail(-1, "ldo32 too small or not a multiple of 4");
+  if ((d->out_pre || d->out_act) && (d->ldo < nst || d->ldo % 4)) return fail(-1, "ldo too small or not a multiple of 4");
+  if (d->act < 0 || d->act > ACT_NONE || d->dact < 0 || d->dact > ACT_NONE) return fail(-1, "act / dact must be 0, 1 or 2");
+  GemmNT g;
+  memset(&g, 0, sizeof(g));
+  g.X = d->X, g.W = d->W, g.bias = d->bias, g.M = (int)d->M, g.N = d->N, g.Kp = d->Kp, g.ldx = d->ldx, g.ldw = d->ldw;
+  g.dsrc = d->dsrc_kind ? d->dsrc : nullptr, g.dsrc_kind = d->dsrc_kind, g.dsrc_ld = d->dsrc_ld, g.dact = d->dact;
+  g.res = d->res, g.ldres = d->ldres, g.add = d->add, g.ldadd = d->ldadd;
+  g.out_f32 = d->out_f32, g.ldo32 = d->ldo32, g.out_pre = d->out_pre, g.out_act = d->out_act, g.ldo = d->ldo, g.act = d->act;
+  if (prec == DPPO_PREC_F32)
+    launch_gemm_nt<F32>(g, (hipStream_t)stream);
+  else
+    launch_gemm_nt<BF16>(g, (hipStream_t)stream);
+  return check_launch();
+}
+
+// 0 and t filled, or -1 with the reason in dppo_last_error()
+static int tn_job_checked(const dppo_gemm_tn_job& j, int es, GemmTN& t) {
+  if (!j.A || !j.B || !j.slab) return fail(-1, "null pointer");
+  if (j.M < 1 || j.M > 0x7fffffff || j.N1 < 1 || j.N2 < 1) return fail(-1, "bad argument: M / N1 / N2");
+  if (j.rows_per_split < 64 || j.rows_per_split % 64) return fail(-1, "rows_per_split must be a multiple of 64");
+  if (j.lda < 1 || j.ldb < 1 || (j.lda * es) % 16 || (j.ldb * es) % 16)
+    return fail(-1, "lda and ldb must be multiples of %d", 16 / es);
+  if (j.ncol_a < 0 || j.ncol_b < 0 || (j.ncol_a * es) % 16 || (j.ncol_b * es) % 16)
+    return fail(-1, "ncol_a and ncol_b must be multiples of %d", 16 / es);
+  if ((j.ncol_a > 0 ? j.ncol_a : j.lda) < j.N1 || (j.ncol_b > 0 ? j.ncol_b : j.ldb) < j.N2)
+    return fail(-1, "lda / ldb (ncol_a / ncol_b) smaller than N1 / N2");
+  memset(&t, 0, sizeof(t));
+  t.A = j.A, t.B = j.B, t.M = (int)j.M, t.N1 = j.N1, t.N2 = j.N2, t.lda = j.lda, t.ldb = j.ldb, t.slab = j.slab, t.ldc = j.N2;
+  t.rows_per_split = j.rows_per_split, t.splits = (int)((j.M + j.rows_per_split - 1) / j.rows_per_split);
+  t.ncol_a = j.ncol_a, t.ncol_b = j.ncol_b;
+  return 0;
+}
+
+int dppo_gemm_tn_group_raw(int prec, const dppo_gemm_tn_job* jobs, int n, float* const* C_out, dppo_stream_t stream) {
+  if (int e = check_prec(prec)) return e;
+  if (!jobs || !C_out) return fail(-1, "null pointer");
+  if (n < 1 || n > MAX_TN_JOBS) return fail(-1, "n must be 1..%d", MAX_TN_JOBS);
+  const int es = prec == DPPO_PREC_F32 ? 4 : 2;
+  GemmTNGroup gr;
+  memset(&gr, 0, sizeof(gr));
+  for (int i = 0; i < n; ++i) {
+    if (!C_out[i]) return fail(-1, "null pointer: C_out[%d]", i);
+    if (int e = tn_job_checked(jobs[i], es, gr.j[i])) return e;
+  }
+  gr.n = n;
+  gemm_tn_group_order(gr);
+  if (prec == DPPO_PREC_F32)
+    launch_gemm_tn_group<F32>(gr, (hipStream_t)stream);
+  else
+    launch_gemm_tn_group<BF16>(gr, (hipStream_t)stream);
+  for (int i = 0; i < n; ++i) {  // the caller's order: a job's slab does not move with the sort
+    const dppo_gemm_tn_job& j = jobs[i];
+    const int splits = (int)((j.M + j.rows_per_split - 1) / j.rows_per_split);
+    launch_slab_reduce_2d(j.slab, splits, j.N1, j.N2, j.N2, C_out[i], j.N2, 1.f, (hipStream_t)stream);
+  }
+  return check_launch();
+}
+
+int dppo_gemm_tn_job_raw(int prec, const dppo_gemm_tn_job* job, float* C, dppo_stream_t stream) {
+  if (int e = check_prec(prec)) return e;
+  if (!job || !C) return fail(-1, "null pointer");
+  GemmTN t;
+  if (int e = tn_job_checked(*job, prec == DPPO_PREC_F32 ? 4 : 2, t)) return e;
+  if (prec == DPPO_PREC_F32)
+    launch_gemm_tn<F32>(t, (hipStream_t)stream);
+  else
+    launch_gemm_tn<BF16>(t, (hipStream_t)stream);
+  launch_slab_reduce_2d(t.slab, t.splits, t.N1, t.N2, t.N2, C, t.N2, 1.f, (hipStream_t)stream);
   return check_launch();
 }

@@ -54,6 +54,9 @@ template <class P>
 void launch_gemm_nt(const GemmNT& a, hipStream_t s);
 template <class P>
 void launch_gemm_tn_group(const GemmTNGroup& gr, hipStream_t s);
+// Orders the n jobs of a group for launch_gemm_tn_group (longest row ranges first: the short jobs fill the last round) and
+// fills base[]
+void gemm_tn_group_order(GemmTNGroup& gr);
 void set_gemm_tn_variant(int v);  // tuning knob 5
 void set_gemm_tn_nbuf(int v);     // tuning knob 26
 void set_gemm_tn_thin(int v);     // tuning knob 6

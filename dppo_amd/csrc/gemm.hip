@@ -715,6 +715,18 @@ void launch_gemm_tn_group(const GemmTNGroup& gr, hipStream_t s) {
     hipLaunchKernelGGL((gemm_tn_group_kernel<P, 2>), grid, dim3(256), LDS, s, gr);
   if (probe) probe_end(s, flops, bytes);
 }
+void gemm_tn_group_order(GemmTNGroup& gr) {
+  for (int i = 1; i < gr.n; ++i)  // insertion sort (stable)
+    for (int k = i; k > 0 && gr.j[k].rows_per_split > gr.j[k - 1].rows_per_split; --k) {
+      const GemmTN t = gr.j[k];
+      gr.j[k] = gr.j[k - 1], gr.j[k - 1] = t;
+    }
+  gr.base[0] = 0;
+  for (int i = 0; i < gr.n; ++i) {
+    const int tiles = ((gr.j[i].N1 + 127) / 128) * ((gr.j[i].N2 + 127) / 128);
+    gr.base[i + 1] = gr.base[i] + gr.j[i].splits * tiles;
+  }
+}
 template void launch_gemm_tn_group<F32>(const GemmTNGroup&, hipStream_t);
 template void launch_gemm_tn_group<BF16>(const GemmTNGroup&, hipStream_t);
 

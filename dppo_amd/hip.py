@@ -84,6 +84,20 @@ class GmmCfg(C.Structure):  # struct dppo_gmm_cfg
                 ("seed_hi", C.c_uint32)]
 
 
+class GemmNTDesc(C.Structure):  # struct dppo_gemm_nt_desc (tests and tools only)
+    _fields_ = [("X", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("M", C.c_int64), ("N", C.c_int32),
+                ("Kp", C.c_int32), ("ldx", C.c_int32), ("ldw", C.c_int32), ("dsrc", C.c_void_p), ("dsrc_kind", C.c_int32),
+                ("dsrc_ld", C.c_int32), ("dact", C.c_int32), ("ldres", C.c_int32), ("res", C.c_void_p), ("add", C.c_void_p),
+                ("out_f32", C.c_void_p), ("out_pre", C.c_void_p), ("out_act", C.c_void_p), ("ldadd", C.c_int32),
+                ("ldo32", C.c_int32), ("ldo", C.c_int32), ("act", C.c_int32)]
+
+
+class GemmTNJob(C.Structure):  # struct dppo_gemm_tn_job (tests and tools only)
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("slab", C.c_void_p), ("M", C.c_int64), ("lda", C.c_int32),
+                ("N1", C.c_int32), ("ldb", C.c_int32), ("N2", C.c_int32), ("rows_per_split", C.c_int32),
+                ("ncol_a", C.c_int32), ("ncol_b", C.c_int32), ("pad", C.c_int32)]
+
+
 DP_HOOK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)  # void (*)(void* user, dppo_stream_t side)
 
 
@@ -194,6 +208,9 @@ SYMBOLS = {
     "dppo_tune_set": (_I, [_I, _I]),
     "dppo_gemm_nt_raw": (_I, [_I, _P, _P, _P, _L, _I, _I, _P, _P, _I, _I, _P]),
     "dppo_gemm_tn_raw": (_I, [_I, _P, _I, _I, _P, _I, _I, _L, _I, _P, _P, _P]),
+    "dppo_gemm_nt_desc_raw": (_I, [_I, C.POINTER(GemmNTDesc), _P]),
+    "dppo_gemm_tn_group_raw": (_I, [_I, C.POINTER(GemmTNJob), _I, C.POINTER(C.c_void_p), _P]),
+    "dppo_gemm_tn_job_raw": (_I, [_I, C.POINTER(GemmTNJob), _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

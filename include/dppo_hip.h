@@ -524,9 +524,49 @@ int dppo_tune_set(int knob, int value);
 int dppo_gemm_nt_raw(int prec, const void* X, const void* W, const float* bias, int64_t M, int N, int Kp,
                      float* out_f32, void* out_elem, int ldo, int act, dppo_stream_t stream);
 /* one bare weight-gradient GEMM: C[N1][N2] = A[M][N1]^T . B[M][N2] (elem operands, leading dims lda/ldb);
- * slab: scratch of at least splits*N1*N2 floats, splits = ceil(M / rows_per_split) */
+ * slab: scratch of at least splits*N1*N2 floats, splits = ceil(M / rows_per_split), rows_per_split a multiple of 64;
+ * lda >= N1, ldb >= N2, both a multiple of 16 bytes (4 fp32 / 8 bf16 elements) */
 int dppo_gemm_tn_raw(int prec, const void* A, int lda, int N1, const void* B, int ldb, int N2, int64_t M,
                      int rows_per_split, float* slab, float* C, dppo_stream_t stream);
+/* gemm_nt with every field of its epilogue (tests only): per output element, in this order,
+ *   v = X . W^T + bias;  v *= dact'(dsrc);  v += res + add;  out_f32 = v, out_pre = elem(v), out_act = elem(act(v)).
+ * X (M, ldx) and W (N, ldw) elem, Kp columns read; dsrc (M, dsrc_ld) fp32 (dsrc_kind 1) or elem (2), 0 = none; res (M, ldres)
+ * fp32 and add (M, ldadd) elem addends or NULL; out_f32 (M, ldo32), out_pre / out_act (M, ldo) or NULL.  act / dact: 0 ReLU,
+ * 1 Mish, 2 identity.  The kernel reads and writes round_up(N, 16) columns of every epilogue operand, so each leading
+ * dimension must be at least that (and a multiple of 4); ldx, ldw >= Kp and a multiple of 16 bytes. */
+typedef struct dppo_gemm_nt_desc {
+  const void* X;
+  const void* W;
+  const float* bias;
+  int64_t M;
+  int32_t N, Kp, ldx, ldw;
+  const void* dsrc;
+  int32_t dsrc_kind, dsrc_ld, dact, ldres;
+  const float* res;
+  const void* add;
+  float* out_f32;
+  void* out_pre;
+  void* out_act;
+  int32_t ldadd, ldo32, ldo, act;
+} dppo_gemm_nt_desc;
+int dppo_gemm_nt_desc_raw(int prec, const dppo_gemm_nt_desc* desc, dppo_stream_t stream);
+/* One weight-gradient product C[N1][N2] = A[M][N1]^T . B[M][N2] of a group (tests only).  slab: scratch of at least
+ * ceil(M / rows_per_split) * N1 * N2 floats; rows_per_split a multiple of 64; lda, ldb a multiple of 16 bytes.
+ * ncol_a / ncol_b (0 = none): the operand's rows OVERLAP -- N1 (N2) readable columns at a row stride lda (ldb) that may be
+ * smaller (an im2col window over a channel-last buffer); then ncol must be a multiple of 16 bytes and at least N1 (N2),
+ * otherwise lda >= N1 and ldb >= N2. */
+typedef struct dppo_gemm_tn_job {
+  const void* A;
+  const void* B;
+  float* slab;
+  int64_t M;
+  int32_t lda, N1, ldb, N2, rows_per_split, ncol_a, ncol_b, pad;
+} dppo_gemm_tn_job;
+/* n = 1..8 jobs through the grouped kernel exactly as a backward pass launches them (longest rows_per_split first, 128 x 128
+ * tiles, knob 26), then one slab reduction per job into C_out[i] (N1 x N2, dense), i in the caller's order. */
+int dppo_gemm_tn_group_raw(int prec, const dppo_gemm_tn_job* jobs, int n, float* const* C_out, dppo_stream_t stream);
+/* one job through the ungrouped dispatch (knobs 5 and 6; overlapping rows run on the register-staged 128 x 128 kernel) */
+int dppo_gemm_tn_job_raw(int prec, const dppo_gemm_tn_job* job, float* C, dppo_stream_t stream);
 
 /* ---- 8f row 4 (second half): mixture-of-Gaussians policy PPO ---------------------------------------------------------
  * Replaces model/common/mlp_gmm.py:11-110 (GMM_MLP.forward: component means tanh(mlp_mean(s)) (B, modes, Ta*Da), fixed or

@@ -179,3 +179,64 @@ def test_new_entry_points_reject_bad_descriptors_with_a_message():
     assert lib.dppo_gmm_logprob(C.byref(wide), C.byref(wts), hip.PREC_BF16, None, None, None, None, C.byref(cfg), None, None, None,
                                 4, None, None, 0, None) == -1
     assert b"out_dim" in lib.dppo_last_error()
+
+
+def test_gemm_test_entries_validate_their_arguments_on_the_host():
+    """dppo_gemm_nt_desc_raw / dppo_gemm_tn_group_raw / dppo_gemm_tn_job_raw / dppo_gemm_tn_raw refuse a bad call with -1
+    and a message before anything is launched (the pointers below are never dereferenced: no GPU here)."""
+    lib = hip.load()
+    p = 0x1000  # non-null, never read
+    err = lib.dppo_last_error
+
+    def nt(**kw):
+        f = dict(X=p, W=p, bias=None, M=100, N=40, Kp=64, ldx=64, ldw=64, dsrc=None, dsrc_kind=0, dsrc_ld=0, dact=0, ldres=0,
+                 res=None, add=None, out_f32=p, out_pre=None, out_act=None, ldadd=0, ldo32=48, ldo=0, act=0)
+        f.update(kw)
+        return C.byref(hip.GemmNTDesc(**f))
+    B16 = hip.PREC_BF16
+    assert lib.dppo_gemm_nt_desc_raw(B16, None, None) == -1 and b"null" in err()
+    for kw, word in ((dict(X=None), b"null"), (dict(W=None), b"null"), (dict(out_f32=None), b"null"), (dict(M=0), b"M"),
+                     (dict(N=0), b"N"), (dict(Kp=72, ldx=72, ldw=72), b"Kp"), (dict(Kp=0), b"Kp"), (dict(ldx=56), b"ldx"),
+                     (dict(ldx=68), b"ldx"), (dict(ldw=70), b"ldw"), (dict(ldw=32), b"ldw"), (dict(ldo32=40), b"ldo32"),
+                     (dict(ldo32=50), b"ldo32"), (dict(out_pre=p, ldo=47), b"ldo"), (dict(out_act=p, ldo=0), b"ldo"),
+                     (dict(dsrc_kind=3), b"dsrc_kind"), (dict(dsrc_kind=1), b"dsrc"), (dict(dsrc_kind=2, dsrc=p, dsrc_ld=44), b"dsrc_ld"),
+                     (dict(res=p, ldres=40), b"ldres"), (dict(add=p, ldadd=16), b"ldadd"), (dict(act=3), b"act"),
+                     (dict(dact=-1), b"act")):
+        assert lib.dppo_gemm_nt_desc_raw(B16, nt(**kw), None) == -1, kw
+        assert word in err(), (kw, err())
+    assert lib.dppo_gemm_nt_desc_raw(7, nt(), None) == -1
+    assert lib.dppo_gemm_nt_desc_raw(hip.PREC_F32, nt(Kp=48, ldx=48, ldw=48), None) == -1 and b"Kp" in err()  # fp32: 32 per k-tile
+    assert lib.dppo_gemm_nt_desc_raw(hip.PREC_F32, nt(ldx=66), None) == -1 and b"ldx" in err()                # fp32: 4 per 16 bytes
+
+    def job(**kw):
+        f = dict(A=p, B=p, slab=p, M=1000, lda=512, N1=512, ldb=64, N2=40, rows_per_split=256, ncol_a=0, ncol_b=0, pad=0)
+        f.update(kw)
+        return hip.GemmTNJob(**f)
+    out = (C.c_void_p * 9)(*([p] * 9))
+    bad_jobs = ((dict(A=None), b"null"), (dict(B=None), b"null"), (dict(slab=None), b"null"), (dict(M=0), b"M"),
+                (dict(N1=0), b"N1"), (dict(rows_per_split=100), b"rows_per_split"), (dict(rows_per_split=0), b"rows_per_split"),
+                (dict(lda=516), b"lda"), (dict(ldb=60), b"ldb"), (dict(lda=504), b"lda"), (dict(ldb=32), b"ldb"),
+                (dict(ncol_a=500), b"ncol_a"), (dict(lda=64, ncol_a=256), b"ncol_a"), (dict(ldb=8, ncol_b=24), b"ncol_b"))
+    for kw, word in bad_jobs:
+        assert lib.dppo_gemm_tn_job_raw(B16, C.byref(job(**kw)), p, None) == -1, kw
+        assert word in err(), (kw, err())
+        jobs = (hip.GemmTNJob * 2)(job(), job(**kw))  # the second job of a group is checked like the first
+        assert lib.dppo_gemm_tn_group_raw(B16, jobs, 2, out, None) == -1, kw
+        assert word in err(), (kw, err())
+    assert lib.dppo_gemm_tn_job_raw(B16, None, p, None) == -1 and b"null" in err()
+    assert lib.dppo_gemm_tn_job_raw(B16, C.byref(job()), None, None) == -1 and b"null" in err()
+    jobs = (hip.GemmTNJob * 9)(*[job() for _ in range(9)])
+    for n in (0, -1, 9):
+        assert lib.dppo_gemm_tn_group_raw(B16, jobs, n, out, None) == -1 and b"1..8" in err()
+    assert lib.dppo_gemm_tn_group_raw(B16, None, 1, out, None) == -1 and b"null" in err()
+    assert lib.dppo_gemm_tn_group_raw(B16, jobs, 1, None, None) == -1 and b"null" in err()
+    out[1] = None
+    assert lib.dppo_gemm_tn_group_raw(B16, jobs, 2, out, None) == -1 and b"C_out[1]" in err()
+    assert lib.dppo_gemm_tn_group_raw(7, jobs, 1, out, None) == -1
+    assert lib.dppo_gemm_tn_job_raw(hip.PREC_F32, C.byref(job(lda=514)), p, None) == -1 and b"lda" in err()  # fp32: multiples of 4
+    # dppo_gemm_tn_raw: the same leading-dimension rules
+    for lda, ldb in ((504, 64), (512, 32), (516, 64), (512, 60)):
+        assert lib.dppo_gemm_tn_raw(B16, p, lda, 512, p, ldb, 40, 1000, 256, p, p, None) == -1, (lda, ldb)
+        assert b"lda" in err()
+    assert lib.dppo_gemm_tn_raw(B16, p, 512, 512, p, 64, 40, 1000, 100, p, p, None) == -1 and b"rows_per_split" in err()
+    assert lib.dppo_gemm_tn_raw(B16, None, 512, 512, p, 64, 40, 1000, 256, p, p, None) == -1

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Micro-benchmark + correctness check of the bare MFMA GEMMs (dppo_gemm_nt_raw / dppo_gemm_tn_raw) at the PPO
 update's shapes.  Variants are timed interleaved in ONE process on random data (cdna_hip_programming.md rule 24/25).
+Every result is ASSERTED against a float64 reference of the same (rounded) operands: per element
+|got - ref| <= 2 L 2^-24 (|A|^T |B|) + one rounding of the stored type, L the contraction length (the worst-case
+summation bound of tests/test_gemm_primitives.py).
 
     python tools/gemm_bench.py [--M 50000] [--rounds 5]
 """
@@ -26,6 +29,18 @@ def time_ms(fn, iters):
     return s.elapsed_time(e) / iters
 
 
+def bound(absA, absB, ref, L, out_eps):
+    """absA (L, n1), absB (L, n2) float64 magnitudes of the operands, ref (n1, n2) float64."""
+    return 2.0 * L * 2.0 ** -24 * (absA.t() @ absB) + out_eps * ref.abs()
+
+
+def check(got, ref, bnd, what):
+    err = (got.double() - ref).abs()
+    worst = (err / bnd.clamp_min(1e-300)).max().item()
+    assert worst <= 1.0, f"{what}: max |err| {err.max().item():.3e} is {worst:.2f} x the summation bound"
+    return err.max().item()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--M", type=int, default=50000)
@@ -48,7 +63,9 @@ def main():
             b = torch.randn(N, device=dev)
             out = torch.empty(M, N, device=dev)
             oe = torch.empty(M, N, device=dev, dtype=dt)
-            ref = X.float() @ W.float().t() + b
+            ref = X.double() @ W.double().t() + b.double()
+            bnd = bound(X.double().abs().t(), W.double().abs().t(), ref, K, 2.0 ** -24) + 2.0 ** -24 * b.double().abs()
+            bnd_e = bnd + (2.0 ** -24 if dt == torch.float32 else 2.0 ** -8) * (ref.abs() + bnd)  # + rounding to elem
 
             def run():
                 hip.check(lib.dppo_gemm_nt_raw(prec, X.data_ptr(), W.data_ptr(), b.data_ptr(), M, N, K, out.data_ptr(),
@@ -58,8 +75,9 @@ def main():
                 lib.dppo_tune_set(0, variant)
                 run()
                 torch.cuda.synchronize()
-                err = (out - ref).abs().max().item()
-                err_e = (oe.float() - torch.relu(ref)).abs().max().item()
+                what = f"gemm_nt {name} M={M} N={N} K={K} staging={'dma' if variant else 'reg'}"
+                err = check(out, ref, bnd, what + " f32-out")
+                err_e = check(oe, torch.relu(ref), bnd_e, what + " elem-out")
                 res[variant] = [err, err_e, []]
             for _ in range(args.rounds):
                 for variant in (0, 1):
@@ -80,7 +98,8 @@ def main():
             splits = (M + rps - 1) // rps
             slab = torch.empty(splits * N1 * N2, device=dev)
             Cc = torch.empty(N1, N2, device=dev)
-            ref = A.float().t() @ B.float()
+            ref = A.double().t() @ B.double()
+            bnd = bound(A.double().abs(), B.double().abs(), ref, M, 2.0 ** -24)
 
             def run_tn():
                 hip.check(lib.dppo_gemm_tn_raw(prec, A.data_ptr(), N1, N1, B.data_ptr(), N2, N2, M, rps, slab.data_ptr(),
@@ -93,7 +112,8 @@ def main():
                 Cc.zero_()
                 run_tn()
                 torch.cuda.synchronize()
-                err = ((Cc - ref).abs().max() / ref.abs().max()).item()
+                check(Cc, ref, bnd, f"gemm_tn {name} M={M} N1={N1} N2={N2} {names[variant]}")
+                err = ((Cc.double() - ref).abs().max() / ref.abs().max()).item()
                 ts = sorted(time_ms(run_tn, args.iters) for _ in range(args.rounds))
                 tf = 2.0 * M * N1 * N2 / (ts[len(ts) // 2] * 1e-3) / 1e12
                 print(f"gemm_tn {name} M={M} N1={N1} N2={N2} splits={splits} {names[variant]:26s}: median "
