@@ -2435,7 +2435,8 @@ static int unet_ppo_entry(const dppo_unet_desc* actor, const dppo_net_desc* crit
   if ((inds == nullptr) == (kinds == nullptr)) return fail(-1, "pass exactly one of inds (rollout mode) / kinds (gathered mode)");
   if (N < 2 || N > (1 << 24)) return fail(-1, "N out of range");
   if (pcfg->ft_denoising_steps < 1 || pcfg->ft_denoising_steps > 1024) return fail(-1, "Kft out of range");
-  if ((size_t)pcfg->ft_denoising_steps * 9 * actor->time_dim * 4 > 64 * 1024) return fail(-1, "Kft * time_dim too large (LDS of the time MLP's backward)");
+  if ((int64_t)pcfg->ft_denoising_steps * actor->time_dim > 16384)  // (its LDS tables go in chunks of steps: no limit from them)
+    return fail(-1, "Kft * time_dim above 16384 (the per-step gradient table of the time MLP's backward)");
   if (pcfg->horizon_steps != actor->horizon_steps || pcfg->action_dim != actor->action_dim) return fail(-1, "Ta / Da mismatch");
   if (pcfg->reward_horizon < 1) return fail(-1, "reward_horizon must be >= 1");
 #define CALL(P)                                                                                                          \
@@ -2510,7 +2511,8 @@ static int unet_mse_entry(const dppo_unet_desc* net, int prec, const float* para
   if (int e = check_prec(prec)) return e;
   if (!params || !packed || !tsteps || !obs || !pairs || !kinds || !grad || !loss || !workspace) return fail(-1, "null pointer");
   if (N < 1 || N > (1 << 24) || n_time < 1 || n_time > 1024) return fail(-1, "N / n_time out of range");
-  if ((size_t)n_time * 9 * net->time_dim * 4 > 64 * 1024) return fail(-1, "n_time * time_dim too large (LDS of the time MLP's backward)");
+  if ((int64_t)n_time * net->time_dim > 16384)  // (its LDS tables go in chunks of steps: no limit from them)
+    return fail(-1, "n_time * time_dim above 16384 (the per-step gradient table of the time MLP's backward)");
 #define CALL(P)                                                                                                          \
   unet_mse_impl<P>(*net, params, (const char*)packed, tsteps, n_time, obs, pairs, kinds, N, grad, loss, workspace, workspace_bytes, \
                    (hipStream_t)stream, d_obs)

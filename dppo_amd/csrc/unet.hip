@@ -166,6 +166,8 @@ int check_desc(const dppo_unet_desc* d) {
   if (d->dim < 8 || d->dim % 8) return api_fail(-1, "unet: dim must be a positive multiple of 8");
   for (int i = 0; i < d->n_levels; ++i)
     if (d->mults[i] < 1 || d->dim * d->mults[i] > 1024) return api_fail(-1, "unet: channel count out of range");
+  if (d->mults[0] != 1)
+    return api_fail(-1, "unet: dim_mults[0] must be 1 (final_conv reads `dim` channels from a map of dim * dim_mults[0])");
   if (d->kernel_size != 3 && d->kernel_size != 5) return api_fail(-1, "unet: kernel_size must be 3 or 5");
   if (d->n_groups < 1 || d->n_groups > 32) return api_fail(-1, "unet: n_groups out of [1,32]");
   for (int i = 0; i < d->n_levels; ++i)
@@ -382,6 +384,7 @@ struct GnArgs {
   int ldr;
   const void* resi;  // image [rows][Tp][ldri]
   int ldri;
+  int rsplit;        // > 0: resi is a concat image [x (rsplit, padded) | skip]: real channel c sits at chan_pos(c, rsplit)
   void* dst;         // image [rows][T + 2 PAD][ldd], written at channel offset coff; pad rows (all ldd channels) zeroed
   int ldd, coff, zero_pads;
   void* dst2;        // optional second destination (the skip connection's half of a concat image)
@@ -428,7 +431,7 @@ __global__ __launch_bounds__(256) void unet_gn_kernel(const GnArgs a) {
       if (a.res == 1)
         v = v + a.resf[((size_t)b * a.Tps + t) * a.ldr + c];
       else if (a.res == 2)
-        v = v + P::to_f32(((const E*)a.resi)[((size_t)b * Tp + t + PAD) * a.ldri + c]);
+        v = v + P::to_f32(((const E*)a.resi)[((size_t)b * Tp + t + PAD) * a.ldri + chan_pos(c, a.rsplit)]);
     }
     dst[(size_t)(t + PAD) * a.ldd + a.coff + c] = P::from_f32(v);
     if (dst2) dst2[(size_t)(t + PAD) * a.ldd2 + a.coff2 + c] = P::from_f32(v);
@@ -671,7 +674,7 @@ struct Runner {
       gemm(in, PAD, 1, pk + r.res.pk, r.co, r.res.Kp, prm + r.res.b, W.res, ldc);
       a.res = 1, a.resf = W.res, a.ldr = ldc;
     } else {
-      a.res = 2, a.resi = in.p, a.ldri = in.C;
+      a.res = 2, a.resi = in.p, a.ldri = in.C, a.rsplit = r.c1.split;
     }
     a.dst = out_img, a.ldd = ldd, a.coff = coff, a.zero_pads = zero_pads;
     a.dst2 = dst2, a.ldd2 = ldd2, a.coff2 = coff2, a.zero_pads2 = zero2;
@@ -1019,53 +1022,60 @@ __global__ __launch_bounds__(256) void unet_temb_segsum_kernel(const float* dg, 
     __syncthreads();
   }
 }
-// backward of time_mlp (Linear(d, 4d) -> Mish -> Linear(4d, d)) from G[k][d] = d loss / d temb[t_k]; one block
+// backward of time_mlp (Linear(d, 4d) -> Mish -> Linear(4d, d)) from G[k][d] = d loss / d temb[t_k]; one block.  The steps go
+// through LDS in chunks of KC (all of them at once wherever Kft * 9 * time_dim floats fit: then the sums below are the plain
+// sums over k); a later chunk adds to what the earlier ones wrote -- each output element belongs to one thread throughout
 __global__ __launch_bounds__(256) void unet_time_bwd_kernel(const float* w1, const float* b1, const float* w2, const float* G,
-                                                            const dppo_step* ksteps, int Kft, int td, float* gw1, float* gb1,
-                                                            float* gw2, float* gb2) {
-  extern __shared__ float sh[];  // per k: e0[td], z1[4td], dz1[4td]
+                                                            const dppo_step* ksteps, int Kft, int KC, int td, float* gw1,
+                                                            float* gb1, float* gw2, float* gb2) {
+  extern __shared__ float sh[];  // per k of a chunk: e0[td], z1[4td], dz1[4td]
   const int H = 4 * td, per = td + 2 * H, tid = threadIdx.x;
-  for (int k = 0; k < Kft; ++k) {
-    float* e0 = sh + k * per;
-    for (int j = tid; j < td; j += 256) e0[j] = sinus(ksteps[k].t, j, td);
-  }
-  __syncthreads();
-  for (int i = tid; i < Kft * H; i += 256) {
-    const int k = i / H, o = i % H;
-    const float* e0 = sh + k * per;
-    float s = b1[o];
-    for (int j = 0; j < td; ++j) s += w1[o * td + j] * e0[j];
-    sh[k * per + td + o] = s;
-  }
-  __syncthreads();
-  for (int i = tid; i < Kft * H; i += 256) {  // dz1 = (W2^T G[k]) * mish'(z1)
-    const int k = i / H, o = i % H;
-    float s = 0.f;
-    for (int j = 0; j < td; ++j) s += w2[j * H + o] * G[k * td + j];
-    sh[k * per + td + H + o] = s * mish_grad_f(sh[k * per + td + o]);
-  }
-  __syncthreads();
-  for (int i = tid; i < td * H; i += 256) {  // gw2[j][o] = sum_k G[k][j] mish(z1[k][o])
-    const int j = i / H, o = i % H;
-    float s = 0.f;
-    for (int k = 0; k < Kft; ++k) s += G[k * td + j] * mish_f(sh[k * per + td + o]);
-    gw2[i] = s;
-  }
-  for (int j = tid; j < td; j += 256) {
-    float s = 0.f;
-    for (int k = 0; k < Kft; ++k) s += G[k * td + j];
-    gb2[j] = s;
-  }
-  for (int i = tid; i < H * td; i += 256) {  // gw1[o][j] = sum_k dz1[k][o] e0[k][j]
-    const int o = i / td, j = i % td;
-    float s = 0.f;
-    for (int k = 0; k < Kft; ++k) s += sh[k * per + td + H + o] * sh[k * per + j];
-    gw1[i] = s;
-  }
-  for (int o = tid; o < H; o += 256) {
-    float s = 0.f;
-    for (int k = 0; k < Kft; ++k) s += sh[k * per + td + H + o];
-    gb1[o] = s;
+  for (int k0 = 0; k0 < Kft; k0 += KC) {
+    const int kn = Kft - k0 < KC ? Kft - k0 : KC;
+    const float* Gc = G + (size_t)k0 * td;
+    if (k0 > 0) __syncthreads();  // the previous chunk's sums have read the tables
+    for (int k = 0; k < kn; ++k) {
+      float* e0 = sh + k * per;
+      for (int j = tid; j < td; j += 256) e0[j] = sinus(ksteps[k0 + k].t, j, td);
+    }
+    __syncthreads();
+    for (int i = tid; i < kn * H; i += 256) {
+      const int k = i / H, o = i % H;
+      const float* e0 = sh + k * per;
+      float s = b1[o];
+      for (int j = 0; j < td; ++j) s += w1[o * td + j] * e0[j];
+      sh[k * per + td + o] = s;
+    }
+    __syncthreads();
+    for (int i = tid; i < kn * H; i += 256) {  // dz1 = (W2^T G[k]) * mish'(z1)
+      const int k = i / H, o = i % H;
+      float s = 0.f;
+      for (int j = 0; j < td; ++j) s += w2[j * H + o] * Gc[k * td + j];
+      sh[k * per + td + H + o] = s * mish_grad_f(sh[k * per + td + o]);
+    }
+    __syncthreads();
+    for (int i = tid; i < td * H; i += 256) {  // gw2[j][o] = sum_k G[k][j] mish(z1[k][o])
+      const int j = i / H, o = i % H;
+      float s = 0.f;
+      for (int k = 0; k < kn; ++k) s += Gc[k * td + j] * mish_f(sh[k * per + td + o]);
+      gw2[i] = k0 > 0 ? gw2[i] + s : s;
+    }
+    for (int j = tid; j < td; j += 256) {
+      float s = 0.f;
+      for (int k = 0; k < kn; ++k) s += Gc[k * td + j];
+      gb2[j] = k0 > 0 ? gb2[j] + s : s;
+    }
+    for (int i = tid; i < H * td; i += 256) {  // gw1[o][j] = sum_k dz1[k][o] e0[k][j]
+      const int o = i / td, j = i % td;
+      float s = 0.f;
+      for (int k = 0; k < kn; ++k) s += sh[k * per + td + H + o] * sh[k * per + j];
+      gw1[i] = k0 > 0 ? gw1[i] + s : s;
+    }
+    for (int o = tid; o < H; o += 256) {
+      float s = 0.f;
+      for (int k = 0; k < kn; ++k) s += sh[k * per + td + H + o];
+      gb1[o] = k0 > 0 ? gb1[o] + s : s;
+    }
   }
 }
 
@@ -1228,7 +1238,7 @@ struct UnetTrainer {
       conv_gemm(in, PAD, 1, pk + r.res.pk, r.co, r.res.Kp, prm + r.res.b, tmpA, ldc);
       a.res = 1, a.resf = tmpA, a.ldr = ldc;
     } else {
-      a.res = 2, a.resi = in.p, a.ldri = in.C;
+      a.res = 2, a.resi = in.p, a.ldri = in.C, a.rsplit = r.c1.split;
     }
     a.dst = out, a.ldd = ldd, a.coff = coff, a.zero_pads = zero_pads, a.dst2 = dst2, a.ldd2 = ldd2, a.coff2 = coff2;
     a.zero_pads2 = zero2;
@@ -1424,7 +1434,9 @@ struct UnetTrainer {
         conv_gemm(dYi, PAD, 1, pk + r.res.pkT, r.ci, Cw, nullptr, gin, ldi);
         conv_gemm(dU1i, PAD - r.c1.ks / 2, 1, pk + r.c1.pkT, r.ci, r.c1.ks * Cw, nullptr, gin, ldi, gin, ldi);
       } else {
-        // identity skip: gin = conv1 data gradient + sum(up).  The GEMM's f32 addend takes one source; a second is added first
+        // identity skip: gin = conv1 data gradient + sum(up).  The GEMM's f32 addend takes one source; a second is added first.
+        // (gin is in REAL channel order -- pack_conv_bwd_kernel -- also when the input is a concat image, so the skip's
+        // gradient adds channel for channel: no chan_pos here, unlike the forward's read from the image)
         if (n_up == 1 && up[0].coff == 0 && up[0].Tp == Tp) {
           conv_gemm(dU1i, PAD - r.c1.ks / 2, 1, pk + r.c1.pkT, r.ci, r.c1.ks * Cw, nullptr, gin, ldi, up[0].p, up[0].ld);
         } else {
@@ -1589,9 +1601,10 @@ struct UnetTrainer {
         hipLaunchKernelGGL(unet_copy_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dgacc, dg_ld(), d.time_dim,
                            d.cond_dim, rows, dobs_out);
       }
-      const size_t lds = (size_t)io.Kft * (d.time_dim + 8 * d.time_dim) * 4;
-      hipLaunchKernelGGL(unet_time_bwd_kernel, dim3(1), dim3(256), lds, s, prm + L.t1.w, prm + L.t1.b, prm + L.t2.w, Gk, io.ksteps,
-                         io.Kft, d.time_dim, grad + L.t1.w, grad + L.t1.b, grad + L.t2.w, grad + L.t2.b);
+      const size_t per_k = (size_t)9 * d.time_dim * 4;  // 64 KiB of LDS hold at least 14 steps (time_dim <= 128)
+      const int KC = (int)(65536 / per_k) < io.Kft ? (int)(65536 / per_k) : io.Kft;
+      hipLaunchKernelGGL(unet_time_bwd_kernel, dim3(1), dim3(256), KC * per_k, s, prm + L.t1.w, prm + L.t1.b, prm + L.t2.w, Gk,
+                         io.ksteps, io.Kft, KC, d.time_dim, grad + L.t1.w, grad + L.t1.b, grad + L.t2.w, grad + L.t2.b);
     }
   }
 
@@ -1603,6 +1616,8 @@ struct UnetTrainer {
     tmpA = new_f32(tmp_floats), tmpB = new_f32(tmp_floats), tmpC = new_f32((size_t)rows * 2 * cmax);
     imgA = take(tmp_floats * P::ESIZE), imgB = take(tmp_floats * P::ESIZE);
     size_t wmax = (size_t)2 * cmax * 5 * 2 * cmax;  // largest packed weight: first up block's conv1 (2C -> C, 5 taps) etc.
+    // ... or an encoder's first linear, [cc <= 2 cmax][time_dim + cond_dim]: the larger one where cond_dim is some ten times the width
+    if ((size_t)2 * cmax * L.Kg > wmax) wmax = (size_t)2 * cmax * L.Kg;
     dwp = new_f32(wmax);
     slab_floats = wmax * 8;
     slab = new_f32(slab_floats);

@@ -355,7 +355,7 @@ typedef struct dppo_unet_desc {
   int32_t action_dim, cond_dim, horizon_steps;
   int32_t time_dim;           /* diffusion_step_embed_dim                                        */
   int32_t dim, n_levels;      /* channels of level i = dim * mults[i]                              */
-  int32_t mults[4];
+  int32_t mults[4];           /* mults[0] must be 1: final_conv is Conv1dBlock(dim, dim)           */
   int32_t kernel_size, n_groups;
   int32_t larger_encoder;     /* cond_mlp_dims is None and not smaller_encoder (unet.py:151)       */
   int32_t cond_predict_scale;

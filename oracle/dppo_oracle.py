@@ -821,7 +821,7 @@ def unet_forward(p: Params, spec: UnetSpec, x: torch.Tensor, t: torch.Tensor, st
     B = x.shape[0]
     h = x.transpose(1, 2)  # channels = action dims, length = chunk steps
     d = spec.diffusion_step_embed_dim
-    emb = sinusoidal(t, d)
+    emb = sinusoidal(t, d).to(p["time_mlp.1.weight"].dtype)  # (float64 parameters: the high-precision reference of the tests)
     g = F.linear(mish(F.linear(emb, p["time_mlp.1.weight"], p["time_mlp.1.bias"])), p["time_mlp.3.weight"],
                  p["time_mlp.3.bias"])
     g = torch.cat([g, state.reshape(B, -1)], dim=-1)

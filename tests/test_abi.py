@@ -181,6 +181,32 @@ def test_new_entry_points_reject_bad_descriptors_with_a_message():
     assert b"out_dim" in lib.dppo_last_error()
 
 
+def test_unet_descriptors_are_rejected_with_a_message():
+    """check_desc of the conv denoiser: a network the reference cannot run is refused by name, not run over the wrong width."""
+    lib = hip.load()
+
+    def desc(mults=(1, 2), **kw):
+        f = dict(action_dim=7, cond_dim=23, horizon_steps=4, time_dim=16, dim=64, n_levels=len(mults),
+                 mults=(C.c_int32 * 4)(*(list(mults) + [0] * (4 - len(mults)))), kernel_size=5, n_groups=8, larger_encoder=1,
+                 cond_predict_scale=1, act=hip.ACT_MISH, groupnorm_eps=1e-5)
+        f.update(kw)
+        return C.byref(hip.UnetDesc(**f))
+    assert lib.dppo_unet_param_count(desc()) > 0
+    assert lib.dppo_unet_param_count(desc(mults=(1, 2, 1))) > 0  # decreasing multipliers are the reference's to run
+    # final_conv is Conv1dBlock(dim, dim) on a map of dim * dim_mults[0] channels: the reference raises unless dim_mults[0] == 1
+    for mults in ((3,), (2, 4), (2, 1)):
+        for call in (lambda d: lib.dppo_unet_param_count(d), lambda d: lib.dppo_unet_packed_bytes(d, hip.PREC_BF16, 20),
+                     lambda d: lib.dppo_unet_workspace_bytes(d, hip.PREC_F32, 4)):
+            assert call(desc(mults=mults)) == -1, mults
+            assert b"final_conv" in lib.dppo_last_error() and b"dim_mults[0]" in lib.dppo_last_error(), lib.dppo_last_error()
+    for kw, word in ((dict(mults=(1, 2, 4, 8, 16)[:4], n_levels=5), b"n_levels"), (dict(dim=36), b"dim"), (dict(n_groups=33), b"n_groups"),
+                     (dict(n_groups=7), b"n_groups"), (dict(horizon_steps=6, mults=(1, 2, 4)), b"horizon_steps"),
+                     (dict(horizon_steps=65), b"horizon_steps"), (dict(action_dim=65), b"action_dim"), (dict(time_dim=130), b"time_dim"),
+                     (dict(cond_dim=1025), b"cond_dim"), (dict(kernel_size=4), b"kernel_size"), (dict(mults=(1, 17)), b"channel")):
+        assert lib.dppo_unet_param_count(desc(**kw)) == -1, kw
+        assert word in lib.dppo_last_error(), (kw, lib.dppo_last_error())
+
+
 def test_gemm_test_entries_validate_their_arguments_on_the_host():
     """dppo_gemm_nt_desc_raw / dppo_gemm_tn_group_raw / dppo_gemm_tn_job_raw / dppo_gemm_tn_raw refuse a bad call with -1
     and a message before anything is launched (the pointers below are never dereferenced: no GPU here)."""
