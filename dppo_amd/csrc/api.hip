@@ -10,6 +10,7 @@
 #include "ppo.h"
 #include "gaussian.h"
 #include "gmm.h"
+#include "idql.h"
 #include "unet.h"
 #include "sampler.h"
 
@@ -431,6 +432,10 @@ static void carve_mlp(Carver& c, const dppo_net_desc& d, int64_t M, bool keep, b
     if (keep || b == 0) {
       a1s = c.take((size_t)M * H * ES);
       a2s = c.take((size_t)M * H * ES);
+    } else if (d.plain) {
+      // a plain layer reads a2[b - 1] and writes a2[b]: two buffers in turn, never one GEMM in place (its workgroups would read
+      // rows that the others' column tiles are overwriting)
+      a2s = b == 1 ? c.take((size_t)M * H * ES) : B.a2[b - 2];
     }
     B.a1[b] = a1s;
     B.a2[b] = a2s;
@@ -2533,6 +2538,244 @@ int dppo_unet_denoise_mse_fwd_bwd_obs(const dppo_unet_desc* net, int prec, const
   if (!d_obs) return fail(-1, "null pointer");
   return unet_mse_entry(net, prec, params, packed, tsteps, n_time, obs, pairs, kinds, N, grad, loss, workspace, workspace_bytes,
                         stream, d_obs);
+}
+
+// ---- IDQL (idql.hip): twin-Q critics, expectile V, best-of-N selection, Polyak target -----------------------------------------
+static int check_idql_q(const dppo_net_desc* q) {
+  if (int e = check_net(q)) return e;
+  if (q->kind != 1 || q->out_dim != 1) return fail(-1, "a Q trunk is a kind-1 descriptor with out_dim 1");
+  return 0;
+}
+static int check_idql_pair(const dppo_net_desc* q, const dppo_net_desc* v) {
+  if (int e = check_idql_q(q)) return e;
+  if (int e = check_net(v)) return e;
+  if (v->kind != 1 || v->out_dim != 1) return fail(-1, "the V critic is a kind-1 descriptor with out_dim 1");
+  if (q->in_dim <= v->cond_dim)
+    return fail(-1, "Q / V descriptors do not pair: Q in_dim=%d must be V cond_dim=%d + the action width", q->in_dim, v->cond_dim);
+  return 0;
+}
+static int check_idql_batch(const dppo_idql_batch* b, int64_t N, bool need_next) {
+  if (!b) return fail(-1, "null batch");
+  if (!b->obs || !b->actions || (need_next && (!b->next_obs || !b->reward || !b->terminated))) return fail(-1, "null pointer in batch");
+  if (b->cap < 1 || b->n_envs < 1 || b->count < 1 || b->count > b->cap || b->head < 0 || b->head >= b->cap)
+    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
+  if (!b->inds && N > b->count * b->n_envs) return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N,
+                                                         (long long)(b->count * b->n_envs));
+  return 0;
+}
+template <class P>
+struct IdqlWs {
+  MlpBufs<P> Q1, Q2, V;
+  double* partial;
+  float *r, *term;
+};
+// train_q: the Q trunks keep their activations and get backward buffers (Q loss); otherwise V does (V loss)
+template <class P>
+static size_t carve_idql(Carver& c, const dppo_net_desc& q, const dppo_net_desc* v, int64_t N, bool twin, bool train_q, bool train_v,
+                         IdqlWs<P>& W) {
+  W.partial = (double*)c.take((size_t)idql_blocks(N) * 4 * sizeof(double));
+  W.r = (float*)c.take((size_t)N * 4);
+  W.term = (float*)c.take((size_t)N * 4);
+  carve_mlp<P>(c, q, N, train_q, train_q, W.Q1);
+  if (twin) carve_mlp<P>(c, q, N, train_q, train_q, W.Q2);
+  if (v) carve_mlp<P>(c, *v, N, train_v, train_v, W.V);
+  return al256(c.off);
+}
+static int64_t idql_ws_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int prec, int64_t N, int double_q, bool train_q,
+                             bool train_v) {
+  if ((v ? check_idql_pair(q, v) : check_idql_q(q)) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  Carver c{nullptr, 0, 0};
+  if (prec == DPPO_PREC_F32) {
+    IdqlWs<F32> W;
+    return (int64_t)carve_idql<F32>(c, *q, v, N, double_q != 0, train_q, train_v, W);
+  }
+  IdqlWs<BF16> W;
+  return (int64_t)carve_idql<BF16>(c, *q, v, N, double_q != 0, train_q, train_v, W);
+}
+int64_t dppo_idql_v_loss_workspace_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int prec, int64_t N, int double_q) {
+  return idql_ws_bytes(q, v, prec, N, double_q, false, true);
+}
+int64_t dppo_idql_q_loss_workspace_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int prec, int64_t N, int double_q) {
+  return idql_ws_bytes(q, v, prec, N, double_q, true, false);
+}
+int64_t dppo_idql_q_forward_workspace_bytes(const dppo_net_desc* q, int prec, int64_t N, int double_q) {
+  return idql_ws_bytes(q, nullptr, prec, N, double_q, false, false);
+}
+static IdqlRows idql_rows_of(const dppo_idql_batch& b, int64_t N, int OD, int AD) {
+  IdqlRows r;
+  memset(&r, 0, sizeof(r));
+  r.obs = b.obs, r.next_obs = b.next_obs, r.actions = b.actions, r.reward = b.reward, r.terminated = b.terminated, r.inds = b.inds;
+  r.cap = b.cap, r.E = b.n_envs, r.head = b.head, r.count = b.count, r.N = N, r.OD = OD, r.AD = AD;
+  return r;
+}
+template <class P>
+static int idql_v_impl(const dppo_net_desc& q, const dppo_net_desc& v, const float* tp, const char* tk1, const char* tk2,
+                       const float* vp, const char* vk, const dppo_idql_batch& b, int64_t N, double tau, bool twin, float* vgrad,
+                       float* adv, double* stats, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  IdqlWs<P> W;
+  const size_t need = carve_idql<P>(c, q, &v, N, twin, false, true, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout LQ = pack_layout<P>(q, 0), LV = pack_layout<P>(v, 0);
+  IdqlRows r = idql_rows_of(b, N, v.cond_dim, q.in_dim - v.cond_dim);
+  r.q1in = W.Q1.in, r.q2in = twin ? W.Q2.in : nullptr, r.vin = W.V.in, r.KpQ = LQ.Kp0, r.KpV = LV.Kp0;
+  launch_idql_rows<P>(r, s);
+  // the two target trunks on side streams beside V's forward; the loss reads all three outputs
+  hipStream_t s1 = fork_side(s, 0);
+  mlp_forward<P>(q, tp, tk1, LQ, N, W.Q1, false, s1);
+  hipStream_t s2 = s;
+  if (twin) {
+    s2 = fork_side(s, 2);
+    mlp_forward<P>(q, tp + param_layout(q).total, tk2, LQ, N, W.Q2, false, s2);
+  }
+  mlp_forward<P>(v, vp, vk, LV, N, W.V, true, s);
+  if (s1 != s) join_side(s, s1, 0);
+  if (s2 != s) join_side(s, s2, 2);
+  IdqlLoss l;
+  memset(&l, 0, sizeof(l));
+  l.q1 = W.Q1.out, l.q2 = twin ? W.Q2.out : nullptr, l.ldq = W.Q1.ldout, l.v = W.V.out, l.ldv = W.V.ldout, l.N = N;
+  l.tau = (float)tau, l.d_a = W.V.d_out, l.ldd = LV.Kpo, l.adv_out = adv, l.partial = W.partial, l.stats = stats;
+  launch_idql_v_loss<P>(l, s);
+  mlp_backward<P>(v, vp, vk, LV, N, W.V, vgrad, nullptr, nullptr, 0, s, false, 1);
+  return check_launch();
+}
+int dppo_idql_v_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int prec, const float* target_q_params,
+                             const void* target_q1_packed, const void* target_q2_packed, const float* v_params,
+                             const void* v_packed, const dppo_idql_batch* batch, int64_t N, double expectile, int double_q,
+                             float* v_grad, float* adv_out, double* stats, void* workspace, int64_t workspace_bytes,
+                             dppo_stream_t stream) {
+  if (int e = check_idql_pair(q, v)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!target_q_params || !target_q1_packed || (double_q && !target_q2_packed) || !v_params || !v_packed || !v_grad || !stats ||
+      !workspace)
+    return fail(-1, "null pointer");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_idql_batch(batch, N, false)) return e;
+  if (!(expectile >= 0.0 && expectile <= 1.0)) return fail(-1, "expectile tau=%g outside [0, 1]", expectile);
+#define CALL(P)                                                                                                                \
+  idql_v_impl<P>(*q, *v, target_q_params, (const char*)target_q1_packed, (const char*)target_q2_packed, v_params,              \
+                 (const char*)v_packed, *batch, N, expectile, double_q != 0, v_grad, adv_out, stats, workspace, workspace_bytes, \
+                 (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+template <class P>
+static int idql_q_impl(const dppo_net_desc& q, const dppo_net_desc& v, const float* qp, const char* qk1, const char* qk2,
+                       const float* vp, const char* vk, const dppo_idql_batch& b, int64_t N, double gamma, bool twin, float* qgrad,
+                       double* stats, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  IdqlWs<P> W;
+  const size_t need = carve_idql<P>(c, q, &v, N, twin, true, false, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout LQ = pack_layout<P>(q, 0), LV = pack_layout<P>(v, 0);
+  const int64_t nq = param_layout(q).total;
+  IdqlRows r = idql_rows_of(b, N, v.cond_dim, q.in_dim - v.cond_dim);
+  r.q1in = W.Q1.in, r.q2in = twin ? W.Q2.in : nullptr, r.nvin = W.V.in, r.KpQ = LQ.Kp0, r.KpV = LV.Kp0;
+  r.r_out = W.r, r.term_out = W.term;
+  launch_idql_rows<P>(r, s);
+  // Q2 on side stream 0 and V(next_obs) on side stream 2 beside Q1; one join before the loss, one after the backward
+  hipStream_t s2 = twin ? fork_side(s, 0) : s;
+  if (twin) mlp_forward<P>(q, qp + nq, qk2, LQ, N, W.Q2, true, s2);
+  hipStream_t s3 = fork_side(s, 2);
+  mlp_forward<P>(v, vp, vk, LV, N, W.V, false, s3);
+  mlp_forward<P>(q, qp, qk1, LQ, N, W.Q1, true, s);
+  if (s2 != s) join_side(s, s2, 0);
+  if (s3 != s) join_side(s, s3, 2);
+  IdqlLoss l;
+  memset(&l, 0, sizeof(l));
+  l.q1 = W.Q1.out, l.q2 = twin ? W.Q2.out : nullptr, l.ldq = W.Q1.ldout, l.v = W.V.out, l.ldv = W.V.ldout, l.N = N;
+  l.reward = W.r, l.terminated = W.term, l.gamma = (float)gamma, l.d_a = W.Q1.d_out, l.d_b = twin ? W.Q2.d_out : nullptr;
+  l.ldd = LQ.Kpo, l.partial = W.partial, l.stats = stats;
+  launch_idql_q_loss<P>(l, s);
+  if (twin) {
+    s2 = fork_side(s, 0);
+    mlp_backward<P>(q, qp + nq, qk2, LQ, N, W.Q2, qgrad + nq, nullptr, nullptr, 0, s2, false, -1);
+  }
+  mlp_backward<P>(q, qp, qk1, LQ, N, W.Q1, qgrad, nullptr, nullptr, 0, s, false, 1);
+  if (s2 != s) join_side(s, s2, 0);
+  return check_launch();
+}
+int dppo_idql_q_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int prec, const float* q_params,
+                             const void* q1_packed, const void* q2_packed, const float* v_params, const void* v_packed,
+                             const dppo_idql_batch* batch, int64_t N, double gamma, int double_q, float* q_grad, double* stats,
+                             void* workspace, int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_idql_pair(q, v)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!q_params || !q1_packed || (double_q && !q2_packed) || !v_params || !v_packed || !q_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
+#define CALL(P)                                                                                                                  \
+  idql_q_impl<P>(*q, *v, q_params, (const char*)q1_packed, (const char*)q2_packed, v_params, (const char*)v_packed, *batch, N, gamma, \
+                 double_q != 0, q_grad, stats, workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+template <class P>
+static int idql_fwd_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const float* obs, int OD,
+                         int64_t obs_rows, const float* actions, int64_t N, bool twin, float* q1o, float* q2o, void* ws,
+                         int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  IdqlWs<P> W;
+  const size_t need = carve_idql<P>(c, q, nullptr, N, twin, false, false, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout LQ = pack_layout<P>(q, 0);
+  IdqlRows r;
+  memset(&r, 0, sizeof(r));
+  r.obs = obs, r.actions = actions, r.obs_mod = obs_rows, r.N = N, r.OD = OD, r.AD = q.in_dim - OD;
+  r.q1in = W.Q1.in, r.q2in = twin ? W.Q2.in : nullptr, r.KpQ = LQ.Kp0;
+  launch_idql_rows<P>(r, s);
+  hipStream_t s2 = twin ? fork_side(s, 0) : s;
+  if (twin) {
+    mlp_forward<P>(q, qp + param_layout(q).total, qk2, LQ, N, W.Q2, false, s2);
+    launch_copy_cols(W.Q2.out, W.Q2.ldout, 0, 1, N, q2o, s2);
+  }
+  mlp_forward<P>(q, qp, qk1, LQ, N, W.Q1, false, s);
+  launch_copy_cols(W.Q1.out, W.Q1.ldout, 0, 1, N, q1o, s);
+  if (s2 != s) join_side(s, s2, 0);
+  return check_launch();
+}
+int dppo_idql_q_forward(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                        const float* obs, int obs_dim, int64_t obs_rows, const float* actions, int64_t N, int double_q,
+                        float* q1_out, float* q2_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_idql_q(q)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!q_params || !q1_packed || !obs || !actions || !q1_out || !workspace || (double_q && (!q2_packed || !q2_out)))
+    return fail(-1, "null pointer");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (obs_rows < 1 || obs_rows > N) return fail(-1, "obs_rows out of [1, N]");
+  if (obs_dim < 1 || obs_dim >= q->in_dim)
+    return fail(-1, "Q descriptor does not pair with obs_dim=%d: in_dim=%d must be obs_dim + the action width", obs_dim, q->in_dim);
+#define CALL(P)                                                                                                                  \
+  idql_fwd_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, obs, obs_dim, obs_rows, actions, N, double_q != 0, \
+                   q1_out, q2_out, workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+int dppo_idql_select(const float* q1, const float* q2, const float* v, int v_per_env, const float* candidates, const float* u,
+                     int64_t B, int S, int width, int mode, double h, uint64_t seed, float* actions, int32_t* idx,
+                     dppo_stream_t stream) {
+  if (!q1 || !candidates || !actions) return fail(-1, "null pointer");
+  if (mode != 0 && mode != 1) return fail(-1, "mode must be 0 (argmax) or 1 (expectile exploration)");
+  if (mode == 1 && !v) return fail(-1, "mode 1 needs v");
+  if (B < 1 || S < 1 || width < 1 || B * (int64_t)S > 0x7fffffff) return fail(-1, "B, S, width out of range");
+  if (!(h >= 0.0 && h <= 1.0)) return fail(-1, "critic_hyperparam tau=%g outside [0, 1]", h);
+  IdqlSelect a;
+  memset(&a, 0, sizeof(a));
+  a.q1 = q1, a.q2 = q2, a.v = v, a.cand = candidates, a.u = u, a.B = B, a.S = S, a.AF = width, a.mode = mode;
+  a.v_per_env = v_per_env ? 1 : 0, a.h = (float)h, a.seed_lo = (uint32_t)seed, a.seed_hi = (uint32_t)(seed >> 32);
+  a.actions = actions, a.idx = idx;
+  launch_idql_select(a, (hipStream_t)stream);
+  return check_launch();
+}
+int dppo_polyak(float* target, const float* source, double tau, int64_t n, dppo_stream_t stream) {
+  if (!target || !source) return fail(-1, "null pointer");
+  if (n < 1) return fail(-1, "n out of range");
+  if (!(tau >= 0.0 && tau <= 1.0)) return fail(-1, "tau=%g outside [0, 1]", tau);
+  launch_polyak(target, source, (float)(1.0 - tau), (float)tau, n, (hipStream_t)stream);
+  return check_launch();
 }
 
 // ---- optimiser ----------------------------------------------------------------------------------------

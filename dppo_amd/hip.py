@@ -98,6 +98,14 @@ class GemmTNJob(C.Structure):  # struct dppo_gemm_tn_job (tests and tools only)
                 ("ncol_a", C.c_int32), ("ncol_b", C.c_int32), ("pad", C.c_int32)]
 
 
+class IdqlBatch(C.Structure):  # struct dppo_idql_batch
+    _fields_ = [("obs", C.c_void_p), ("next_obs", C.c_void_p), ("actions", C.c_void_p), ("reward", C.c_void_p),
+                ("terminated", C.c_void_p), ("inds", C.c_void_p), ("cap", C.c_int64), ("n_envs", C.c_int64),
+                ("head", C.c_int64), ("count", C.c_int64)]
+
+
+IDQL_STAT_COUNT = 3
+
 DP_HOOK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)  # void (*)(void* user, dppo_stream_t side)
 
 
@@ -164,6 +172,15 @@ SYMBOLS = {
     "dppo_gmm_bc_workspace_bytes": (_L, [_ND, _ND, _I, _L]),
     "dppo_gmm_bc_loss_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(GmmCfg), _P, _P, _P, _L, _P, _P, _P, _P, _P, _L,
                                       _P]),
+    # IDQL: twin-Q / expectile-V losses over the device replay ring, best-of-N selection, Polyak target (csrc/idql.hip)
+    "dppo_idql_v_loss_workspace_bytes": (_L, [_ND, _ND, _I, _L, _I]),
+    "dppo_idql_v_loss_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, _P, C.POINTER(IdqlBatch), _L, _D, _I, _P, _P, _P, _P, _L, _P]),
+    "dppo_idql_q_loss_workspace_bytes": (_L, [_ND, _ND, _I, _L, _I]),
+    "dppo_idql_q_loss_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, _P, C.POINTER(IdqlBatch), _L, _D, _I, _P, _P, _P, _L, _P]),
+    "dppo_idql_q_forward_workspace_bytes": (_L, [_ND, _I, _L, _I]),
+    "dppo_idql_q_forward": (_I, [_ND, _I, _P, _P, _P, _P, _I, _L, _P, _L, _I, _P, _P, _P, _L, _P]),
+    "dppo_idql_select": (_I, [_P, _P, _P, _I, _P, _P, _L, _I, _I, _I, _D, C.c_uint64, _P, _P, _P]),
+    "dppo_polyak": (_I, [_P, _P, _D, _L, _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

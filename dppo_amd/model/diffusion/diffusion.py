@@ -286,6 +286,9 @@ class DiffusionModel(nn.Module):
         t ~ U{0..K-1} per sample).  ``noise`` / ``t`` optionally replace the internal draws (parity tests)."""
         if t is None:
             t = torch.randint(0, self.denoising_steps, (len(x),), device=x.device).long()
+            # drawn here, so t < denoising_steps: p_losses' range guard (a device read of t.max(), i.e. a host
+            # synchronisation per minibatch) can only fire when denoising_steps itself is above its limit
+            return self.p_losses(x, cond, t, noise=noise, t_checked=self.denoising_steps <= 1024)
         return self.p_losses(x, cond, t, noise=noise)
 
     def q_sample(self, x_start, t, noise=None):
@@ -309,14 +312,14 @@ class DiffusionModel(nn.Module):
             cache[key] = torch.from_numpy(tab.view(np.uint8)).to(device)
         return cache[key]
 
-    def p_losses(self, x_start, cond, t, noise=None):
+    def p_losses(self, x_start, cond, t, noise=None, t_checked=False):
         """mse(eps_theta(x_t, t, cond), eps) with the gradient of every network parameter computed by the same kernels
         as the PPO update (row builder -> fused forward -> loss -> fused backward -> grouped weight-gradient GEMM); the
         returned scalar carries them into ``.backward()`` (reference ``p_losses`` :325-349)."""
         import ctypes as C
         state = cond["state"]
         hip.require_gpu(state, "DiffusionModel.p_losses")
-        if t.numel() and int(t.max()) >= 1024:
+        if not t_checked and t.numel() and int(t.max()) >= 1024:  # (t_checked: ``loss`` drew t itself, below the limit)
             raise NotImplementedError("dppo_amd: supervised loss supports denoising_steps <= 1024")
         N, dev = len(x_start), x_start.device
         if noise is None:

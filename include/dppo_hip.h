@@ -702,6 +702,65 @@ int dppo_vis_encode(const dppo_vis_desc* net, int prec, const float* params, con
 int dppo_vis_backward(const dppo_vis_desc* net, int prec, const float* params, const void* packed, const float* d_obs,
                       int ld_dobs, int64_t B, float* grad, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
 
+/* ---- IDQL: implicit diffusion Q-learning (off-policy fine-tuning of the diffusion policy) ------------------------------
+ * Replaces model/diffusion/diffusion_idql.py:42-95, 125-188 (IDQLDiffusion.loss_critic_v / loss_critic_q /
+ * update_target_critic / forward) and model/common/critic.py:57-113 (CriticObsAct).  The actor's loss is the plain
+ * denoising MSE (dppo_denoise_mse_fwd_bwd) and its sampler the plain K-step chain (dppo_sample_chain).
+ * A Q trunk is a kind-1 descriptor with in_dim = cond_dim = To*Do + Ta*Da whose rows are [obs | action]; V is the
+ * state-value critic on To*Do.  The two trunks of a twin critic share one descriptor and one flat fp32 image [Q1 | Q2]
+ * (Q2 at float offset dppo_net_param_count(q)); each has its own packed image.  double_q = 0: Q1 only, the *q2* arguments
+ * are ignored.  The twin trunks run side by side on the library's side streams.
+ *
+ * Minibatches are gathered from a device-resident replay ring: obs, next_obs (cap, n_envs, To*Do), actions
+ * (cap, n_envs, Ta*Da), reward, terminated (cap, n_envs), of which `count` steps are stored, the oldest in slot `head`.
+ * Row n of a minibatch is the transition with logical index inds[n] (inds == NULL: n) in "s e -> (s e)" order over the stored
+ * steps, oldest first: step s sits in slot (head + s) % cap.  Indices are clamped into [0, count * n_envs).  Plain (N, .)
+ * arrays are the ring with cap = count = N, n_envs = 1, head = 0. */
+typedef struct dppo_idql_batch {
+  const float* obs;
+  const float* next_obs;
+  const float* actions;
+  const float* reward;
+  const float* terminated;
+  const int64_t* inds; /* (N,) device, or NULL                                                   */
+  int64_t cap, n_envs, head, count;
+} dppo_idql_batch;
+#define DPPO_IDQL_STAT_COUNT 3
+/* adv = min(q1, q2) - v with the TARGET twin (no gradient) and V on obs; loss = mean(where(adv > 0, expectile, 1 - expectile)
+ * * adv^2).  v_grad <- d loss / d V params (flat, OVERWRITTEN); adv_out (N,) optional; stats[3] <- {loss, mean adv,
+ * share of adv > 0} (device doubles; per-block partials in double, summed in block order: two calls are bit-identical). */
+int64_t dppo_idql_v_loss_workspace_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int prec, int64_t N, int double_q);
+int dppo_idql_v_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int prec, const float* target_q_params,
+                             const void* target_q1_packed, const void* target_q2_packed, const float* v_params,
+                             const void* v_packed, const dppo_idql_batch* batch, int64_t N, double expectile, int double_q,
+                             float* v_grad, float* adv_out, double* stats, void* workspace, int64_t workspace_bytes,
+                             dppo_stream_t stream);
+/* target = reward + gamma * V(next_obs) * (1 - terminated) in fp32 (gamma rounded to fp32 once, V without gradient);
+ * loss = mean((q1 - target)^2) + mean((q2 - target)^2).  q_grad <- d loss / d [Q1 | Q2] params (flat, OVERWRITTEN);
+ * stats[3] <- {loss, mean q1, mean target}. */
+int64_t dppo_idql_q_loss_workspace_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int prec, int64_t N, int double_q);
+int dppo_idql_q_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int prec, const float* q_params,
+                             const void* q1_packed, const void* q2_packed, const float* v_params, const void* v_packed,
+                             const dppo_idql_batch* batch, int64_t N, double gamma, int double_q, float* q_grad, double* stats,
+                             void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
+/* q1_out, q2_out (N,) <- Q1, Q2 on rows [obs[n % obs_rows] | actions[n]]: obs (obs_rows, obs_dim), actions
+ * (N, in_dim - obs_dim).  The S*B candidate rows of best-of-N sampling share their B observations this way. */
+int64_t dppo_idql_q_forward_workspace_bytes(const dppo_net_desc* q, int prec, int64_t N, int double_q);
+int dppo_idql_q_forward(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                        const float* obs, int obs_dim, int64_t obs_rows, const float* actions, int64_t N, int double_q,
+                        float* q1_out, float* q2_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
+/* Best-of-N action selection.  q1, q2 (S*B,) sample-major (row s*B + b; q2 may be NULL); v (S*B,), or (B,) with
+ * v_per_env != 0 (mode 1 only); candidates (S*B, width).  mode 0: argmax over s of min(q1, q2), the first index on ties.
+ * mode 1: s drawn with probability w_s / sum w, w_s = (min(q1, q2) - v > 0 ? h : 1 - h), by inverse CDF in index order in
+ * fp32 from the uniform u[b] (u == NULL: Philox4x32-10 keyed by seed, counter b).  actions (B, width), idx (B,) int32
+ * (may be NULL). */
+int dppo_idql_select(const float* q1, const float* q2, const float* v, int v_per_env, const float* candidates, const float* u,
+                     int64_t B, int S, int width, int mode, double h, uint64_t seed, float* actions, int32_t* idx,
+                     dppo_stream_t stream);
+/* target <- target * (float)(1 - tau) + source * (float)tau: two fp32 products and one fp32 sum per element, no fma
+ * (update_target_critic's rounding).  16-byte accesses where both pointers are 16-byte aligned. */
+int dppo_polyak(float* target, const float* source, double tau, int64_t n, dppo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
