@@ -104,7 +104,7 @@ struct PackLayout {  // byte offsets into the packed image
 };
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 // Width of a network's input rows x (and of the row-major first-layer operand): in_dim padded to 64 -- and, for a denoiser,
-// with at least 24 spare columns behind in_dim: the one-hot of the row's denoising step lives there (temb_onehot_col), and
+// with at least 24 spare columns behind in_dim: the one-hot of the row's denoising step lives there (plan_route()), and
 // without room for it the time-embedding gradient costs a gemm_nt over all rows, a segmented sum and two more launches
 // (halfcheetah: in_dim 57, 7 spare of 64: +40 us per update until the rows became 128 wide).
 static int row_kp0(const dppo_net_desc& d) {
@@ -354,6 +354,25 @@ struct Carver {
     return p;
   }
 };
+// a *_workspace_bytes export: carve(c, P{}) runs one of the carve_* functions against a null base, in the call's precision
+template <class F>
+static int64_t ws_bytes(int prec, F carve) {
+  Carver c{nullptr, 0, 0};
+  return (int64_t)(prec == DPPO_PREC_F32 ? carve(c, F32{}) : carve(c, BF16{}));
+}
+
+// Which kernels one network's fused backward launches, and on which streams: decided once per network per call (its shape step
+// at the head of carve_mlp, plan_route() right behind the carve) and only READ from there on -- by carve_mlp, the row builders' callers,
+// mlp_forward and the backward's stages.  dppo_backward_route() exports it: every field is described at its DPPO_ROUTE_* bit
+// in include/dppo_hip.h.
+struct BwdRoute {
+  bool fused, one_block, lowrank, merged;
+  int onehot_col;  // column of the input rows where the one-hot of the row's denoising step starts, -1 = none
+  bool dw0;
+  int dw0_nhot;  // one-hot columns among the 32 of the in-kernel dW0
+  bool dw0_round, need_aux, side_tail, tail_post, post_one;
+  bool aux_side;  // (not exported) need_aux's pass runs on side stream TAIL_SIDE: the caller has one
+};
 
 template <class P>
 struct MlpBufs {  // activations of one network for M rows
@@ -389,7 +408,7 @@ struct MlpBufs {  // activations of one network for M rows
   size_t slab_used;   // floats handed out since the last flush
   SlabJobs slab_jobs; // reductions pending on the pool (flush_slabs)
   GemmTNGroup tn_group;  // weight-gradient GEMMs pending on the pool: launched together by flush_slabs
-  bool dw0;         // set by the caller between carve and the backward (dw0_ok()): the backward keeps dW0 on chip, dh_0 is never stored
+  BwdRoute route;
   // side streams to join into the flushing stream right behind the GEMM launch: the barrier packets (~10 us each even when
   // the event fired long ago) are then processed while the GEMMs run instead of at the end of the call
   hipStream_t join_s[2];
@@ -397,8 +416,6 @@ struct MlpBufs {  // activations of one network for M rows
   float* part;  // column-sum / segment-sum partials
   float* lowrank;  // [out_dim][H] T = d_out^T . act(z1) of the top block (see lowrank_dw_kernel)
   float* lowrank_u;  // [out_dim][Kp0] U = d_out^T . x (merged-top networks: dWout is rebuilt from U and T, see PostReduce)
-  bool merged;       // this network's forward ran merged (fused_can_merge): h_nb was never stored
-  bool post_zeroed;      // the caller's row builder zeroed post_counter and tail_counter in this call
   double* post_counter;  // 8 zeroed bytes: arrival counter of post_reduce_kernel (zeroed by the row builder, left zero)
   unsigned* tail_counter;  // the 8 bytes right behind it (zeroed with it): arrival counter of tail_post_kernel's thin reductions
   size_t slab_floats, part_floats;
@@ -408,11 +425,8 @@ constexpr int REDUCE_BLOCKS = 256;
 constexpr int POST_COUNTER_DOUBLES = 2;  // post_counter and tail_counter: one row-builder zero array
 
 static bool lowrank_top(const dppo_net_desc& d, int64_t M);
-// the one-block backward kernel writes no dh_nb tensor: it needs the low-rank dW2
 template <class P>
-static bool bwd_one(const dppo_net_desc& d, int64_t M) {
-  return fused_bwd_one_block<P>(d) && d.out_dim <= 128 && lowrank_top(d, M);
-}
+static int plan_route(const dppo_net_desc& d, int64_t M, int Kft, int flags, MlpBufs<P>& B);
 
 static int g_dbg = 0;  // tuning knob 8: timing experiments on the fused kernels (results are wrong while it is set)
 template <class P>
@@ -421,6 +435,13 @@ static void carve_mlp(Carver& c, const dppo_net_desc& d, int64_t M, bool keep, b
   const int H = d.hidden, nb = d.n_blocks;
   const int Kp0 = row_kp0(d), Kpo = round_up(d.out_dim, 64);
   memset(&B, 0, sizeof(B));
+  // The route's shape step: what (network, rows, knobs) alone decide.  The per-tile column sums below are sized by it; the rest
+  // (plan_route) needs what this carve produces.
+  BwdRoute& R = B.route;
+  R.onehot_col = -1, R.lowrank = lowrank_top(d, M);
+  R.one_block = fused_bwd_one_block<P>(d) && d.out_dim <= 128 && R.lowrank;  // (its kernel writes no dh_nb: it needs the low-rank dW2)
+  R.merged = fused_ok<P>(d) && fused_can_merge<P>(d);
+  R.fused = fused_ok<P>(d) && M > 0 && fused_rows_per_tile<P>(d, R.one_block) > 0;
   B.in = c.take((size_t)M * Kp0 * ES);
   const int nh = keep ? nb + 1 : (nb > 0 ? 2 : 1);
   float* hbuf[MAX_BLOCKS + 1];
@@ -465,7 +486,7 @@ static void carve_mlp(Carver& c, const dppo_net_desc& d, int64_t M, bool keep, b
       B.dh_all[b] = c.take((size_t)M * H * ES);
       B.dz1_all[b] = b == 0 ? B.dz1 : c.take((size_t)M * H * ES);
     }
-    const int mt = d.plain || d.out_dim > 128 ? 0 : fused_rows_per_tile<P>(d, bwd_one<P>(d, M));
+    const int mt = d.plain || d.out_dim > 128 ? 0 : fused_rows_per_tile<P>(d, R.one_block);
     B.tiles = mt > 0 ? (int)((M + mt - 1) / mt) : 0;
     B.tile_colsum = (float*)c.take((size_t)(2 * nb + 2 + (d.use_layernorm ? 4 * nb : 0)) * (B.tiles > 0 ? B.tiles : 1) * H * 4);
     const int tdp = round_up(d.time_dim > 0 ? d.time_dim : 1, 16);
@@ -484,9 +505,11 @@ static void carve_mlp(Carver& c, const dppo_net_desc& d, int64_t M, bool keep, b
     B.lowrank_u = (float*)c.take((size_t)round_up(d.out_dim, 16) * Kp0 * 4);
     B.post_counter = (double*)c.take(POST_COUNTER_DOUBLES * 8);
     B.tail_counter = (unsigned*)(B.post_counter + 1);
-    B.post_zeroed = false;
     B.w0T = c.take((size_t)round_up(d.cond_dim > 0 ? d.cond_dim : 1, 16) * H * ES);
     B.dobs = (float*)c.take((size_t)M * round_up(d.cond_dim > 0 ? d.cond_dim : 1, 16) * 4);
+    // the route of a caller that has nothing to add (no denoising steps, no zeroed counters, no side stream); the entry points
+    // that do (BC, denoise-MSE, PPO) plan again with their own inputs before they build their rows
+    plan_route<P>(d, M, 0, 0, B);
   }
 }
 
@@ -543,8 +566,7 @@ static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk
       f.hpre[nb] = B.hE;
       f.ln_stats = d.use_layernorm ? B.ln_stats : nullptr;
     }
-    B.merged = fused_can_merge<P>(d);
-    if (B.merged) {  // the block's second layer folded into the out layer: h_nb is never formed (fused_forward_merged_kernel)
+    if (B.route.merged) {  // the block's second layer folded into the out layer: h_nb is never formed (fused_forward_merged_kernel)
       f.merge_top = 1, f.ks0v = (d.in_dim + P::KB - 1) / P::KB, f.hpre[nb] = nullptr;
       if (g_dbg & 64) f.hpre[0] = nullptr;   // timing experiments: the forward does not store act'(h_0) ...
       if (g_dbg & 128) f.a2[0] = nullptr;    // ... / act(z1)
@@ -667,13 +689,6 @@ constexpr int64_t MOM_RIDER_MAX_N = 16384;
 // the K padding of the input rows, dW0's extra columns are S[h][k] = sum over the rows of step k of dh0[row][h], and
 // d loss / d temb[k] = W0[:, temb columns]^T S[:, k] -- no second pass over dh0, no segmented reduction (tuning knob 11).
 static int g_temb_onehot = 1;
-template <class P>
-static int temb_onehot_col(const dppo_net_desc& d, const PackLayout& L, int Kft, const MlpBufs<P>& B) {
-  if (!g_temb_onehot || d.kind != 0 || !fused_ok<P>(d) || Kft < 1) return -1;
-  if (d.cond_out > 0 && d.cond_out % 16) return -1;  // the encoder's epilogue zero-fills up to a multiple of 16 columns
-  if (L.Kp0 - d.in_dim < Kft || (size_t)(d.hidden + d.time_dim) * Kft > B.part_floats) return -1;
-  return d.in_dim;
-}
 // In-kernel first-layer weight gradient (tuning knob 37; fused.h, FusedBwdArgs::dw0_slab).  dh_0 -- a third of the bytes the
 // weight-gradient GEMMs read, for a 512 x 64 output -- is then neither stored nor read back: the one-block backward multiplies each
 // tile of it with the tile's input rows while both are on chip and keeps the partial product in LDS.  The 64 KB that has room for
@@ -681,9 +696,7 @@ static int temb_onehot_col(const dppo_net_desc& d, const PackLayout& L, int Kft,
 // the temb columns are a function of k alone (their gradient is rebuilt from the one-hot sums, PostReduce::dW0t; the kernel
 // skips them when it reads the row tile: act_flat and time_dim must be multiples of 4), and of the Kft one-hot columns the last
 // may be left out (every row carries exactly one: PostReduce::S_rest, with the bias gradient taken of the rounded dh_0) --
-// hopper: 12 + 11 + 9 = 32.
-// Needs the one-block backward on its compact walk, the one-hot time columns, post_reduce in one launch, nobody asking for
-// d loss / d observation, no cond_mlp, and a slab per workgroup in the pool.
+// hopper: 12 + 11 + 9 = 32.  (What else it needs: plan_route().)
 static int g_dw0 = 1;
 // Tuning knob 38: with the in-kernel dW0 everything the time-embedding gradient needs -- the one-hot sums, the first layer's bias
 // gradient, then G = W0_temb^T . S and the time MLP's backward (a chain of dependent steps: 11 of post_reduce's 16 us) -- comes out
@@ -695,23 +708,40 @@ static int g_side_tail = 1;
 // which read only the two THIN products -- is ONE launch (tail_post_kernel: the thin products' reduce blocks first, the dependent
 // blocks poll their arrival, the big slabs are reduced beside them) instead of two.
 static int g_tail_post = 1;
-static int dw0_cols(const dppo_net_desc& d) { return d.kind == 0 ? d.act_flat + d.cond_dim : d.in_dim; }
-static int dw0_nhot(const dppo_net_desc& d, int Kft) {  // one-hot columns that fit behind the data columns
-  const int room = 32 - dw0_cols(d);
-  return d.kind != 0 ? 0 : (room >= Kft ? Kft : room);
-}
+// The rest of the route: what needs the carve (tiles, part_floats, slab_floats), the denoising steps and the caller.  flags
+// (DPPO_ROUTE_IN_*): the caller's row builder zeroes post_counter and tail_counter in this call; somebody asks for
+// d loss / d observation; the tail may use side stream TAIL_SIDE.  Runs before the rows are built: they carry the one-hot columns.
 template <class P>
-static bool dw0_ok(const dppo_net_desc& d, int64_t M, const PackLayout& L, int Kft, const MlpBufs<P>& B, bool wants_dobs) {
-  if (!g_dw0 || P::ESIZE != 2 || wants_dobs || d.cond_hidden > 0 || !g_tn_group || !g_post_one) return false;
-  if (!fused_ok<P>(d) || B.tiles <= 0 || !bwd_one<P>(d, M) || !fused_dw0_shape(d) || L.Kp0 < 64) return false;
-  if (d.kind == 0) {
-    if (temb_onehot_col<P>(d, L, Kft, B) < 0 || !B.post_zeroed || d.in_dim != d.act_flat + d.time_dim + d.cond_dim) return false;
-    if (d.act_flat % 4 || d.time_dim % 4 || 32 + d.time_dim > 64) return false;
-    if (dw0_nhot(d, Kft) < Kft - 1) return false;
-  } else if (d.in_dim > 32) {
-    return false;
-  }
-  return (size_t)fused_bwd_one_grid<P>(d, M) * d.hidden * 32 <= B.slab_floats / 2;
+static int plan_route(const dppo_net_desc& d, int64_t M, int Kft, int flags, MlpBufs<P>& B) {
+  BwdRoute& R = B.route;
+  const bool zeroed = flags & DPPO_ROUTE_IN_ZEROED, wants_dobs = flags & DPPO_ROUTE_IN_DOBS;
+  const int Kp0 = row_kp0(d);
+  const bool side = flags & DPPO_ROUTE_IN_SIDE;
+  // (the encoder's epilogue zero-fills up to a multiple of 16 columns; S[H][Kft] and G[td][Kft] live in B.part)
+  const bool oh = g_temb_onehot && d.kind == 0 && fused_ok<P>(d) && Kft >= 1 && !(d.cond_out > 0 && d.cond_out % 16) &&
+                  Kp0 - d.in_dim >= Kft && (size_t)(d.hidden + d.time_dim) * Kft <= B.part_floats;
+  R.onehot_col = oh ? d.in_dim : -1;
+  const int room = 32 - (d.kind == 0 ? d.act_flat + d.cond_dim : d.in_dim);  // one-hot columns that fit behind the data columns
+  const int nhot = d.kind != 0 ? 0 : (room >= Kft ? Kft : room);
+  R.dw0 = g_dw0 && P::ESIZE == 2 && zeroed && !wants_dobs && d.cond_hidden <= 0 && g_tn_group && g_post_one && R.fused &&
+          R.one_block && fused_dw0_shape(d) && Kp0 >= 64 &&
+          (size_t)fused_bwd_one_grid<P>(d, M) * d.hidden * 32 <= B.slab_floats / 2;  // a slab per workgroup in the pool
+  if (d.kind == 0)
+    R.dw0 = R.dw0 && oh && d.in_dim == d.act_flat + d.time_dim + d.cond_dim && d.act_flat % 4 == 0 && d.time_dim % 4 == 0 &&
+            32 + d.time_dim <= 64 && nhot >= Kft - 1;
+  else
+    R.dw0 = R.dw0 && d.in_dim <= 32;
+  if (R.dw0 && (g_dbg & 33))
+    return fail(-1, "tuning knob 8, bits 0 and 5 (values 1 and 32: no dh_0 store) cannot run with the in-kernel dW0: set knob 37 to 0 first");
+  R.dw0_nhot = R.dw0 ? nhot : 0;
+  R.dw0_round = R.dw0 && d.kind == 0 && nhot < Kft;  // (the last one-hot column is rebuilt from the bias gradient)
+  R.need_aux = d.kind == 0 && !oh;
+  R.aux_side = R.need_aux && side;
+  R.side_tail = R.dw0 && d.kind == 0 && side && g_side_tail && g_early_join && zeroed && !(g_dbg & 28);
+  R.tail_post = R.side_tail && g_tail_post;  // (dw0 implies the one-block backward: there is always a post-reduce part)
+  // its arrival counter (zeroed by the row builder) is only needed by the time-embedding part
+  R.post_one = g_post_one && (!oh || zeroed) && (R.lowrank || oh || R.merged || R.one_block);
+  return 0;
 }
 template <class P>
 static void flush_slabs(MlpBufs<P>& B, hipStream_t s, const SlotOuts* slots = nullptr, int slot_width = 0,
@@ -844,232 +874,253 @@ static void cond_backward(const dppo_net_desc& d, const float* prm, const char* 
   launch_colsum<P>(B.d_cz, (int)M, d.cond_hidden, L.C1p, B.part, REDUCE_BLOCKS, grad + pl.c1b, 1.f, s);
 }
 
-// d_out (B.d_out, [M][Kpo] elem) -> gradients of every parameter of the network into `grad`
+// ---- the fused backward, stage by stage.  Every stage READS B.route; none decides routing. ---------------------------
+constexpr int TAIL_SIDE = 1;  // side-stream index of the actor's bias / time-embedding gradient tail
+// one kernel produces every data gradient (dh[nb..0], dz1[..]) and their per-tile column sums; returns its refusal code
 template <class P>
-static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
-                         MlpBufs<P>& B, float* grad, const int32_t* krow, const dppo_step* ksteps, int Kft,
-                         hipStream_t s, bool bout_done = false, int aux_idx = 1, const LossArgs* fin = nullptr) {
-  // fin: the loss's statistics are finalised off the critical path (on the tail stream, or after the GEMMs)
+static int launch_backward_kernel(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
+                                  MlpBufs<P>& B, hipStream_t s, float*& dw0_slab) {
+  const BwdRoute& R = B.route;
   const ParamLayout pl = param_layout(d);
   const int H = d.hidden, nb = d.n_blocks;
-  if (fused_ok<P>(d) && B.tiles > 0) {
-    // one kernel produces every data gradient (dh[nb..0], dz1[..]) and their per-tile column sums
-    FusedBwdArgs f;
-    memset(&f, 0, sizeof(f));
-    const FusedGeom fg = fused_geom<P>(d);
-    f.bstream = (const u32x4*)(pk + L.bstream), f.d_out = B.d_out, f.ld_dout = L.Kpo, f.M = (int)M, f.KpB0 = fg.KpB0;
-    f.nb = nb, f.act = d.act, f.colsum = B.tile_colsum, f.out_valid = d.out_dim;
-    f.dout_slot = bout_done ? -1 : 2 * nb + 1 + (d.use_layernorm ? 4 * nb : 0);
-    const bool post = false;  // the forward left the derivative sources in z1 / hpre (see emit())
-    f.params = prm, f.use_ln = d.use_layernorm, f.ln_stats = B.ln_stats;
-    if (d.use_layernorm) fill_ln_off(d, pl, f.ln_off);
-    for (int b = 0; b < nb; ++b) {
-      f.m1[b] = post ? B.a2[b] : B.z1[b];
-      f.m0[b] = post ? B.a1[b] : B.hpre[b];
-      f.dz1[b] = B.dz1_all[b];
-    }
-    for (int b = 0; b <= nb; ++b) f.dh[b] = B.dh_all[b];
-    const bool lowrank = lowrank_top(d, M);
-    if (lowrank) f.dh[nb] = nullptr;  // only dW2 of the top block read it: see lowrank_dw_kernel
-    const bool one = bwd_one<P>(d, M);  // (what carve_mlp sized the per-tile column sums for)
-    f.one_block = one ? 1 : 0;
-    if (g_dbg & 1)  // timing experiment: no gradient stores (the weight-gradient GEMMs then read stale buffers)
-      for (int b = 0; b <= nb; ++b) f.dh[b] = nullptr, f.dz1[b < nb ? b : 0] = nullptr;
-    if (g_dbg & 32) f.dh[0] = nullptr;  // timing experiment: dh_0 is not stored (bound of the in-kernel dW0)
-    if (g_dbg & 2)  // timing experiment: no derivative-source fetch
-      for (int b = 0; b < nb; ++b) f.m1[b] = f.m0[b] = nullptr;
-    // in-kernel dW0 (dw0_ok() held when the rows were built): a slab per workgroup out of the pool, reduced with the GEMMs' slabs
-    const bool dw0 = B.dw0 && one && !(g_dbg & 33);
-    const int dw0_nh = dw0 ? dw0_nhot(d, Kft) : 0;
-    float* dw0_slab = nullptr;
-    int dw0_grid = 0;
-    if (B.dw0 && !dw0) {
-      g_fused_fault = -7;  // (the compact rows were built for a pass that cannot use them: dw0_ok() and this function disagree)
-      return;
-    }
-    if (dw0) {
-      dw0_grid = fused_bwd_one_grid<P>(d, M);
-      if ((size_t)dw0_grid * H * 32 > B.slab_floats - B.slab_used) flush_slabs(B, s);
-      dw0_slab = B.slab + B.slab_used;
-      B.slab_used += (size_t)dw0_grid * H * 32;
-      f.dh[0] = nullptr, f.dw0_slab = dw0_slab, f.xc = B.in, f.ld_xc = L.Kp0;
-      f.xc_af = d.kind == 0 ? d.act_flat : 64, f.xc_skip = d.kind == 0 ? d.time_dim : 0;
-      f.dw0_round = d.kind == 0 && dw0_nh < Kft ? 1 : 0;  // (the last one-hot column is rebuilt from the bias gradient)
-    }
-    g_fused_fault = launch_fused_backward<P>(d, f, s);
-    if (g_fused_fault != 0) return;
-    {
-      // bias gradients = column sums, reduced over tiles in one launch; slot order: dh[nb..0], then dz1[nb-1..0]
-      SlotOuts so;
-      memset(&so, 0, sizeof(so));
-      so.n_slots = 2 * nb + 1;
-      for (int b = nb - 1; b >= 0; --b) {
-        so.out[nb - (b + 1)] = grad + pl.l2b[b];
-        so.out[(nb + 1) + (nb - 1 - b)] = grad + pl.l1b[b];
-      }
-      so.out[nb] = grad + pl.b0;
-      if (d.use_layernorm) {  // 4 more slots per block, top block first: d gamma1, d beta1, d gamma2, d beta2
-        for (int b = nb - 1; b >= 0; --b) {
-          const int ls = (2 * nb + 1) + 4 * (nb - 1 - b);
-          so.out[ls] = grad + pl.n1w[b], so.out[ls + 1] = grad + pl.n1b[b];
-          so.out[ls + 2] = grad + pl.n2w[b], so.out[ls + 3] = grad + pl.n2b[b];
-        }
-        so.n_slots += 4 * nb;
-      }
-      for (int i = 0; i < so.n_slots; ++i) so.n[i] = H;
-      if (one) so.n[0] = 0;  // colsum(dh_nb) is not formed by the one-block kernel: db2 comes from PostReduce::db2
-      // in-kernel dW0 without room for the last one-hot column: the bias gradient is the column sums of the rounded dh_0
-      const float* s_rest = dw0 && f.dw0_round ? grad + pl.b0 : nullptr;
-      if (!bout_done) so.out[so.n_slots] = grad + pl.bout, so.n[so.n_slots] = d.out_dim, ++so.n_slots;  // the d_out slot
-      // The bias sums and the loss statistics ride in the slab-reduction launch behind the GEMMs (tail_reduce_kernel).
-      // Only the rare time-embedding gradient WITHOUT the one-hot columns (a gemm_nt + segmented sum over all rows, see
-      // temb_onehot_col) still runs beside the GEMMs on a side stream (it shares B.part with nothing on s).
-      const int oh = d.kind == 0 ? temb_onehot_col<P>(d, L, Kft, B) : -1;  // must match what the row builder was told
-      const bool need_aux = d.kind == 0 && oh < 0;
-      hipStream_t aux = aux_idx >= 0 && need_aux ? fork_side(s, aux_idx) : s;
-      if (need_aux) time_embedding_grad<P>(d, prm, pk, L, M, B, B.dh_all[0], grad, krow, ksteps, Kft, aux);
-      // merged top (the forward never formed h_nb): dWout = d_out^T . h_nb is rebuilt behind the slab reduce from
-      // U = d_out^T . x and T = d_out^T . act(z1) (PostReduce::U); T is then needed whether or not dW2 uses it
-      const bool merged = B.merged;
-      const bool side_tail = dw0 && d.kind == 0 && oh >= 0 && aux_idx >= 0 && !need_aux && g_side_tail && g_early_join && g_post_one &&
-                             B.post_zeroed && !(g_dbg & 28);
-      TailReduce side_t;
-      memset(&side_t, 0, sizeof(side_t));
-      if (merged)
-        weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.in, L.Kp0, d.in_dim, M, B, B.lowrank_u, L.Kp0, s, true);
-      else
-        weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.hE, H, H, M, B, grad + pl.Wout, H, s, true);
-      for (int b = nb - 1; b >= 0; --b) {
-        if ((lowrank || merged) && b == nb - 1)  // T = d_out^T . act(z1), [out_dim][H]; dW2 = Wout^T . T after the slab reduce
-          weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.a2[b], H, H, M, B, B.lowrank, H, s, true);
-        if (!(lowrank && b == nb - 1))
-          weight_grad<P>(B.dh_all[b + 1], H, H, B.a2[b], H, H, M, B, grad + pl.l2w[b], H, s, true);
-        weight_grad<P>(B.dz1_all[b], H, H, B.a1[b], H, H, M, B, grad + pl.l1w[b], H, s, true);
-      }
-      if (dw0) {  // the kernel's per-workgroup partials [grid][H][32]: data columns -> dW0, one-hot columns -> S[h][k] (B.part)
-        auto job = [&](int c0, int cols, float* out, int ldo) {
-          SlabJob& j = side_tail ? side_t.jobs.j[side_t.jobs.n++] : B.slab_jobs.j[B.slab_jobs.n++];
-          j.slab = dw0_slab, j.out = out, j.splits = dw0_grid, j.rows = H, j.cols = cols, j.lds = 32, j.ldo = ldo, j.transpose = 0;
-          j.c0 = c0, j.wide = dw0_grid >= 32 ? 1 : 0;  // (a slab per workgroup: slab_job_block_wide)
-        };
-        if (d.kind == 0) {
-          job(0, d.act_flat, grad + pl.W0, d.in_dim);
-          job(d.act_flat, d.cond_dim, grad + pl.W0 + d.act_flat + d.time_dim, d.in_dim);
-          job(d.act_flat + d.cond_dim, dw0_nh, B.part, Kft);
-        } else {
-          job(0, d.in_dim, grad + pl.W0, d.in_dim);
-        }
-      } else if (g_dbg & 32) {  // timing experiment: no dW0 product in the group
-      } else if (oh >= 0)  // + Kft one-hot columns: their block of the result is S[h][k] (B.part), see temb_onehot_col()
-        weight_grad<P>(B.dh_all[0], H, H, B.in, L.Kp0, d.in_dim + Kft, M, B, grad + pl.W0, d.in_dim, s, true, d.in_dim, B.part,
-                       Kft);
-      else
-        weight_grad<P>(B.dh_all[0], H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s, true);
-      if (side_tail) {
-        // what the backward kernel alone feeds: its dW0 slabs, the bias sums, the loss statistics, then the time-embedding
-        // gradient -- queued on the side stream here, BEHIND the kernel and BESIDE the GEMM launch that follows on s
-        hipStream_t st = fork_side(s, aux_idx);
-        side_t.colsum = B.tile_colsum, side_t.tiles = B.tiles, side_t.width = H, side_t.slots = so;
-        launch_tail_reduce(side_t, fin, st);
-        PostReduce qs;
-        memset(&qs, 0, sizeof(qs));
-        qs.H = H, qs.out_dim = d.out_dim;
-        qs.S = B.part, qs.W0 = prm + pl.W0, qs.ldw0 = d.in_dim, qs.AF = d.act_flat, qs.Kft = Kft, qs.td = d.time_dim;
-        qs.G = B.part + (size_t)H * Kft, qs.w1 = prm + pl.te1_w, qs.b1 = prm + pl.te1_b, qs.w2 = prm + pl.te2_w;
-        qs.ksteps = ksteps, qs.gw1 = grad + pl.te1_w, qs.gb1 = grad + pl.te1_b, qs.gw2 = grad + pl.te2_w, qs.gb2 = grad + pl.te2_b;
-        qs.S_rest = s_rest, qs.dW0t = grad + pl.W0, qs.temb = (const float*)(pk + L.temb), qs.temb_bf16 = P::ESIZE == 2 ? 1 : 0;
-        qs.counter = (unsigned*)B.post_counter;
-        launch_post_reduce(qs, st);
-        B.join_s[B.n_join] = st, B.join_idx[B.n_join++] = aux_idx;  // (joined right behind the GEMM launch: flush_slabs)
-      }
-      if (aux != s && g_early_join) B.join_s[B.n_join] = aux, B.join_idx[B.n_join++] = aux_idx;
-      const bool tail_post = side_tail && g_tail_post && (lowrank || merged || one);
-      if (tail_post)
-        flush_slabs(B, s, nullptr, 0, nullptr, true);  // the GEMMs; their slabs are reduced with the post-reduce parts below
-      else if (side_tail)
-        flush_slabs(B, s);  // the GEMMs' own slabs
-      else
-        flush_slabs(B, s, &so, H, fin);  // every slab of this backward, its bias sums and the loss statistics: one launch
-      if (aux != s && !g_early_join) join_side(s, aux, aux_idx);
-      PostReduce q;
-      memset(&q, 0, sizeof(q));
-      q.H = H, q.out_dim = d.out_dim, q.T = B.lowrank;
-      if (merged) {  // (cs = column sums of d_out = the out-layer bias gradient, reduced on the aux stream joined above)
-        q.U = B.lowrank_u, q.ldu = L.Kp0, q.in_dim = d.in_dim, q.W0 = prm + pl.W0, q.ldw0 = d.in_dim, q.W2 = prm + pl.l2w[nb - 1];
-        q.b0 = prm + pl.b0, q.b2 = prm + pl.l2b[nb - 1], q.cs = grad + pl.bout, q.dWout = grad + pl.Wout;
-      }
-      if (one) q.db2 = grad + pl.l2b[0], q.Wout_b = prm + pl.Wout, q.cs = grad + pl.bout;
-      // everything behind the reduction in one launch (knob 18); its arrival counter (zeroed by the row builder) is only
-      // needed by the time-embedding part
-      if (g_post_one && (oh < 0 || B.post_zeroed) && (lowrank || oh >= 0 || merged || one)) {
-        if (lowrank) q.Wout = prm + pl.Wout, q.dW = grad + pl.l2w[nb - 1];
-        if (oh >= 0 && !side_tail) {
-          q.S = B.part, q.W0 = prm + pl.W0, q.ldw0 = d.in_dim, q.AF = d.act_flat, q.Kft = Kft, q.td = d.time_dim;
-          q.G = B.part + (size_t)H * Kft, q.w1 = prm + pl.te1_w, q.b1 = prm + pl.te1_b, q.w2 = prm + pl.te2_w;
-          q.ksteps = ksteps, q.gw1 = grad + pl.te1_w, q.gb1 = grad + pl.te1_b, q.gw2 = grad + pl.te2_w;
-          q.gb2 = grad + pl.te2_b;
-          if (dw0)  // the time-embedding columns of dW0 from the one-hot sums, the last of which may have to be rebuilt
-            q.S_rest = s_rest, q.dW0t = grad + pl.W0, q.temb = (const float*)(pk + L.temb), q.temb_bf16 = P::ESIZE == 2 ? 1 : 0;
-        }
-        q.counter = (unsigned*)B.post_counter;
-        if (tail_post) {  // (no time-embedding part here: it went to the side stream)
-          TailPost tp;
-          memset(&tp, 0, sizeof(tp));
-          for (int pass = 0; pass < 2; ++pass)  // the thin products' jobs first
-            for (int i = 0; i < B.slab_jobs.n; ++i) {
-              const SlabJob& j = B.slab_jobs.j[i];
-              const bool thin = j.out == B.lowrank || j.out == B.lowrank_u;
-              if (thin == (pass == 0)) tp.jobs.j[tp.jobs.n++] = j;
-              if (thin && pass == 0) ++tp.n_first_jobs;
-            }
-          tp.q = q;
-          tp.q.wait_cnt = B.tail_counter;  // (zeroed by the row builder: B.post_zeroed)
-          launch_tail_post(tp, s);
-          B.slab_jobs.n = 0, B.slab_used = 0;
-        } else {
-          launch_post_reduce(q, s);
-        }
-      } else {
-        launch_wout_grad(q, s);  // (merged top and / or one-block backward; nothing otherwise)
-        if (lowrank) launch_lowrank_dw(prm + pl.Wout, B.lowrank, d.out_dim, H, grad + pl.l2w[nb - 1], s);
-        if (oh >= 0)
-          launch_time_backward_from_sums(prm + pl.te1_w, prm + pl.te1_b, prm + pl.te2_w, B.part, prm + pl.W0, d.in_dim,
-                                         d.act_flat, H, B.part + (size_t)H * Kft, ksteps, Kft, d.time_dim, grad + pl.te1_w,
-                                         grad + pl.te1_b, grad + pl.te2_w, grad + pl.te2_b, s);
-      }
-      B.dh0_final = dw0 ? nullptr : B.dh_all[0];  // (in-kernel dW0: no dh_0 exists; dw0_ok() made sure nobody asks)
-      return;
-    }
+  FusedBwdArgs f;
+  memset(&f, 0, sizeof(f));
+  f.bstream = (const u32x4*)(pk + L.bstream), f.d_out = B.d_out, f.ld_dout = L.Kpo, f.M = (int)M, f.KpB0 = fused_geom<P>(d).KpB0;
+  f.nb = nb, f.act = d.act, f.colsum = B.tile_colsum, f.out_valid = d.out_dim;
+  f.dout_slot = 2 * nb + 1 + (d.use_layernorm ? 4 * nb : 0);
+  f.params = prm, f.use_ln = d.use_layernorm, f.ln_stats = B.ln_stats;
+  if (d.use_layernorm) fill_ln_off(d, pl, f.ln_off);
+  for (int b = 0; b < nb; ++b)  // the forward left the derivative sources in z1 / hpre (see emit())
+    f.m1[b] = B.z1[b], f.m0[b] = B.hpre[b], f.dz1[b] = B.dz1_all[b];
+  for (int b = 0; b <= nb; ++b) f.dh[b] = B.dh_all[b];
+  if (R.lowrank) f.dh[nb] = nullptr;  // only dW2 of the top block read it: see lowrank_dw_kernel
+  f.one_block = R.one_block ? 1 : 0;
+  if (g_dbg & 1)  // timing experiment: no gradient stores (the weight-gradient GEMMs then read stale buffers)
+    for (int b = 0; b <= nb; ++b) f.dh[b] = nullptr, f.dz1[b < nb ? b : 0] = nullptr;
+  if (g_dbg & 32) f.dh[0] = nullptr;  // timing experiment: dh_0 is not stored (bound of the in-kernel dW0)
+  if (g_dbg & 2)  // timing experiment: no derivative-source fetch
+    for (int b = 0; b < nb; ++b) f.m1[b] = f.m0[b] = nullptr;
+  dw0_slab = nullptr;
+  if (R.dw0) {  // in-kernel dW0: a slab per workgroup out of the pool, reduced with the GEMMs' slabs
+    const size_t need = (size_t)fused_bwd_one_grid<P>(d, M) * H * 32;
+    if (need > B.slab_floats - B.slab_used) flush_slabs(B, s);
+    dw0_slab = B.slab + B.slab_used;
+    B.slab_used += need;
+    f.dh[0] = nullptr, f.dw0_slab = dw0_slab, f.xc = B.in, f.ld_xc = L.Kp0;
+    f.xc_af = d.kind == 0 ? d.act_flat : 64, f.xc_skip = d.kind == 0 ? d.time_dim : 0;
+    f.dw0_round = R.dw0_round ? 1 : 0;
   }
-  if (d.plain) {
-    if (fin) launch_loss_finalize(*fin, s);
-    weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.a2[nb - 1], H, H, M, B, grad + pl.Wout, H, s);
-    launch_colsum<P>(B.d_out, (int)M, d.out_dim, L.Kpo, B.part, REDUCE_BLOCKS, grad + pl.bout, 1.f, s);
-    GemmNT q;  // dz = (upstream . W) * act'(z): starts from d_out . Wout at the last hidden layer's pre-activation
-    memset(&q, 0, sizeof(q));
-    q.M = (int)M, q.N = H, q.Kp = L.Kpo, q.ldx = L.Kpo, q.ldw = L.Kpo, q.ldo = H;
-    q.X = B.d_out, q.W = pk + L.WoutT, q.dsrc = B.z1[nb - 1], q.dsrc_kind = 2, q.dsrc_ld = H, q.dact = d.act, q.out_pre = B.dh;
-    launch_gemm_nt<P>(q, s);
-    void* dz = B.dh;
-    void* other = B.dz1;
+  return launch_fused_backward<P>(d, f, s);
+}
+// bias gradients = column sums, reduced over tiles in one launch; slot order: dh[nb..0], then dz1[nb-1..0]
+static SlotOuts bias_slots(const dppo_net_desc& d, const ParamLayout& pl, const BwdRoute& R, float* grad) {
+  const int H = d.hidden, nb = d.n_blocks;
+  SlotOuts so;
+  memset(&so, 0, sizeof(so));
+  so.n_slots = 2 * nb + 1;
+  for (int b = nb - 1; b >= 0; --b) {
+    so.out[nb - (b + 1)] = grad + pl.l2b[b];
+    so.out[(nb + 1) + (nb - 1 - b)] = grad + pl.l1b[b];
+  }
+  so.out[nb] = grad + pl.b0;
+  if (d.use_layernorm) {  // 4 more slots per block, top block first: d gamma1, d beta1, d gamma2, d beta2
     for (int b = nb - 1; b >= 0; --b) {
-      weight_grad<P>(dz, H, H, b == 0 ? B.a1[0] : B.a2[b - 1], H, H, M, B, grad + pl.l1w[b], H, s);
-      launch_colsum<P>(dz, (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.l1b[b], 1.f, s);
-      memset(&q, 0, sizeof(q));
-      q.M = (int)M, q.N = H, q.Kp = H, q.ldx = H, q.ldw = H, q.ldo = H;
-      q.X = dz, q.W = pk + L.W1T[b], q.dsrc = b == 0 ? B.hpre[0] : B.z1[b - 1], q.dsrc_kind = 2, q.dsrc_ld = H, q.dact = d.act;
-      q.out_pre = other;
-      launch_gemm_nt<P>(q, s);
-      void* t = dz;
-      dz = other, other = t;
+      const int ls = (2 * nb + 1) + 4 * (nb - 1 - b);
+      so.out[ls] = grad + pl.n1w[b], so.out[ls + 1] = grad + pl.n1b[b];
+      so.out[ls + 2] = grad + pl.n2w[b], so.out[ls + 3] = grad + pl.n2b[b];
     }
-    weight_grad<P>(dz, H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s);
-    launch_colsum<P>(dz, (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.b0, 1.f, s);
-    if (d.kind == 0) time_embedding_grad<P>(d, prm, pk, L, M, B, dz, grad, krow, ksteps, Kft, s);
-    B.dh0_final = dz;
+    so.n_slots += 4 * nb;
+  }
+  for (int i = 0; i < so.n_slots; ++i) so.n[i] = H;
+  if (R.one_block) so.n[0] = 0;  // colsum(dh_nb) is not formed by the one-block kernel: db2 comes from PostReduce::db2
+  so.out[so.n_slots] = grad + pl.bout, so.n[so.n_slots] = d.out_dim, ++so.n_slots;  // the d_out slot: the out layer's bias gradient
+  return so;
+}
+// the weight-gradient products, queued for one grouped launch (flush_slabs); the in-kernel dW0's slab jobs go to `side`
+// when the side tail reduces them
+template <class P>
+static void queue_weight_grads(const dppo_net_desc& d, const ParamLayout& pl, const PackLayout& L, int64_t M, MlpBufs<P>& B,
+                               float* grad, int Kft, hipStream_t s, float* dw0_slab, SlabJobs& side) {
+  const BwdRoute& R = B.route;
+  const int H = d.hidden, nb = d.n_blocks;
+  // merged top (the forward never formed h_nb): dWout = d_out^T . h_nb is rebuilt behind the slab reduce from
+  // U = d_out^T . x and T = d_out^T . act(z1) (PostReduce::U); T is then needed whether or not dW2 uses it
+  if (R.merged)
+    weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.in, L.Kp0, d.in_dim, M, B, B.lowrank_u, L.Kp0, s, true);
+  else
+    weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.hE, H, H, M, B, grad + pl.Wout, H, s, true);
+  for (int b = nb - 1; b >= 0; --b) {
+    if ((R.lowrank || R.merged) && b == nb - 1)  // T = d_out^T . act(z1), [out_dim][H]; dW2 = Wout^T . T after the slab reduce
+      weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.a2[b], H, H, M, B, B.lowrank, H, s, true);
+    if (!(R.lowrank && b == nb - 1))
+      weight_grad<P>(B.dh_all[b + 1], H, H, B.a2[b], H, H, M, B, grad + pl.l2w[b], H, s, true);
+    weight_grad<P>(B.dz1_all[b], H, H, B.a1[b], H, H, M, B, grad + pl.l1w[b], H, s, true);
+  }
+  if (R.dw0) {  // the kernel's per-workgroup partials [grid][H][32]: data columns -> dW0, one-hot columns -> S[h][k] (B.part)
+    const int grid = fused_bwd_one_grid<P>(d, M);
+    auto job = [&](int c0, int cols, float* out, int ldo) {
+      SlabJob& j = R.side_tail ? side.j[side.n++] : B.slab_jobs.j[B.slab_jobs.n++];
+      j.slab = dw0_slab, j.out = out, j.splits = grid, j.rows = H, j.cols = cols, j.lds = 32, j.ldo = ldo, j.transpose = 0;
+      j.c0 = c0, j.wide = grid >= 32 ? 1 : 0;  // (a slab per workgroup: slab_job_block_wide)
+    };
+    if (d.kind == 0) {
+      job(0, d.act_flat, grad + pl.W0, d.in_dim);
+      job(d.act_flat, d.cond_dim, grad + pl.W0 + d.act_flat + d.time_dim, d.in_dim);
+      job(d.act_flat + d.cond_dim, R.dw0_nhot, B.part, Kft);
+    } else {
+      job(0, d.in_dim, grad + pl.W0, d.in_dim);
+    }
+  } else if (g_dbg & 32) {  // timing experiment: no dW0 product in the group
+  } else if (R.onehot_col >= 0)  // + Kft one-hot columns: their block of the result is S[h][k] (B.part), see plan_route()
+    weight_grad<P>(B.dh_all[0], H, H, B.in, L.Kp0, d.in_dim + Kft, M, B, grad + pl.W0, d.in_dim, s, true, d.in_dim, B.part, Kft);
+  else
+    weight_grad<P>(B.dh_all[0], H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s, true);
+}
+// the time-embedding half of a PostReduce: G = W0_temb^T . S from the one-hot sums S (B.part), then the time MLP's backward
+template <class P>
+static void fill_time_post(PostReduce& q, const dppo_net_desc& d, const ParamLayout& pl, const float* prm, const char* pk,
+                           const PackLayout& L, const MlpBufs<P>& B, float* grad, const dppo_step* ksteps, int Kft) {
+  q.S = B.part, q.W0 = prm + pl.W0, q.ldw0 = d.in_dim, q.AF = d.act_flat, q.Kft = Kft, q.td = d.time_dim;
+  q.G = B.part + (size_t)d.hidden * Kft, q.w1 = prm + pl.te1_w, q.b1 = prm + pl.te1_b, q.w2 = prm + pl.te2_w;
+  q.ksteps = ksteps, q.gw1 = grad + pl.te1_w, q.gb1 = grad + pl.te1_b, q.gw2 = grad + pl.te2_w, q.gb2 = grad + pl.te2_b;
+  if (B.route.dw0) {  // the time-embedding columns of dW0 from the one-hot sums, the last of which may have to be rebuilt
+    // (without room for it the first layer's bias gradient is the column sums of the rounded dh_0)
+    q.S_rest = B.route.dw0_round ? grad + pl.b0 : nullptr, q.dW0t = grad + pl.W0;
+    q.temb = (const float*)(pk + L.temb), q.temb_bf16 = P::ESIZE == 2 ? 1 : 0;
+  }
+}
+// Side tail (knob 38): what the backward kernel alone feeds -- its dW0 slabs, the bias sums, the loss statistics, then the
+// time-embedding gradient -- queued on the side stream BEHIND the kernel and BESIDE the GEMM launch that follows on s
+template <class P>
+static void launch_side_tail(const dppo_net_desc& d, const ParamLayout& pl, const float* prm, const char* pk, const PackLayout& L,
+                             MlpBufs<P>& B, float* grad, const dppo_step* ksteps, int Kft, hipStream_t s, const SlotOuts& so,
+                             const SlabJobs& jobs, const LossArgs* fin) {
+  hipStream_t st = fork_side(s, TAIL_SIDE);
+  TailReduce t;
+  memset(&t, 0, sizeof(t));
+  t.jobs = jobs, t.colsum = B.tile_colsum, t.tiles = B.tiles, t.width = d.hidden, t.slots = so;
+  launch_tail_reduce(t, fin, st);
+  PostReduce q;
+  memset(&q, 0, sizeof(q));
+  q.H = d.hidden, q.out_dim = d.out_dim;
+  fill_time_post<P>(q, d, pl, prm, pk, L, B, grad, ksteps, Kft);
+  q.counter = (unsigned*)B.post_counter;
+  launch_post_reduce(q, st);
+  B.join_s[B.n_join] = st, B.join_idx[B.n_join++] = TAIL_SIDE;  // (joined right behind the GEMM launch: flush_slabs)
+}
+// what follows the slab reduction on s: the low-rank dW2, dWout / db2 of a merged / one-block network, the time-embedding
+// gradient from the one-hot sums (unless the side tail took it) -- one launch (knob 18; with knob 41 the slab reduction too)
+template <class P>
+static void launch_post(const dppo_net_desc& d, const ParamLayout& pl, const float* prm, const char* pk, const PackLayout& L,
+                        MlpBufs<P>& B, float* grad, const dppo_step* ksteps, int Kft, hipStream_t s) {
+  const BwdRoute& R = B.route;
+  const int H = d.hidden, nb = d.n_blocks;
+  const bool oh = R.onehot_col >= 0;
+  PostReduce q;
+  memset(&q, 0, sizeof(q));
+  q.H = H, q.out_dim = d.out_dim, q.T = B.lowrank;
+  if (R.merged) {  // (cs = column sums of d_out = the out-layer bias gradient, reduced on the aux stream joined above)
+    q.U = B.lowrank_u, q.ldu = L.Kp0, q.in_dim = d.in_dim, q.W0 = prm + pl.W0, q.ldw0 = d.in_dim, q.W2 = prm + pl.l2w[nb - 1];
+    q.b0 = prm + pl.b0, q.b2 = prm + pl.l2b[nb - 1], q.cs = grad + pl.bout, q.dWout = grad + pl.Wout;
+  }
+  if (R.one_block) q.db2 = grad + pl.l2b[0], q.Wout_b = prm + pl.Wout, q.cs = grad + pl.bout;
+  if (!R.post_one) {
+    launch_wout_grad(q, s);  // (merged top and / or one-block backward; nothing otherwise)
+    if (R.lowrank) launch_lowrank_dw(prm + pl.Wout, B.lowrank, d.out_dim, H, grad + pl.l2w[nb - 1], s);
+    if (oh) {
+      PostReduce t = {};
+      fill_time_post<P>(t, d, pl, prm, pk, L, B, grad, ksteps, Kft);
+      launch_time_backward_from_sums(t.w1, t.b1, t.w2, t.S, t.W0, t.ldw0, t.AF, H, t.G, ksteps, Kft, t.td, t.gw1, t.gb1, t.gw2, t.gb2, s);
+    }
     return;
   }
-  if (fin) launch_loss_finalize(*fin, s);
+  if (R.lowrank) q.Wout = prm + pl.Wout, q.dW = grad + pl.l2w[nb - 1];
+  if (oh && !R.side_tail) fill_time_post<P>(q, d, pl, prm, pk, L, B, grad, ksteps, Kft);
+  q.counter = (unsigned*)B.post_counter;
+  if (!R.tail_post) {
+    launch_post_reduce(q, s);
+    return;
+  }
+  TailPost tp;  // (no time-embedding part here: it went to the side stream)
+  memset(&tp, 0, sizeof(tp));
+  for (int pass = 0; pass < 2; ++pass)  // the thin products' jobs first
+    for (int i = 0; i < B.slab_jobs.n; ++i) {
+      const SlabJob& j = B.slab_jobs.j[i];
+      const bool thin = j.out == B.lowrank || j.out == B.lowrank_u;
+      if (thin == (pass == 0)) tp.jobs.j[tp.jobs.n++] = j;
+      if (thin && pass == 0) ++tp.n_first_jobs;
+    }
+  tp.q = q;
+  tp.q.wait_cnt = B.tail_counter;  // (zeroed by the row builder: DPPO_ROUTE_IN_ZEROED)
+  launch_tail_post(tp, s);
+  B.slab_jobs.n = 0, B.slab_used = 0;
+}
+template <class P>
+static void backward_fused(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
+                           MlpBufs<P>& B, float* grad, const int32_t* krow, const dppo_step* ksteps, int Kft,
+                           hipStream_t s, const LossArgs* fin) {
+  const BwdRoute& R = B.route;
+  const ParamLayout pl = param_layout(d);
+  float* dw0_slab;
+  g_fused_fault = launch_backward_kernel<P>(d, prm, pk, L, M, B, s, dw0_slab);
+  if (g_fused_fault != 0) return;
+  const SlotOuts so = bias_slots(d, pl, R, grad);
+  // The bias sums and the loss statistics ride in the slab-reduction launch behind the GEMMs (tail_reduce_kernel).
+  // Only the rare time-embedding gradient WITHOUT the one-hot columns (a gemm_nt + segmented sum over all rows) still runs
+  // beside the GEMMs on a side stream (it shares B.part with nothing on s).
+  hipStream_t aux = R.aux_side ? fork_side(s, TAIL_SIDE) : s;
+  if (R.need_aux) time_embedding_grad<P>(d, prm, pk, L, M, B, B.dh_all[0], grad, krow, ksteps, Kft, aux);
+  SlabJobs side_jobs = {};
+  queue_weight_grads<P>(d, pl, L, M, B, grad, Kft, s, dw0_slab, side_jobs);
+  if (R.side_tail) launch_side_tail<P>(d, pl, prm, pk, L, B, grad, ksteps, Kft, s, so, side_jobs, fin);
+  if (aux != s && g_early_join) B.join_s[B.n_join] = aux, B.join_idx[B.n_join++] = TAIL_SIDE;
+  if (R.tail_post)
+    flush_slabs(B, s, nullptr, 0, nullptr, true);  // the GEMMs; their slabs are reduced with the post-reduce parts below
+  else if (R.side_tail)
+    flush_slabs(B, s);  // the GEMMs' own slabs
+  else
+    flush_slabs(B, s, &so, d.hidden, fin);  // every slab of this backward, its bias sums and the loss statistics: one launch
+  if (aux != s && !g_early_join) join_side(s, aux, TAIL_SIDE);
+  launch_post<P>(d, pl, prm, pk, L, B, grad, ksteps, Kft, s);
+  B.dh0_final = R.dw0 ? nullptr : B.dh_all[0];  // (in-kernel dW0: no dh_0 exists; plan_route() made sure nobody asks)
+}
+// a plain MLP's backward, layer by layer
+template <class P>
+static void backward_plain(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
+                           MlpBufs<P>& B, float* grad, const int32_t* krow, const dppo_step* ksteps, int Kft, hipStream_t s) {
+  const ParamLayout pl = param_layout(d);
+  const int H = d.hidden, nb = d.n_blocks;
+  weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.a2[nb - 1], H, H, M, B, grad + pl.Wout, H, s);
+  launch_colsum<P>(B.d_out, (int)M, d.out_dim, L.Kpo, B.part, REDUCE_BLOCKS, grad + pl.bout, 1.f, s);
+  GemmNT q;  // dz = (upstream . W) * act'(z): starts from d_out . Wout at the last hidden layer's pre-activation
+  memset(&q, 0, sizeof(q));
+  q.M = (int)M, q.N = H, q.Kp = L.Kpo, q.ldx = L.Kpo, q.ldw = L.Kpo, q.ldo = H;
+  q.X = B.d_out, q.W = pk + L.WoutT, q.dsrc = B.z1[nb - 1], q.dsrc_kind = 2, q.dsrc_ld = H, q.dact = d.act, q.out_pre = B.dh;
+  launch_gemm_nt<P>(q, s);
+  void* dz = B.dh;
+  void* other = B.dz1;
+  for (int b = nb - 1; b >= 0; --b) {
+    weight_grad<P>(dz, H, H, b == 0 ? B.a1[0] : B.a2[b - 1], H, H, M, B, grad + pl.l1w[b], H, s);
+    launch_colsum<P>(dz, (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.l1b[b], 1.f, s);
+    memset(&q, 0, sizeof(q));
+    q.M = (int)M, q.N = H, q.Kp = H, q.ldx = H, q.ldw = H, q.ldo = H;
+    q.X = dz, q.W = pk + L.W1T[b], q.dsrc = b == 0 ? B.hpre[0] : B.z1[b - 1], q.dsrc_kind = 2, q.dsrc_ld = H, q.dact = d.act;
+    q.out_pre = other;
+    launch_gemm_nt<P>(q, s);
+    void* t = dz;
+    dz = other, other = t;
+  }
+  weight_grad<P>(dz, H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s);
+  launch_colsum<P>(dz, (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.b0, 1.f, s);
+  if (d.kind == 0) time_embedding_grad<P>(d, prm, pk, L, M, B, dz, grad, krow, ksteps, Kft, s);
+  B.dh0_final = dz;
+}
+// the residual trunk's backward on the layered GEMM path
+template <class P>
+static void backward_layered(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
+                             MlpBufs<P>& B, float* grad, const int32_t* krow, const dppo_step* ksteps, int Kft, hipStream_t s) {
+  const ParamLayout pl = param_layout(d);
+  const int H = d.hidden, nb = d.n_blocks;
   // output layer parameters
   weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.hE, H, H, M, B, grad + pl.Wout, H, s);
   launch_colsum<P>(B.d_out, (int)M, d.out_dim, L.Kpo, B.part, REDUCE_BLOCKS, grad + pl.bout, 1.f, s);
@@ -1103,6 +1154,18 @@ static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* p
   launch_colsum<P>(B.dh, (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.b0, 1.f, s);
   if (d.kind == 0) time_embedding_grad<P>(d, prm, pk, L, M, B, B.dh, grad, krow, ksteps, Kft, s);
   B.dh0_final = B.dh;
+}
+
+// d_out (B.d_out, [M][Kpo] elem) -> gradients of every parameter of the network into `grad`
+// fin: the loss's statistics are finalised off the critical path (on the tail stream, or after the GEMMs)
+template <class P>
+static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
+                         MlpBufs<P>& B, float* grad, const int32_t* krow, const dppo_step* ksteps, int Kft,
+                         hipStream_t s, const LossArgs* fin = nullptr) {
+  if (B.route.fused) return backward_fused<P>(d, prm, pk, L, M, B, grad, krow, ksteps, Kft, s, fin);
+  if (fin) launch_loss_finalize(*fin, s);  // (the fused backward finalises them in one of its reduction launches)
+  if (d.plain) return backward_plain<P>(d, prm, pk, L, M, B, grad, krow, ksteps, Kft, s);
+  backward_layered<P>(d, prm, pk, L, M, B, grad, krow, ksteps, Kft, s);
 }
 
 // d loss / d observation of a trunk WITHOUT an observation encoder: d_obs[m][c] = sum_h dh0[m][h] W0[h][col0 + c], where the
@@ -1194,19 +1257,14 @@ int dppo_pack_net(const dppo_net_desc* net, int prec, int n_time, const float* p
 }
 
 // ---- forwards --------------------------------------------------------------------------------------
-template <class P>
-static int64_t fwd_ws_bytes(const dppo_net_desc& d, int64_t rows) {
-  Carver c{nullptr, 0, 0};
-  MlpBufs<P> B;
-  carve_mlp<P>(c, d, rows, false, false, B);
-  return (int64_t)al256(c.off);
-}
 int64_t dppo_mlp_forward_workspace_bytes(const dppo_net_desc* net, int prec, int64_t rows) {
   if (check_net(net) || check_prec(prec)) return -1;
   if (rows < 0 || rows > 0x7fffffff) return fail(-1, "rows out of range");
-#define CALL(P) fwd_ws_bytes<P>(*net, rows)
-  return DPPO_DISPATCH(prec, CALL);
-#undef CALL
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    MlpBufs<decltype(p)> B;
+    carve_mlp<decltype(p)>(c, *net, rows, false, false, B);
+    return al256(c.off);
+  });
 }
 
 template <class P>
@@ -1353,14 +1411,11 @@ int64_t dppo_plain_sample_workspace_bytes(const dppo_net_desc* actor, int prec, 
   if (check_net(actor) || check_prec(prec)) return -1;
   if (actor->kind != 0 || !actor->plain) return fail(-1, "dppo_plain_sample_chain needs a plain actor descriptor");
   if (B < 1 || B > 0x7fffffff) return fail(-1, "B out of range");
-  Carver c{nullptr, 0, 0};
-  float* x;
-  if (prec == DPPO_PREC_F32) {
-    MlpBufs<F32> Bz;
-    return (int64_t)carve_plain_sample<F32>(c, *actor, B, Bz, x);
-  }
-  MlpBufs<BF16> Bz;
-  return (int64_t)carve_plain_sample<BF16>(c, *actor, B, Bz, x);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    MlpBufs<decltype(p)> Bz;
+    float* x;
+    return carve_plain_sample<decltype(p)>(c, *actor, B, Bz, x);
+  });
 }
 template <class P>
 static int plain_sample_impl(const dppo_net_desc& d, const float* pb, const char* kb, const float* pf, const char* kf,
@@ -1411,7 +1466,9 @@ int64_t dppo_sample_chain_workspace_bytes(const dppo_net_desc* actor, int prec, 
   if (check_net(actor) || check_prec(prec)) return -1;
   if (actor->plain) return fail(-1, "plain MLP trunks sample through dppo_plain_sample_chain (dppo_plain_sample_workspace_bytes)");
   if (B < 1) return fail(-1, "B out of range");
-  return prec == DPPO_PREC_F32 ? (int64_t)sample_ws<F32>(*actor, B) : (int64_t)sample_ws<BF16>(*actor, B);
+#define CALL(P) (int64_t) sample_ws<P>(*actor, B)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
 }
 
 int64_t dppo_sample_chain_exchange_bytes(const dppo_net_desc* actor, int prec, int64_t B) {
@@ -1444,21 +1501,15 @@ int dppo_sample_chain(const dppo_net_desc* actor, int prec, const float* params_
 }
 
 // ---- chain log-probs ---------------------------------------------------------------------------------
-template <class P>
-static int64_t logprob_ws_bytes(const dppo_net_desc& d, int64_t rows) {
-  Carver c{nullptr, 0, 0};
-  MlpBufs<P> B;
-  carve_mlp<P>(c, d, rows, false, false, B);
-  c.take((size_t)rows * 4);
-  c.take((size_t)rows * 4);
-  return (int64_t)al256(c.off);
-}
 int64_t dppo_chain_logprob_workspace_bytes(const dppo_net_desc* actor, int prec, int64_t B, int Kft) {
   if (check_net(actor) || check_prec(prec)) return -1;
   if (B < 0 || Kft < 1 || B * Kft > 0x7fffffff) return fail(-1, "B*Kft out of range");
-#define CALL(P) logprob_ws_bytes<P>(*actor, B* Kft)
-  return DPPO_DISPATCH(prec, CALL);
-#undef CALL
+  return ws_bytes(prec, [&](Carver& c, auto p) {  // the network's buffers, then brow and krow
+    MlpBufs<decltype(p)> W;
+    carve_mlp<decltype(p)>(c, *actor, B * Kft, false, false, W);
+    c.take((size_t)B * Kft * 4), c.take((size_t)B * Kft * 4);
+    return al256(c.off);
+  });
 }
 
 template <class P>
@@ -1522,43 +1573,54 @@ int64_t dppo_bc_loss_workspace_bytes(const dppo_net_desc* actor, int prec, int64
   if (Kft > 1024 || (int64_t)Kft * actor->time_dim > 65536 ||
       time_backward_lds_bytes(Kft, actor->time_dim) > 156 * 1024)
     return fail(-1, "Kft * time_dim = %d too large for the time-embedding backward (LDS)", Kft * actor->time_dim);
-  Carver c{nullptr, 0, 0};
-  int32_t *br, *kr;
-  if (prec == DPPO_PREC_F32) {
-    MlpBufs<F32> W;
-    return (int64_t)carve_bc<F32>(c, *actor, B * Kft, W, br, kr);
-  }
-  MlpBufs<BF16> W;
-  return (int64_t)carve_bc<BF16>(c, *actor, B * Kft, W, br, kr);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    MlpBufs<decltype(p)> W;
+    int32_t *br, *kr;
+    return carve_bc<decltype(p)>(c, *actor, B * Kft, W, br, kr);
+  });
 }
-template <class P>
-static int bc_impl(const dppo_net_desc& d, const float* prm, const char* pk, const dppo_diffusion_cfg& cfg,
-                   const dppo_step* ksteps, int Kft, const float* obs, const float* chains, int64_t Bn, float* grad,
-                   double* loss, void* ws, int64_t wsb, hipStream_t s) {
-  const int64_t M = Bn * Kft;
+// Behaviour cloning and the supervised denoising loss are one pipeline: rows -> cond_encode -> forward -> loss -> backward ->
+// cond_backward (-> obs_grad).  `br` arrives with the caller's row sources (chains or pairs / kinds, obs); loss(B, L, partial)
+// launches the caller's loss, from B.out into B.d_out.
+template <class P, class Loss>
+static int denoise_train(const dppo_net_desc& d, const float* prm, const char* pk, BuildRows br, const dppo_step* steps, int Kft,
+                         int64_t M, float* grad, float* d_obs, void* ws, int64_t wsb, hipStream_t s, Loss loss) {
   Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> B;
   int32_t *brow, *krow;
   double* partial;
   const size_t need = carve_bc<P>(c, d, M, B, brow, krow, &partial);
   if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = plan_route<P>(d, M, Kft, DPPO_ROUTE_IN_SIDE | (d_obs ? DPPO_ROUTE_IN_DOBS : 0), B)) return e;
   const PackLayout L = pack_layout<P>(d, 0);
-  BuildRows br;
-  memset(&br, 0, sizeof(br));
-  br.chains = chains, br.obs = obs, br.temb = (const float*)(pk + L.temb), br.ksteps = ksteps;
+  br.temb = (const float*)(pk + L.temb), br.ksteps = steps;
   br.Kft = Kft, br.AF = d.act_flat, br.td = d.time_dim, br.cond = d.cond_dim, br.M = M, br.obs_in_a = 1;
-  br.inA = B.in, br.KpA = L.Kp0, br.brow = brow, br.krow = krow, br.onehot0 = temb_onehot_col<P>(d, L, Kft, B);
+  br.inA = B.in, br.KpA = L.Kp0, br.brow = brow, br.krow = krow, br.onehot0 = B.route.onehot_col;
   if (d.cond_hidden > 0) br.obs_in_a = 0, br.inC = B.cin, br.KpC = L.Kpc;
   launch_build_rows<P>(br, s);
   if (d.cond_hidden > 0) cond_encode<P>(d, prm, pk, L, M, B.cin, B, B.in, nullptr, 0, true, s);
   mlp_forward<P>(d, prm, pk, L, M, B, true, s);
-  BcArgs ba;
-  ba.eps = B.out, ba.lde = B.ldout, ba.chains = chains, ba.ksteps = ksteps, ba.cfg = cfg, ba.Kft = Kft;
-  ba.AF = d.act_flat, ba.M = M, ba.d_eps = B.d_out, ba.ldde = L.Kpo, ba.loss = loss, ba.partial = partial;
-  launch_bc_loss<P>(ba, s);
-  mlp_backward<P>(d, prm, pk, L, M, B, grad, krow, ksteps, Kft, s, false);
+  loss(B, L, partial);
+  mlp_backward<P>(d, prm, pk, L, M, B, grad, krow, steps, Kft, s);
   if (d.cond_hidden > 0) cond_backward<P>(d, prm, pk, L, M, B, B.dh0_final, B.cin, grad, s);
+  if (d_obs) obs_grad<P>(d, prm, M, B, d_obs, s);
   return check_launch();
+}
+template <class P>
+static int bc_impl(const dppo_net_desc& d, const float* prm, const char* pk, const dppo_diffusion_cfg& cfg,
+                   const dppo_step* ksteps, int Kft, const float* obs, const float* chains, int64_t Bn, float* grad,
+                   double* loss, void* ws, int64_t wsb, hipStream_t s) {
+  const int64_t M = Bn * Kft;
+  BuildRows br;
+  memset(&br, 0, sizeof(br));
+  br.chains = chains, br.obs = obs;
+  return denoise_train<P>(d, prm, pk, br, ksteps, Kft, M, grad, nullptr, ws, wsb, s,
+                          [&](MlpBufs<P>& B, const PackLayout& L, double* partial) {
+                            BcArgs ba;
+                            ba.eps = B.out, ba.lde = B.ldout, ba.chains = chains, ba.ksteps = ksteps, ba.cfg = cfg, ba.Kft = Kft;
+                            ba.AF = d.act_flat, ba.M = M, ba.d_eps = B.d_out, ba.ldde = L.Kpo, ba.loss = loss, ba.partial = partial;
+                            launch_bc_loss<P>(ba, s);
+                          });
 }
 int dppo_bc_loss_fwd_bwd(const dppo_net_desc* actor, int prec, const float* params, const void* packed,
                          const dppo_diffusion_cfg* cfg, const dppo_step* ksteps, int Kft, const float* obs,
@@ -1592,30 +1654,16 @@ template <class P>
 static int mse_impl(const dppo_net_desc& d, const float* prm, const char* pk, const dppo_step* tsteps, int n_time,
                     const float* obs, const float* pairs, const int64_t* kinds, int64_t M, float* grad, double* loss,
                     void* ws, int64_t wsb, hipStream_t s, float* d_obs = nullptr) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
-  MlpBufs<P> B;
-  int32_t *brow, *krow;
-  double* partial;
-  const size_t need = carve_bc<P>(c, d, M, B, brow, krow, &partial);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
-  const PackLayout L = pack_layout<P>(d, 0);
   BuildRows br;  // gathered mode: row n = (pairs[n][0], temb(tsteps[kinds[n]].t), obs[n])
   memset(&br, 0, sizeof(br));
-  br.kinds = kinds, br.chains = pairs, br.obs = obs, br.temb = (const float*)(pk + L.temb), br.ksteps = tsteps;
-  br.Kft = n_time, br.AF = d.act_flat, br.td = d.time_dim, br.cond = d.cond_dim, br.M = M, br.obs_in_a = 1;
-  br.inA = B.in, br.KpA = L.Kp0, br.brow = brow, br.krow = krow, br.onehot0 = temb_onehot_col<P>(d, L, n_time, B);
-  if (d.cond_hidden > 0) br.obs_in_a = 0, br.inC = B.cin, br.KpC = L.Kpc;
-  launch_build_rows<P>(br, s);
-  if (d.cond_hidden > 0) cond_encode<P>(d, prm, pk, L, M, B.cin, B, B.in, nullptr, 0, true, s);
-  mlp_forward<P>(d, prm, pk, L, M, B, true, s);
-  MseArgs ma;
-  ma.eps = B.out, ma.lde = B.ldout, ma.pairs = pairs, ma.AF = d.act_flat, ma.M = M, ma.d_eps = B.d_out, ma.ldde = L.Kpo;
-  ma.loss = loss, ma.partial = partial;
-  launch_mse_loss<P>(ma, s);
-  mlp_backward<P>(d, prm, pk, L, M, B, grad, krow, tsteps, n_time, s, false);
-  if (d.cond_hidden > 0) cond_backward<P>(d, prm, pk, L, M, B, B.dh0_final, B.cin, grad, s);
-  if (d_obs) obs_grad<P>(d, prm, M, B, d_obs, s);
-  return check_launch();
+  br.kinds = kinds, br.chains = pairs, br.obs = obs;
+  return denoise_train<P>(d, prm, pk, br, tsteps, n_time, M, grad, d_obs, ws, wsb, s,
+                          [&](MlpBufs<P>& B, const PackLayout& L, double* partial) {
+                            MseArgs ma;
+                            ma.eps = B.out, ma.lde = B.ldout, ma.pairs = pairs, ma.AF = d.act_flat, ma.M = M, ma.d_eps = B.d_out;
+                            ma.ldde = L.Kpo, ma.loss = loss, ma.partial = partial;
+                            launch_mse_loss<P>(ma, s);
+                          });
 }
 static int mse_entry(const dppo_net_desc* actor, int prec, const float* params, const void* packed,
                              const dppo_step* tsteps, int n_time, const float* obs, const float* pairs,
@@ -1690,13 +1738,10 @@ static size_t carve_ppo(Carver& c, const dppo_net_desc& a, const dppo_net_desc& 
 int64_t dppo_ppo_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* critic, int prec, int64_t N) {
   if (check_net(actor) || check_net(critic) || check_prec(prec)) return -1;
   if (N < 2 || N > 0x7fffffff) return fail(-1, "N out of range");
-  Carver c{nullptr, 0, 0};
-  if (prec == DPPO_PREC_F32) {
-    PpoWs<F32> W;
-    return (int64_t)carve_ppo<F32>(c, *actor, *critic, N, W);
-  }
-  PpoWs<BF16> W;
-  return (int64_t)carve_ppo<BF16>(c, *actor, *critic, N, W);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    PpoWs<decltype(p)> W;
+    return carve_ppo<decltype(p)>(c, *actor, *critic, N, W);
+  });
 }
 
 template <class P>
@@ -1712,6 +1757,10 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
   const PackLayout LA = pack_layout<P>(a, 0), LC = pack_layout<P>(cr, 0);
   const int Kft = pcfg.ft_denoising_steps;
+  // (the row builders below zero both networks' counters; only the actor's tail has a side stream)
+  const int dobs_a = oio && oio->d_obs_actor ? DPPO_ROUTE_IN_DOBS : 0, dobs_c = oio && oio->d_obs_critic ? DPPO_ROUTE_IN_DOBS : 0;
+  if (int e = plan_route<P>(a, N, Kft, DPPO_ROUTE_IN_ZEROED | DPPO_ROUTE_IN_SIDE | dobs_a, W.A)) return e;
+  if (int e = plan_route<P>(cr, N, Kft, DPPO_ROUTE_IN_ZEROED | dobs_c, W.C)) return e;
   // The critic pipeline (rows -> forward -> value loss -> backward -> weight gradients) and the actor pipeline (rows ->
   // advantage moments -> forward -> policy loss -> ...) share nothing but the call's inputs: one fork at entry, one join
   // at the end.  A cross-stream event hop costs 10-17 us of device idle time; at entry it hides behind the actor's row
@@ -1723,17 +1772,15 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   memset(&br, 0, sizeof(br));
   br.zero_b = W.moments, br.n_zero_b = 32;  // zeroed by the row builder (every statistic has one owner launch that writes it)
   // post_reduce_kernel's arrival counter and, behind it, tail_post_kernel's (both networks')
-  br.zero_a = W.A.post_counter, br.n_zero_a = POST_COUNTER_DOUBLES, W.A.post_zeroed = true;
+  br.zero_a = W.A.post_counter, br.n_zero_a = POST_COUNTER_DOUBLES;
   br.zero_c = W.C.post_counter, br.n_zero_c = POST_COUNTER_DOUBLES;
-  W.A.dw0 = dw0_ok<P>(a, N, LA, Kft, W.A, oio && oio->d_obs_actor);
-  W.C.dw0 = dw0_ok<P>(cr, N, LC, Kft, W.C, oio && oio->d_obs_critic);
   if (Kft <= 1024) br.loss_tab = W.loss_tab, br.pcfg = pcfg;
   br.inds = inds, br.kinds = kinds, br.chains = chains_k, br.obs = obs_k, br.temb = (const float*)(ak + LA.temb);
   br.ksteps = ksteps;
   br.Kft = Kft, br.AF = a.act_flat, br.td = a.time_dim, br.cond = a.cond_dim, br.M = N;
   br.inA = W.A.in, br.KpA = LA.Kp0, br.inC = W.C.in, br.KpC = LC.Kp0, br.brow = W.brow, br.krow = W.krow;
   br.obs_in_a = a.cond_hidden > 0 ? 0 : 1;  // with cond_mlp the encoder fills the state columns (from the critic's obs rows)
-  br.onehot0 = temb_onehot_col<P>(a, LA, Kft, W.A);
+  br.onehot0 = W.A.route.onehot_col;
   // advantage moments as riders of the actor's row builder (knob 36): no launch between the rows and the actor's forward
   const bool mom_rider = gmom == nullptr && (g_mom_rider == 1 || (g_mom_rider == 0 && N <= MOM_RIDER_MAX_N));
   if (mom_rider) br.mom_adv = adv_k, br.mom_out = W.moments, br.n_zero_b = 8;  // (block 0 must not zero the riders' slots, [8, ...))
@@ -1763,7 +1810,6 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   if (mom_rider) la.mom_blocks = ADV_RIDER_BLOCKS, la.moments_out = W.moments;
   la.tab = Kft <= 1024 ? W.loss_tab : nullptr;
   la.d_eps = W.A.d_out, la.ldde = LA.Kpo, la.d_v = W.C.d_out, la.lddv = LC.Kpo, la.stats = stats;
-  const bool fuse_bout = false;  // out-layer bias gradients come from the fused backward's d_out column sums
   const bool two_streams = s2 != s;
   // critic half
   mlp_forward<P>(cr, cp, ck, LC, N, W.C, true, s2);
@@ -1776,7 +1822,7 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
     la.brow = W.brow, la.n_count = 0;
     // (no tail stream of its own: a fork from a forked stream crashes hipGraph capture on ROCm 7.0 at capture end, and
     // the critic's tail is one 10-us reduction)
-    mlp_backward<P>(cr, cp, ck, LC, N, W.C, cgrad, nullptr, nullptr, 0, s2, fuse_bout, -1, &lv);
+    mlp_backward<P>(cr, cp, ck, LC, N, W.C, cgrad, nullptr, nullptr, 0, s2, &lv);
     if (oio && oio->d_obs_critic) obs_grad<P>(cr, cp, N, W.C, oio->d_obs_critic, s2);
     // data parallel: everything that writes critic_grad is enqueued on s2 -- the caller queues the critic slice's
     // all-reduce behind it THERE, so that it runs while the actor's forward / backward still occupy the main stream
@@ -1787,12 +1833,12 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   la.part = two_streams ? 1 : 3, la.partial = W.loss_partial;
   launch_ppo_loss<P>(la, s);
   if (!two_streams) {
-    mlp_backward<P>(cr, cp, ck, LC, N, W.C, cgrad, nullptr, nullptr, 0, s, fuse_bout, -1);
+    mlp_backward<P>(cr, cp, ck, LC, N, W.C, cgrad, nullptr, nullptr, 0, s);
     if (oio && oio->d_obs_critic) obs_grad<P>(cr, cp, N, W.C, oio->d_obs_critic, s);
     if (hook && hook->critic_grads_enqueued) hook->critic_grads_enqueued(hook->user, (dppo_stream_t)s);
   }
   if (two_streams && g_early_join) W.A.join_s[W.A.n_join] = s2, W.A.join_idx[W.A.n_join++] = 0;
-  mlp_backward<P>(a, ap, ak, LA, N, W.A, agrad, W.krow, ksteps, Kft, s, fuse_bout, 1, &la);
+  mlp_backward<P>(a, ap, ak, LA, N, W.A, agrad, W.krow, ksteps, Kft, s, &la);
   if (a.cond_hidden > 0) cond_backward<P>(a, ap, ak, LA, N, W.A, W.A.dh0_final, W.C.in, agrad, s);
   if (oio && oio->d_obs_actor) obs_grad<P>(a, ap, N, W.A, oio->d_obs_actor, s);
   if (!(two_streams && g_early_join) || W.A.n_join > 0) join_side(s, s2);  // (n_join > 0: the backward never flushed)
@@ -1907,14 +1953,11 @@ static size_t carve_gauss(Carver& c, const dppo_net_desc& a, const dppo_net_desc
 int64_t dppo_gaussian_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* critic, int prec, int64_t N) {
   if (check_net(actor) || (critic && check_net(critic)) || check_prec(prec)) return -1;
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  Carver c{nullptr, 0, 0};
-  double *m, *sc, *pa;
-  if (prec == DPPO_PREC_F32) {
-    MlpBufs<F32> A, Cb;
-    return (int64_t)carve_gauss<F32>(c, *actor, critic, N, critic != nullptr, A, Cb, m, sc, pa);
-  }
-  MlpBufs<BF16> A, Cb;
-  return (int64_t)carve_gauss<BF16>(c, *actor, critic, N, critic != nullptr, A, Cb, m, sc, pa);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    MlpBufs<decltype(p)> A, Cb;
+    double *m, *sc, *pa;
+    return carve_gauss<decltype(p)>(c, *actor, critic, N, critic != nullptr, A, Cb, m, sc, pa);
+  });
 }
 template <class P>
 static int gauss_infer_impl(const dppo_net_desc& d, const float* prm, const char* pk, const dppo_gaussian_cfg& cfg,
@@ -1996,9 +2039,9 @@ static int gauss_ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const
   g.partial = partial, g.stats = stats, g.logvar_grad = lvgrad;
   launch_gauss_loss<P>(g, s);
   s2 = fork_side(s);
-  mlp_backward<P>(cr, cp, ck, LC, N, Cb, cgrad, nullptr, nullptr, 0, s2, false, -1);
+  mlp_backward<P>(cr, cp, ck, LC, N, Cb, cgrad, nullptr, nullptr, 0, s2);
   if (oio && oio->d_obs_critic) obs_grad<P>(cr, cp, N, Cb, oio->d_obs_critic, s2);
-  mlp_backward<P>(a, ap, ak, LA, N, A, agrad, nullptr, nullptr, 0, s, false, 1);
+  mlp_backward<P>(a, ap, ak, LA, N, A, agrad, nullptr, nullptr, 0, s);
   if (oio && oio->d_obs_actor) obs_grad<P>(a, ap, N, A, oio->d_obs_actor, s);
   if (s2 != s) join_side(s, s2);
   return check_launch();
@@ -2059,14 +2102,11 @@ int dppo_gaussian_ppo_loss_fwd_bwd_obs(const dppo_net_desc* actor, const dppo_ne
 int64_t dppo_gaussian_bc_workspace_bytes(const dppo_net_desc* actor, int prec, int64_t N) {
   if (check_net(actor) || check_prec(prec)) return -1;
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  Carver c{nullptr, 0, 0};
-  double *m, *sc, *pa;
-  if (prec == DPPO_PREC_F32) {
-    MlpBufs<F32> A, Cb;
-    return (int64_t)carve_gauss<F32>(c, *actor, nullptr, N, true, A, Cb, m, sc, pa);
-  }
-  MlpBufs<BF16> A, Cb;
-  return (int64_t)carve_gauss<BF16>(c, *actor, nullptr, N, true, A, Cb, m, sc, pa);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    MlpBufs<decltype(p)> A, Cb;
+    double *m, *sc, *pa;
+    return carve_gauss<decltype(p)>(c, *actor, nullptr, N, true, A, Cb, m, sc, pa);
+  });
 }
 template <class P>
 static int gauss_bc_impl(const dppo_net_desc& a, const float* ap, const char* ak, const dppo_gaussian_cfg& cfg,
@@ -2085,7 +2125,7 @@ static int gauss_bc_impl(const dppo_net_desc& a, const float* ap, const char* ak
   g.cfg = cfg, g.mean_pre = A.out, g.ldm = A.ldout, g.logvar = logvar, g.actions = actions, g.N = N, g.AF = a.out_dim;
   g.d_mean = A.d_out, g.lddm = LA.Kpo, g.partial = partial, g.logvar_grad = lvgrad, g.ent_coef = ent_coef, g.bc_out = out;
   launch_gauss_nll<P>(g, s);
-  mlp_backward<P>(a, ap, ak, LA, N, A, agrad, nullptr, nullptr, 0, s, false, 1);
+  mlp_backward<P>(a, ap, ak, LA, N, A, agrad, nullptr, nullptr, 0, s);
   return check_launch();
 }
 int dppo_gaussian_bc_loss_fwd_bwd(const dppo_net_desc* actor, int prec, const float* params, const void* packed,
@@ -2138,15 +2178,11 @@ int64_t dppo_gmm_workspace_bytes(const dppo_net_desc* mean, const dppo_net_desc*
                                  int64_t N) {
   if (check_net(mean) || check_net(weights) || (critic && check_net(critic)) || check_prec(prec)) return -1;
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  Carver c{nullptr, 0, 0};
-  double *m, *sc, *pa;
-  const int K = GMM_MAX_MODES * 64;
-  if (prec == DPPO_PREC_F32) {
-    MlpBufs<F32> Am, Aw, Cb;
-    return (int64_t)carve_gmm<F32>(c, *mean, *weights, critic, N, K, critic != nullptr, Am, Aw, Cb, m, sc, pa);
-  }
-  MlpBufs<BF16> Am, Aw, Cb;
-  return (int64_t)carve_gmm<BF16>(c, *mean, *weights, critic, N, K, critic != nullptr, Am, Aw, Cb, m, sc, pa);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    MlpBufs<decltype(p)> Am, Aw, Cb;
+    double *m, *sc, *pa;
+    return carve_gmm<decltype(p)>(c, *mean, *weights, critic, N, GMM_MAX_MODES * 64, critic != nullptr, Am, Aw, Cb, m, sc, pa);
+  });
 }
 template <class P>
 static int gmm_infer_impl(const dppo_net_desc& am, const dppo_net_desc& aw, const float* mp, const char* mk, const float* wp,
@@ -2231,9 +2267,9 @@ static int gmm_ppo_impl(const dppo_net_desc& am, const dppo_net_desc& aw, const 
   g.partial = partial, g.stats = stats, g.logvar_grad = lvgrad;
   launch_gmm_loss<P>(g, s);
   s2 = fork_side(s);
-  mlp_backward<P>(cr, cp, ck, LC, N, Cb, cgrad, nullptr, nullptr, 0, s2, false, -1);
-  mlp_backward<P>(am, mp, mk, LM, N, Am, mgrad, nullptr, nullptr, 0, s, false, 1);
-  mlp_backward<P>(aw, wp, wk, LW, N, Aw, wgrad, nullptr, nullptr, 0, s, false, 1);
+  mlp_backward<P>(cr, cp, ck, LC, N, Cb, cgrad, nullptr, nullptr, 0, s2);
+  mlp_backward<P>(am, mp, mk, LM, N, Am, mgrad, nullptr, nullptr, 0, s);
+  mlp_backward<P>(aw, wp, wk, LW, N, Aw, wgrad, nullptr, nullptr, 0, s);
   if (s2 != s) join_side(s, s2);
   return check_launch();
 }
@@ -2266,15 +2302,11 @@ int dppo_gmm_ppo_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* we
 int64_t dppo_gmm_bc_workspace_bytes(const dppo_net_desc* mean, const dppo_net_desc* weights, int prec, int64_t N) {
   if (check_net(mean) || check_net(weights) || check_prec(prec)) return -1;
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  Carver c{nullptr, 0, 0};
-  double *m, *sc, *pa;
-  const int K = GMM_MAX_MODES * 64;
-  if (prec == DPPO_PREC_F32) {
-    MlpBufs<F32> Am, Aw, Cb;
-    return (int64_t)carve_gmm<F32>(c, *mean, *weights, nullptr, N, K, true, Am, Aw, Cb, m, sc, pa);
-  }
-  MlpBufs<BF16> Am, Aw, Cb;
-  return (int64_t)carve_gmm<BF16>(c, *mean, *weights, nullptr, N, K, true, Am, Aw, Cb, m, sc, pa);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    MlpBufs<decltype(p)> Am, Aw, Cb;
+    double *m, *sc, *pa;
+    return carve_gmm<decltype(p)>(c, *mean, *weights, nullptr, N, GMM_MAX_MODES * 64, true, Am, Aw, Cb, m, sc, pa);
+  });
 }
 template <class P>
 static int gmm_bc_impl(const dppo_net_desc& am, const dppo_net_desc& aw, const float* mp, const char* mk, const float* wp,
@@ -2299,8 +2331,8 @@ static int gmm_bc_impl(const dppo_net_desc& am, const dppo_net_desc& aw, const f
   g.partial = partial, g.logvar_grad = lvgrad, g.bc_out = out;
   launch_gmm_nll<P>(g, s);
   s2 = fork_side(s);
-  mlp_backward<P>(aw, wp, wk, LW, N, Aw, wgrad, nullptr, nullptr, 0, s2, false, -1);
-  mlp_backward<P>(am, mp, mk, LM, N, Am, mgrad, nullptr, nullptr, 0, s, false, 1);
+  mlp_backward<P>(aw, wp, wk, LW, N, Aw, wgrad, nullptr, nullptr, 0, s2);
+  mlp_backward<P>(am, mp, mk, LM, N, Am, mgrad, nullptr, nullptr, 0, s);
   if (s2 != s) join_side(s, s2);
   return check_launch();
 }
@@ -2359,13 +2391,10 @@ static size_t carve_unet_ppo(Carver& c, const dppo_unet_desc& u, const dppo_net_
 int64_t dppo_unet_ppo_workspace_bytes(const dppo_unet_desc* actor, const dppo_net_desc* critic, int prec, int64_t N) {
   if (unet_check_desc(actor) || check_net(critic) || check_prec(prec)) return -1;
   if (N < 2 || N > (1 << 24)) return fail(-1, "N out of range");
-  Carver c{nullptr, 0, 0};
-  if (prec == DPPO_PREC_F32) {
-    UnetPpoWs<F32> W;
-    return (int64_t)carve_unet_ppo<F32>(c, *actor, critic, N, W);
-  }
-  UnetPpoWs<BF16> W;
-  return (int64_t)carve_unet_ppo<BF16>(c, *actor, critic, N, W);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    UnetPpoWs<decltype(p)> W;
+    return carve_unet_ppo<decltype(p)>(c, *actor, critic, N, W);
+  });
 }
 template <class P>
 static int unet_ppo_impl(const dppo_unet_desc& u, const dppo_net_desc& cr, const float* ap, const char* ak, const float* cp,
@@ -2412,7 +2441,7 @@ static int unet_ppo_impl(const dppo_unet_desc& u, const dppo_net_desc& cr, const
   la.part = 3, la.partial = W.loss_partial;
   launch_ppo_loss<P>(la, s);
   s2 = fork_side(s);
-  mlp_backward<P>(cr, cp, ck, LC, N, W.C, cgrad, nullptr, nullptr, 0, s2, false, -1, &la);
+  mlp_backward<P>(cr, cp, ck, LC, N, W.C, cgrad, nullptr, nullptr, 0, s2, &la);
   if (oio && oio->d_obs_critic) obs_grad<P>(cr, cp, N, W.C, oio->d_obs_critic, s2);
   unet_trainer_backward<P>(T, W.d_eps, W.ldde, agrad, oio ? oio->d_obs_actor : nullptr);
   unet_trainer_free<P>(T);
@@ -2477,13 +2506,10 @@ int dppo_unet_ppo_loss_fwd_bwd_obs(const dppo_unet_desc* actor, const dppo_net_d
 int64_t dppo_unet_denoise_mse_workspace_bytes(const dppo_unet_desc* net, int prec, int64_t N) {
   if (unet_check_desc(net) || check_prec(prec)) return -1;
   if (N < 1 || N > (1 << 24)) return fail(-1, "N out of range");
-  Carver c{nullptr, 0, 0};
-  if (prec == DPPO_PREC_F32) {
-    UnetPpoWs<F32> W;
-    return (int64_t)carve_unet_ppo<F32>(c, *net, nullptr, N, W);
-  }
-  UnetPpoWs<BF16> W;
-  return (int64_t)carve_unet_ppo<BF16>(c, *net, nullptr, N, W);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    UnetPpoWs<decltype(p)> W;
+    return carve_unet_ppo<decltype(p)>(c, *net, nullptr, N, W);
+  });
 }
 template <class P>
 static int unet_mse_impl(const dppo_unet_desc& u, const float* prm, const char* pk, const dppo_step* tsteps, int n_time,
@@ -2585,13 +2611,10 @@ static int64_t idql_ws_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int
                              bool train_v) {
   if ((v ? check_idql_pair(q, v) : check_idql_q(q)) || check_prec(prec)) return -1;
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  Carver c{nullptr, 0, 0};
-  if (prec == DPPO_PREC_F32) {
-    IdqlWs<F32> W;
-    return (int64_t)carve_idql<F32>(c, *q, v, N, double_q != 0, train_q, train_v, W);
-  }
-  IdqlWs<BF16> W;
-  return (int64_t)carve_idql<BF16>(c, *q, v, N, double_q != 0, train_q, train_v, W);
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    IdqlWs<decltype(p)> W;
+    return carve_idql<decltype(p)>(c, *q, v, N, double_q != 0, train_q, train_v, W);
+  });
 }
 int64_t dppo_idql_v_loss_workspace_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int prec, int64_t N, int double_q) {
   return idql_ws_bytes(q, v, prec, N, double_q, false, true);
@@ -2637,7 +2660,7 @@ static int idql_v_impl(const dppo_net_desc& q, const dppo_net_desc& v, const flo
   l.q1 = W.Q1.out, l.q2 = twin ? W.Q2.out : nullptr, l.ldq = W.Q1.ldout, l.v = W.V.out, l.ldv = W.V.ldout, l.N = N;
   l.tau = (float)tau, l.d_a = W.V.d_out, l.ldd = LV.Kpo, l.adv_out = adv, l.partial = W.partial, l.stats = stats;
   launch_idql_v_loss<P>(l, s);
-  mlp_backward<P>(v, vp, vk, LV, N, W.V, vgrad, nullptr, nullptr, 0, s, false, 1);
+  mlp_backward<P>(v, vp, vk, LV, N, W.V, vgrad, nullptr, nullptr, 0, s);
   return check_launch();
 }
 int dppo_idql_v_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int prec, const float* target_q_params,
@@ -2690,9 +2713,9 @@ static int idql_q_impl(const dppo_net_desc& q, const dppo_net_desc& v, const flo
   launch_idql_q_loss<P>(l, s);
   if (twin) {
     s2 = fork_side(s, 0);
-    mlp_backward<P>(q, qp + nq, qk2, LQ, N, W.Q2, qgrad + nq, nullptr, nullptr, 0, s2, false, -1);
+    mlp_backward<P>(q, qp + nq, qk2, LQ, N, W.Q2, qgrad + nq, nullptr, nullptr, 0, s2);
   }
-  mlp_backward<P>(q, qp, qk1, LQ, N, W.Q1, qgrad, nullptr, nullptr, 0, s, false, 1);
+  mlp_backward<P>(q, qp, qk1, LQ, N, W.Q1, qgrad, nullptr, nullptr, 0, s);
   if (s2 != s) join_side(s, s2, 0);
   return check_launch();
 }
@@ -2908,6 +2931,28 @@ int dppo_tune_set(int knob, int value) {
     default: break;
   }
   return fail(-1, "unknown tuning knob %d", knob);
+}
+
+template <class P>
+static int route_mask(const dppo_net_desc& d, int64_t M, int Kft, int flags, int* mask_out) {
+  Carver c{nullptr, 0, 0};
+  MlpBufs<P> B;
+  carve_mlp<P>(c, d, M, true, true, B);
+  if (int e = plan_route<P>(d, M, Kft, flags, B)) return e;
+  const BwdRoute& R = B.route;
+  const bool bit[12] = {R.fused,   R.one_block,    R.lowrank,   R.merged,   R.onehot_col >= 0, R.dw0,
+                        R.dw0_nhot > 0, R.dw0_round, R.need_aux, R.side_tail, R.tail_post, R.post_one};
+  *mask_out = 0;
+  for (int i = 0; i < 12; ++i) *mask_out |= bit[i] ? 1 << i : 0;
+  return 0;
+}
+int dppo_backward_route(const dppo_net_desc* net, int prec, int64_t M, int Kft, int flags, int* mask_out) {
+  if (int e = check_net(net)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!mask_out || M < 1 || M > 0x7fffffff || Kft < 0 || Kft > 1024 || (flags & ~7)) return fail(-1, "bad argument");
+#define CALL(P) route_mask<P>(*net, M, Kft, flags, mask_out)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
 }
 
 int dppo_gemm_nt_raw(int prec, const void* X, const void* W, const float* bias, int64_t M, int N, int Kp, float* out_f32,

@@ -223,6 +223,7 @@ SYMBOLS = {
     "dppo_probe_collect_bytes": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]),
     "dppo_tune_set": (_I, [_I, _I]),
+    "dppo_backward_route": (_I, [_ND, _I, _L, _I, _I, C.POINTER(C.c_int)]),
     "dppo_gemm_nt_raw": (_I, [_I, _P, _P, _P, _L, _I, _I, _P, _P, _I, _I, _P]),
     "dppo_gemm_tn_raw": (_I, [_I, _P, _I, _I, _P, _I, _I, _L, _I, _P, _P, _P]),
     "dppo_gemm_nt_desc_raw": (_I, [_I, C.POINTER(GemmNTDesc), _P]),

@@ -468,7 +468,13 @@ int dppo_probe_collect_bytes(double* total_ms_host, int* launches_host, double* 
  *         of them pays)
  * knob 8: timing experiments (results are wrong while set): bit 0 / 1 the fused backward without its gradient stores / derivative
  *         fetch, bit 2 / 3 / 4 the reduction launch behind the weight-gradient GEMMs without its slab reductions / bias sums / loss
- *         statistics (tools/tail_reduce_parts.sh)
+ *         statistics (tools/tail_reduce_parts.sh), bit 5 no dh_0 store and no first-layer product (the bound of knob 37).  Bits 0
+ *         and 5 (values 1 and 32) cannot run with the in-kernel first-layer gradient: a call whose route takes it
+ *         (DPPO_ROUTE_DW0) fails with a message while one of them is set -- set knob 37 to 0 first.
+ *
+ *         Bits 2, 3 and 4 also change the ROUTE, not only a launch's arguments: the reduction they cut parts out of is the one
+ *         launch behind the GEMMs, so while one of them is set the side tail (knob 38) and with it knob 41's launch are off
+ *         (DPPO_ROUTE_SIDE_TAIL / _TAIL_POST clear) -- decided where the route is planned, no stage looks at them for that
  * knob 5: weight-gradient GEMM kernel, 0 = register-staged (default), 1..8 = an LDS-DMA ring configuration, -1 = by shape
  * knob 6: thin (512 x 64) weight-gradient tiles on (default 1) / off
  * knob 11: time-embedding gradient from a one-hot of the denoising step in the K padding of the actor's input rows, so
@@ -519,6 +525,27 @@ int dppo_probe_collect_bytes(double* total_ms_host, int* launches_host, double* 
  * retired (experiments that were measured, lost and removed with their code): 9, 10, 31, 32, 33, 34, 35,
  *          39, 40 -- setting one of them, like an unknown number, returns an error */
 int dppo_tune_set(int knob, int value);
+/* Which path the fused backward of `net` takes for M rows and Kft denoising steps under the current knobs: pure host code, no
+ * GPU needed.  `flags` says what the caller brings (DPPO_ROUTE_IN_*): the PPO entries pass ZEROED | SIDE for the actor and ZEROED
+ * for the critic, behaviour cloning and the denoising loss pass SIDE, every other entry 0 (and Kft = 0); DOBS where d_obs is
+ * asked for.  *mask_out gets one DPPO_ROUTE_* bit per decision.  Returns 0, or an error for a bad argument or a knob
+ * combination that the route refuses (knob 8). */
+#define DPPO_ROUTE_IN_ZEROED 1 /* the call's row builder zeroes the arrival counters of the post-reduce kernels */
+#define DPPO_ROUTE_IN_DOBS 2   /* the caller wants d loss / d observation (needs dh_0 in memory) */
+#define DPPO_ROUTE_IN_SIDE 4   /* the backward's tail may run on the library's second side stream */
+#define DPPO_ROUTE_FUSED 0x001     /* fused row-tile backward (else the layered GEMM chain, and no other bit means anything) */
+#define DPPO_ROUTE_ONE_BLOCK 0x002 /* the one-block backward kernel (knobs 23, 30) */
+#define DPPO_ROUTE_LOWRANK 0x004   /* top block's dW2 from the rank-out_dim factorisation (knobs 16, 30) */
+#define DPPO_ROUTE_MERGED 0x008    /* merged forward: dWout rebuilt from two thin products (knob 22) */
+#define DPPO_ROUTE_ONEHOT 0x010    /* one-hot step columns in the input rows carry the time-embedding gradient (knob 11) */
+#define DPPO_ROUTE_DW0 0x020       /* first-layer weight gradient inside the backward kernel (knob 37) */
+#define DPPO_ROUTE_DW0_NHOT 0x040  /* ... with one-hot columns among its 32 */
+#define DPPO_ROUTE_DW0_ROUND 0x080 /* ... the last of which did not fit and is rebuilt from the bias gradient */
+#define DPPO_ROUTE_NEED_AUX 0x100  /* time-embedding gradient as a pass of its own over dh_0 */
+#define DPPO_ROUTE_SIDE_TAIL 0x200 /* the kernel-fed reductions on the side stream under the GEMMs (knob 38) */
+#define DPPO_ROUTE_TAIL_POST 0x400 /* slab reductions and post-reduce parts behind the GEMMs in one launch (knob 41) */
+#define DPPO_ROUTE_POST_ONE 0x800  /* everything behind the slab reduction in one launch (knob 18) */
+int dppo_backward_route(const dppo_net_desc* net, int prec, int64_t M, int Kft, int flags, int* mask_out);
 /* one bare layer GEMM: out[M][ldo] = act(X[M][Kp] . W[N][Kp]^T + bias) with elem = prec operands;
  * out_f32 and/or out_elem may be NULL; ldo >= round_up(N,16) */
 int dppo_gemm_nt_raw(int prec, const void* X, const void* W, const float* bias, int64_t M, int N, int Kp,

@@ -597,7 +597,8 @@ def test_fused_path_matches_layered_path(prec, tol, sname):
 @pytest.mark.parametrize("sname,knob", [("hopper", 22), ("can", 22), ("halfcheetah", 22), ("can_relu", 22), ("hopper", 23),
                                         ("can", 23), ("square_like", 23), ("hopper", 25), ("halfcheetah", 25), ("hopper", 36),
                                         ("can", 36), ("hopper", 37), ("halfcheetah", 37), ("can", 37), ("hopper", 38),
-                                        ("hopper", 41)])
+                                        ("hopper", 41), ("hopper", 11), ("hopper", 12), ("hopper", 14), ("hopper", 16),
+                                        ("hopper", 18), ("can", 16), ("can", 18)])
 def test_one_block_kernels_match_the_general_ones(prec, tol, sname, knob):
     _one_block_ab(prec, tol, sname, knob)
 
@@ -622,7 +623,10 @@ def _one_block_ab(prec, tol, sname, knob, N=6500, Kft=10):
     first layer's weight gradient accumulated inside the one-block backward (dh_0 never stored; hopper: actor and critic, the
     others: the critic).  Knob 38: with it, the reductions the backward kernel feeds and the time-embedding gradient on a side
     stream under the weight-gradient GEMMs.  Knob 41: the GEMMs' slab reductions and the post-reduce parts behind them in one
-    launch.  Same log-probs, values, loss
+    launch.  Knobs 11, 12, 14, 16, 18: the time-embedding gradient as a pass of its own, one launch per weight-gradient GEMM,
+    side streams joined at the call's end, the top block's dW2 as an H x H GEMM (and with it the general backward kernel), the
+    post-reduce parts as separate launches -- each of them also takes the in-kernel dW0's conditions away or, for 14, the side
+    tail's (csrc/api.hip plan_route(); ``dppo_backward_route`` reports the route).  Same log-probs, values, loss
     statistics and gradients -- tensor by tensor -- as the general kernels."""
     from dppo_amd import hip
     lib = hip.load()

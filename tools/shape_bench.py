@@ -3,8 +3,10 @@
 bench.py's terms, not bench lines): timing only, random weights, synthetic rollout.
 
     python tools/shape_bench.py [--shapes hopper,can,square,transport,furniture] [--prec bf16] [--batch 7500]
+    python tools/shape_bench.py --route     # no GPU: only print which path each shape's update takes (dppo_backward_route)
 """
 import argparse
+import ctypes as C
 import os
 import sys
 import time
@@ -29,8 +31,21 @@ SHAPES = {
 }
 
 
+ROUTE_BITS = ("fused", "one_block", "lowrank", "merged", "onehot", "dw0", "dw0_nhot", "dw0_round", "need_aux", "side_tail",
+              "tail_post", "post_one")  # DPPO_ROUTE_* of include/dppo_hip.h, bit 0 first
+
+
+def route_line(net, prec, N, Kft, flags):
+    from dppo_amd import hip
+    mask = C.c_int(0)
+    hip.check(hip.load().dppo_backward_route(C.byref(net.net_desc()), hip.PREC_BY_NAME[prec], N, Kft, flags, C.byref(mask)),
+              "dppo_backward_route")
+    return " ".join(b for i, b in enumerate(ROUTE_BITS) if mask.value >> i & 1) or "layered"
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--route", action="store_true", help="print the backward route of each shape's PPO update and exit (no GPU)")
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--prec", default="bf16")
     ap.add_argument("--steps", type=int, default=10)
@@ -50,6 +65,10 @@ def main():
                              cond_mlp_dims=c["cm"], activation_type=c["fn"], use_layernorm=c["ln"], residual_style=True,
                              precision=args.prec)
         critic = CriticObs(cond_dim=c["obs"], mlp_dims=c["cdims"], activation_type="Mish", residual_style=True, precision=args.prec)
+        if args.route:  # the PPO entry's flags: counters zeroed for both networks, the side stream for the actor's tail
+            print(f"{name:10s} N={c['batch']:6d} actor:  {route_line(actor, args.prec, c['batch'], c['Kft'], 1 | 4)}\n"
+                  f"{'':19s} critic: {route_line(critic, args.prec, c['batch'], c['Kft'], 1)}")
+            continue
         kw = dict(use_ddim=True, ddim_steps=c["Kft"], eta=EtaFixed(base_eta=1.0)) if c["ddim"] else {}
         m = PPODiffusion(actor=actor, critic=critic, ft_denoising_steps=c["Kft"], horizon_steps=c["ta"], obs_dim=c["obs"],
                          action_dim=c["act"], denoising_steps=c["K"], device=str(dev), gamma_denoising=0.99, clip_ploss_coef=0.01,
