@@ -545,9 +545,14 @@ static void cond_encode(const dppo_net_desc& d, const float* prm, const char* pk
 
 template <class P>
 static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
-                        MlpBufs<P>& B, bool keep, hipStream_t s) {
+                        MlpBufs<P>& B, bool keep, hipStream_t s, const LossArgs* fuse_loss = nullptr) {
+  // fuse_loss: the policy half of the PPO loss in the forward kernel's epilogue (fuse_loss_ok() held: the merged fused kernel runs)
   const ParamLayout pl = param_layout(d);
   const int H = d.hidden, nb = d.n_blocks;
+  if (fuse_loss != nullptr && !(fused_ok<P>(d) && B.route.merged)) {
+    g_fused_fault = -8;  // (fuse_loss_ok() and this function disagree)
+    return;
+  }
   if (fused_ok<P>(d)) {
     FusedFwdArgs f;
     memset(&f, 0, sizeof(f));
@@ -574,7 +579,7 @@ static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk
       f.ostream0 = (const u32x4*)(pk + L.ostream0), f.ostream2 = (const u32x4*)(pk + L.ostream2);
       f.cbias2 = (const float*)(pk + L.cbias2);
     }
-    g_fused_fault = launch_fused_forward<P>(d, f, s);
+    g_fused_fault = launch_fused_forward<P>(d, f, s, fuse_loss);
     return;
   }
   if (d.plain) {  // x -> act(W0 x) -> act(W_b .) ... -> Wout .   (pre-activations kept for the backward: hpre[0], z1[b])
@@ -648,11 +653,11 @@ static SideStream* side_stream(int idx) {
   }
   return &t;
 }
+static bool side_stream_on(int idx) { return (((g_overlap == 1 ? 7 : g_overlap >> 1) >> idx) & 1) != 0; }
 static hipStream_t fork_side(hipStream_t main, int idx = 0) {  // returns the stream the independent part should use
   // g_overlap: 0 = none, 1 = every side stream, other values = bit mask over the side-stream indices, shifted by one
   // (e.g. 2 = the critic pipeline's only)
-  const int mask = g_overlap == 1 ? 7 : g_overlap >> 1;
-  SideStream* t = ((mask >> idx) & 1) ? side_stream(idx) : nullptr;
+  SideStream* t = side_stream_on(idx) ? side_stream(idx) : nullptr;
   if (t == nullptr) return main;
   (void)hipEventRecord(t->fork, main);
   (void)hipStreamWaitEvent(t->s, t->fork, 0);
@@ -685,6 +690,7 @@ static int g_mom_rider = 0;  // tuning knob 36: the minibatch's advantage moment
                               // serial order, profiles/r03_moments_rider_ab.txt); at BASELINE configs[2]'s 7,500 the step is a chain of
                               // launches and one fewer is 0.186 -> 0.180 ms
 constexpr int64_t MOM_RIDER_MAX_N = 16384;
+static bool mom_rider_on(int64_t N, bool has_gmom) { return !has_gmom && (g_mom_rider == 1 || (g_mom_rider == 0 && N <= MOM_RIDER_MAX_N)); }
 // Time-embedding gradient through the first layer's weight-gradient GEMM: with a one-hot of the row's denoising step k in
 // the K padding of the input rows, dW0's extra columns are S[h][k] = sum over the rows of step k of dh0[row][h], and
 // d loss / d temb[k] = W0[:, temb columns]^T S[:, k] -- no second pass over dh0, no segmented reduction (tuning knob 11).
@@ -1744,6 +1750,20 @@ int64_t dppo_ppo_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc
   });
 }
 
+// Tuning knob 42: the policy half of the PPO loss in the epilogue of the actor's fused forward, spread over the workgroup
+// (loss_dev.h; fused.hip, LOSSF): no loss launch between the actor's forward and backward, the forward's eps tile never goes to
+// HBM.  What takes it (everything else keeps the separate launch): bf16; the merged one-block forward with one out tile and
+// 64-row tiles (hidden 512, a head of at most 16 outputs = the action chunk, so cnt <= 16); the value half on the critic's own
+// stream; no advantage-moment riders (their partial sums are added by the loss launch's block 0).  The per-step tables in LDS
+// bound Kft at 64.  dppo_ppo_loss_route() exports the answer.
+static int g_fuse_loss = 1;
+template <class P>
+static bool fuse_loss_ok(const dppo_net_desc& d, int64_t N, bool has_gmom, bool two_streams, int Kft) {
+  if (!g_fuse_loss || P::ESIZE != 2 || !two_streams || mom_rider_on(N, has_gmom)) return false;
+  if (!fused_ok<P>(d) || !fused_can_merge<P>(d) || !fused_loss_shape(d, Kft)) return false;
+  return d.kind == 0 && d.out_dim == d.act_flat && d.act_flat <= 16 && pack_layout<P>(d, 0).Kpo % 8 == 0;
+}
+
 template <class P>
 static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float* ap, const char* ak, const float* cp,
                     const char* ck, const dppo_diffusion_cfg& dcfg, const dppo_ppo_cfg& pcfg, const dppo_step* ksteps,
@@ -1782,7 +1802,7 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   br.obs_in_a = a.cond_hidden > 0 ? 0 : 1;  // with cond_mlp the encoder fills the state columns (from the critic's obs rows)
   br.onehot0 = W.A.route.onehot_col;
   // advantage moments as riders of the actor's row builder (knob 36): no launch between the rows and the actor's forward
-  const bool mom_rider = gmom == nullptr && (g_mom_rider == 1 || (g_mom_rider == 0 && N <= MOM_RIDER_MAX_N));
+  const bool mom_rider = mom_rider_on(N, gmom != nullptr);
   if (mom_rider) br.mom_adv = adv_k, br.mom_out = W.moments, br.n_zero_b = 8;  // (block 0 must not zero the riders' slots, [8, ...))
   const float* obs_c = oio && oio->obs_critic ? oio->obs_critic : nullptr;  // the critic's own observation rows (pixel nets)
   const bool split = s2 != s || obs_c != nullptr;
@@ -1811,6 +1831,10 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
   la.tab = Kft <= 1024 ? W.loss_tab : nullptr;
   la.d_eps = W.A.d_out, la.ldde = LA.Kpo, la.d_v = W.C.d_out, la.lddv = LC.Kpo, la.stats = stats;
   const bool two_streams = s2 != s;
+  // the policy half of the loss in the actor forward's epilogue (knob 42): its arguments as the policy launch would get them
+  LossArgs lpol = la;
+  lpol.part = 1, lpol.partial = W.loss_partial;
+  const bool fuse_loss = fuse_loss_ok<P>(a, N, gmom != nullptr, two_streams, Kft);
   // critic half
   mlp_forward<P>(cr, cp, ck, LC, N, W.C, true, s2);
   if (two_streams) {
@@ -1829,9 +1853,9 @@ static int ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const float
     if (hook && hook->critic_grads_enqueued) hook->critic_grads_enqueued(hook->user, (dppo_stream_t)s2);
   }
   // actor half
-  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
+  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s, fuse_loss ? &lpol : nullptr);
   la.part = two_streams ? 1 : 3, la.partial = W.loss_partial;
-  launch_ppo_loss<P>(la, s);
+  if (!fuse_loss) launch_ppo_loss<P>(la, s);
   if (!two_streams) {
     mlp_backward<P>(cr, cp, ck, LC, N, W.C, cgrad, nullptr, nullptr, 0, s);
     if (oio && oio->d_obs_critic) obs_grad<P>(cr, cp, N, W.C, oio->d_obs_critic, s);
@@ -2928,6 +2952,7 @@ int dppo_tune_set(int knob, int value) {
     case 38: g_side_tail = value; return 0;         // with knob 37: what the backward kernel alone feeds runs on a side stream under the GEMMs (1, default) or behind them (0)
     case 39: case 40: return retired_knob(knob);
     case 41: g_tail_post = value; return 0;         // with knob 38: the GEMMs' slab reductions and the post-reduce parts behind them in one launch (1, default) or two (0)
+    case 42: g_fuse_loss = value; return 0;         // policy half of the PPO loss in the epilogue of the actor's fused forward where it qualifies (1, default) or always a launch (0)
     default: break;
   }
   return fail(-1, "unknown tuning knob %d", knob);
@@ -2953,6 +2978,16 @@ int dppo_backward_route(const dppo_net_desc* net, int prec, int64_t M, int Kft, 
 #define CALL(P) route_mask<P>(*net, M, Kft, flags, mask_out)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
+}
+
+int dppo_ppo_loss_route(const dppo_net_desc* actor, const dppo_net_desc* critic, int prec, int64_t N, int has_global_moments) {
+  if (int e = check_net(actor)) return e;
+  if (int e = check_net(critic)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (N < 2 || N > 0x7fffffff) return fail(-1, "N out of range");
+  // (the value half runs on the critic's stream whenever side stream 0 is on: ppo_impl's two_streams)
+  if (prec == DPPO_PREC_F32) return fuse_loss_ok<F32>(*actor, N, has_global_moments != 0, side_stream_on(0), 0) ? 1 : 0;
+  return fuse_loss_ok<BF16>(*actor, N, has_global_moments != 0, side_stream_on(0), 0) ? 1 : 0;
 }
 
 int dppo_gemm_nt_raw(int prec, const void* X, const void* W, const float* bias, int64_t M, int N, int Kp, float* out_f32,

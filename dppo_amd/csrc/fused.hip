@@ -5,6 +5,7 @@
 #include "gemm.h"
 #include "tile_ln.h"
 #include "pack_dev.h"
+#include "loss_dev.h"
 
 #ifndef DPPO_BWD_LATE
 #define DPPO_BWD_LATE 1
@@ -786,8 +787,21 @@ __global__ __launch_bounds__(512, 2 * OCC) void fused_forward_kernel(const Fused
 // The weight-gradient side (api.hip, mlp_backward): dWout = d_out^T h_1 is rebuilt from U = d_out^T x and T = d_out^T act(z1).
 // S1 > 0 (ring depth 4): the input tile's layer is walked as its S1 = ks0v <= 2 k-steps that hold data instead of the
 // padded four (CEngine); S1 = 0: the padded walk.
-template <class P, int TPW, int MR, int OT, int ACT, int S1>
-__device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a) {
+// LOSSF (bf16, OT = 1; training): the policy half of the PPO loss runs in the tile's epilogue (loss_dev.h) -- the tile's eps never
+// goes to HBM, there is no loss launch between the actor's forward and backward.  The epilogue is spread over the workgroup: wave w
+// owns samples 8 w .. 8 w + 7 of the tile, thread = (sample, slot), so its three phases need no workgroup barrier between them (LDS
+// executes a wave's instructions in order).  Each thread loads the chain pair and old log-probs of ITS elements (and lanes 0-7 their
+// sample's advantage) into registers behind the H-wide k-loop and waits for them in front of the second emit (the row / step
+// indices were staged with the input tile), so the ReLU kernels' epilogue has no vmcnt wait.  (DESIGN 13.10 has what the forms
+// measured: the LDS-DMA gather of the first form was 3-5 us slower; why is not isolated.)
+//   element phase, thread = (sample, slot): elements slot, slot + 8 below cnt -> clamped log-probs and gradient source in LDS;
+//   sample phase, lanes 0-7, one sample each: the two sums over j ascending, the row math, coef and the sample's four statistics to LDS;
+//   store phase, thread = (sample, chunk): the d loss / d eps row, 16 bytes per lane.
+// Behind the tile's last barrier waves 0-3 add the 64 samples' statistics, one statistic each, by ppo_loss_kernel's shuffle tree
+// -- a tile is 64 samples, the loss kernel's block -- and write la.partial[tile].
+template <class P, int TPW, int MR, int OT, int ACT, int S1, bool LOSSF>
+__device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a, const LossArgs& la) {
+  static_assert(!LOSSF || (OT == 1 && MR == 4 && TPW == 4 && S1 > 0 && P::ESIZE == 2), "fused policy loss: bf16, one out tile, 64-row tiles of H = 512");
   constexpr int PD = ring_depth<TPW, MR>(), ES = P::ESIZE, KB = P::KB;
   static_assert(S1 == 0 || PD == 4, "the compact walk is written for a ring of four positions");
   constexpr int H = 128 * TPW, KSH = H / KB, HRB = H * ES, MT = 16 * MR;
@@ -821,6 +835,20 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a)
   // the first pass runs late, in the second pass's phase (a partial result carried through the H-wide k-loop is 8-16 more
   // live registers in a kernel that has none to spare: 24-56 spilled), so the tile gets its own [MT][ks0v * 64 B] region
   char* xin = WIDE ? (char*)(w0cL + ks0v * OT * 64) : bufB;
+  // LOSSF, behind the fragments (fused_loss_lds()): per row the element offsets of its chain pair and of its old log-probs, then
+  // (sample's rollout row, step); the tile's per-sample statistics; the denoising steps; the loss's per-step table [2 Kft + 2] and the sample count.
+  // In buffer A behind the out-layer partials (dead from the barrier behind the second emit on): eps tile [MT][16] f32 at +16 KB,
+  // the element phase's three arrays [MT][LOSS_ROW] f32 at +40 KB, coef [MT] at +56 KB
+  long long* metaL = (long long*)(w0cL + ks0v * OT * 64);
+  double* statL = (double*)(metaL + 3 * MT);      // [MT][4]
+  float* stepL = (float*)(statL + 4 * MT);        // [Kft][LOSS_STEP]
+  float* tabL = stepL + (LOSSF ? la.pcfg.ft_denoising_steps * LOSS_STEP : 0);
+  float* epsL = (float*)(bufA + 16 * 1024);
+  float* lpnL = (float*)(bufA + 40 * 1024);
+  float* lpoL = lpnL + MT * LOSS_ROW;
+  float* gsL = lpoL + MT * LOSS_ROW;
+  float* coefL = (float*)(bufA + 56 * 1024);
+  static_assert(!LOSSF || (40 * 1024 + 3 * MT * LOSS_ROW * 4 <= 56 * 1024 && 56 * 1024 + MT * 4 <= MT * HRB), "fused policy loss: buffer A layout");
   const int wbase = wid * 16 * TPW;
   const int to_w = wid % OT, kh_w = wid / OT;  // WIDE: this wave's out tile and K slice
   for (int idx = tid; idx < 2 * H; idx += 512) biasL[idx] = a.params[a.bias_off[idx / H] + idx % H];
@@ -828,6 +856,23 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a)
   if constexpr (!WIDE)
     for (int idx = tid; idx < KSH * OT * 64; idx += 512) woutL[idx] = a.ostream2[idx];
   for (int idx = tid; idx < ks0v * OT * 64; idx += 512) w0cL[idx] = a.ostream0[idx];
+  if constexpr (LOSSF) {  // ppo_loss_kernel's prologue: the per-step table, the advantage moments; and the denoising steps
+    const int Kft = la.pcfg.ft_denoising_steps;
+    for (int k = tid; k < 2 * Kft; k += 512) tabL[k] = la.tab[k];
+    for (int k = tid; k < Kft; k += 512) {
+      const dppo_step st = la.ksteps[k];
+      float* sl = stepL + k * LOSS_STEP;
+      sl[0] = st.c0, sl[1] = st.c1, sl[2] = st.c2, sl[3] = st.c3, sl[4] = st.std;
+      sl[5] = la.tab[2 * Kft + k];  // log std_k (build_rows_kernel)
+    }
+    if (tid == 0) {
+      const double Nm = la.moments[2], mean = la.moments[0] / Nm;
+      const double varu = (la.moments[1] - Nm * mean * mean) / (Nm - 1.0);  // unbiased (torch.std)
+      tabL[2 * Kft] = (float)mean;
+      tabL[2 * Kft + 1] = (float)sqrt(varu > 0 ? varu : 0);
+      tabL[2 * Kft + 2] = (float)(la.n_count > 0 ? la.n_count : Nm);  // samples in the (global) minibatch
+    }
+  }
   if (tid < 16) flags[tid] = 0;
   uint32_t seq = 0;
   // (visible after the first tile's barrier)
@@ -845,8 +890,34 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a)
     const int row0 = tile * MT;
     STAMP(0);
     load_tile<MT>(xin, in_rb, in_km, (const char*)a.in, a.ld_in * ES, row0, M);
+    if constexpr (LOSSF) {
+      int t_ = tid;
+      asm volatile("" : "+v"(t_));
+      if (t_ < MT) {
+        const int n = row0 + t_, Kft = la.pcfg.ft_denoising_steps, AF = la.AF;
+        const long long b = n < M ? la.brow[n] : 0, k = n < M ? la.krow[n] : 0;
+        metaL[3 * t_] = la.gathered ? b * 2 * AF : (b * (Kft + 1) + k) * AF;
+        metaL[3 * t_ + 1] = la.gathered ? b * AF : (b * Kft + k) * AF;
+        metaL[3 * t_ + 2] = (b << 32) | k;
+      }
+    }
     __syncthreads();
     STAMP(1);
+    // LOSSF: touch the cache lines of the tile's loss inputs now (five dwords per row: both ends of the chain pair and of the old
+    // log-probs, the advantage), a whole k-loop ahead of the loads that use them
+    uint32_t warm = 0;
+    if constexpr (LOSSF) {
+      int t_ = tid;
+      asm volatile("" : "+v"(t_));
+      const int row = t_ / 5, part = t_ - row * 5;
+      if (row < MT && row0 + row < M) {
+        const int AF = la.AF;
+        const float* src = part < 2   ? la.chains + lds_load(metaL + 3 * row) + (part ? 2 * AF - 1 : 0)
+                           : part < 4 ? la.logprobs_k + lds_load(metaL + 3 * row + 1) + (part == 3 ? AF - 1 : 0)
+                                      : la.adv_k + (int)(lds_load(metaL + 3 * row + 2) >> 32);
+        warm = *(const uint32_t*)src;
+      }
+    }
     f32x4 acc[TPW][MR];
     auto bias_init = [&](int layer) {
 #pragma unroll
@@ -895,6 +966,29 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a)
       eng.run(acc, bufA, HRB, 15, KSH, r, g, FLAGS ? flags : nullptr, seq);
     }
     STAMP(5);
+    // LOSSF: this thread's loss inputs, requested in front of the emit's stores (see the head comment): elements slot and slot + 8
+    // of its sample's x_k, x_k+1 (adjacent in memory) and old log-probs; lanes 0-7: the advantage of sample 8 wid + lane
+    float lx[2] = {0.f, 0.f}, lxn[2] = {0.f, 0.f}, lo[2] = {0.f, 0.f}, ladv = 0.f;
+    if constexpr (LOSSF) {
+      asm volatile("" ::"v"(warm));  // (the touches have landed long ago)
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      const int AF = la.AF, sm = 8 * wid + (ln >> 3), slot = ln & 7;
+      const int cnt = (la.pcfg.reward_horizon < la.pcfg.horizon_steps ? la.pcfg.reward_horizon : la.pcfg.horizon_steps) * la.pcfg.action_dim;
+      if (row0 + sm < M) {
+        const float* ch = la.chains + lds_load(metaL + 3 * sm);
+        const float* ol = la.logprobs_k + lds_load(metaL + 3 * sm + 1);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int j = slot + 8 * q;
+          if (j < cnt) lx[q] = glb_load(ch + j), lxn[q] = glb_load(ch + AF + j), lo[q] = glb_load(ol + j);
+        }
+      }
+      if (ln < 8 && row0 + 8 * wid + ln < M) ladv = glb_load(la.adv_k + (int)(lds_load(metaL + 3 * (8 * wid + ln) + 2) >> 32));
+      // (they are waited for HERE, with none of the emit's stores issued yet: vmcnt counts loads and stores in issue order, so a
+      // wait for them behind the emit would wait for its stores as well)
+      asm volatile("" : "+v"(lx[0]), "+v"(lxn[0]), "+v"(lo[0]), "+v"(lx[1]), "+v"(lxn[1]), "+v"(lo[1]), "+v"(ladv)::"memory");
+    }
     emit<P, TPW, MR>(acc, ACT, bufB, a.a2[0], H, wbase, g, r, row0, M, a.z1[0]);  // z1[0] <- act'(z1) (Mish) / sign words
     STAMP(6);
     __syncthreads();  // the out layer's work items read every wave's features
@@ -956,18 +1050,85 @@ __device__ __forceinline__ void fused_forward_merged_body(const FusedFwdArgs& a)
       float s = biasL[2 * H + j];
 #pragma unroll
       for (int kh = 0; kh < KSPLIT; ++kh) s += part[(((kh * MR + m) * OT + to) * 16 + jj) * 16 + rr];
-      if (row0 + row < M)
+      if constexpr (LOSSF)
+        epsL[row * 16 + j] = s;
+      else if (row0 + row < M)
         a.out[(size_t)(row0 + row) * a.ldout + j] = s;
     }
     STAMP(13);
+    if constexpr (LOSSF) {
+      __syncthreads();  // the eps tile is in place
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      const int cnt = (la.pcfg.reward_horizon < la.pcfg.horizon_steps ? la.pcfg.reward_horizon : la.pcfg.horizon_steps) * la.pcfg.action_dim;
+      const int sm = 8 * wid + (ln >> 3), slot = ln & 7;  // element and store phases: this thread's sample and slot
+      {  // ---- element phase
+        const int k = (int)(lds_load(metaL + 3 * sm + 2) & 0xffffffffll);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int j = slot + 8 * q;
+          if (j < cnt) {
+            float lpn, lpo, gs;
+            loss_element_nc(la.dcfg, stepL + k * LOSS_STEP, lx[q], lxn[q], lds_load(epsL + sm * 16 + j), lo[q], lpn, lpo, gs);
+            lpnL[sm * LOSS_ROW + j] = lpn, lpoL[sm * LOSS_ROW + j] = lpo, gsL[sm * LOSS_ROW + j] = gs;
+          }
+        }
+      }
+      // (the wave's own LDS stores, read back by other lanes of the same wave: in order, no workgroup barrier)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      if (ln < 8) {  // ---- sample phase: one lane per sample
+        const int s1 = 8 * wid + ln;
+        double s4[4] = {0, 0, 0, 0};
+        float coef = 0.f;
+        if (row0 + s1 < M) {
+          const int k = (int)(lds_load(metaL + 3 * s1 + 2) & 0xffffffffll);
+          coef = policy_loss_sample_nc(la.pcfg, tabL, k, ladv, lpnL + s1 * LOSS_ROW, lpoL + s1 * LOSS_ROW, cnt, s4);
+        }
+        coefL[s1] = coef;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) statL[4 * s1 + q] = s4[q];
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      if (row0 + sm < M) {  // ---- store phase: the row's 16-byte chunks (eight bf16 each), zero padded to ldde
+        const float coef = lds_load(coefL + sm);
+        typename P::elem_t* de = (typename P::elem_t*)la.d_eps + (size_t)(row0 + sm) * la.ldde;
+        for (int c = slot; c < la.ldde / 8; c += 8) *(u32x4*)(de + c * 8) = policy_loss_chunk_nc(coef, gsL + sm * LOSS_ROW, c, cnt);
+      }
+    }
     __syncthreads();  // the next tile's input lands in buffer B; its layer-0 emit in buffer A, where the partials were read
     STAMP(14);
+    if constexpr (LOSSF) {
+      // the tile's partial sums by the loss kernel's shuffle tree over its 64 samples (v_loss belongs to the value half's launch).
+      // statL is written again only behind the next tile's barriers.
+      // One statistic per wave (waves 0-3; each tree is the loss kernel's, six dependent shuffles of a double).
+      if (wid < 4) {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        double v = lds_load(statL + 4 * ln + wid);
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        if (ln == 0) {
+          double* po = la.partial + (size_t)tile * 8;
+          po[wid == 0 ? DPPO_STAT_PG_LOSS : wid == 1 ? DPPO_STAT_APPROX_KL : wid == 2 ? DPPO_STAT_CLIPFRAC : DPPO_STAT_RATIO] = v;
+          if (wid == 0) po[DPPO_STAT_V_LOSS] = 0.0;
+        }
+      }
+    }
   }
 }
 
 template <class P, int TPW, int MR, int OT, int ACT, int S1>
 __global__ __launch_bounds__(512, 2) void fused_forward_merged_kernel(const FusedFwdArgs a) {
-  fused_forward_merged_body<P, TPW, MR, OT, ACT, S1>(a);
+  fused_forward_merged_body<P, TPW, MR, OT, ACT, S1, false>(a, LossArgs{});
+}
+// The fused-loss variant under a register cap: two of its waves must leave a SIMD 64 free registers, or the critic's launches can
+// no longer slip a wave in beside these persistent workgroups.  amdgpu_num_vgpr(112): on gfx90a+ the compiler
+// DOUBLES the request (unified VGPR + AGPR file), so this is 224, the plain kernel's allocation.
+template <class P, int TPW, int MR, int ACT, int S1>
+__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(112))) void fused_forward_merged_loss_kernel(const FusedFwdArgs a,
+                                                                                                              const LossArgs la) {
+  fused_forward_merged_body<P, TPW, MR, 1, ACT, S1, true>(a, la);
 }
 
 // =================================================================================================
@@ -1543,22 +1704,44 @@ bool fused_can_merge(const dppo_net_desc& d) {
 template bool fused_can_merge<F32>(const dppo_net_desc&);
 template bool fused_can_merge<BF16>(const dppo_net_desc&);
 
-template <class P, int TPW, int MR, int ACT, int S1, int OT = 1>
-static int launch_fwd_merged_cfg2(const FusedFwdArgs& a, hipStream_t s) {
+// shapes the fused policy loss covers (the caller adds its own conditions on the loss's arguments: fused_loss_shape())
+constexpr int FUSED_LOSS_MAX_KFT = 64;
+// per row three offsets and four statistics, then per step LOSS_STEP dwords and two table entries, then the advantage moments and count
+static size_t fused_loss_lds(int Kft) { return (size_t)64 * (3 * 8 + 4 * 8) + ((size_t)(Kft * (LOSS_STEP + 2) + 3) * 4 + 15) / 16 * 16; }
+template <class P, int TPW, int MR, int ACT, int S1, int OT = 1, bool LOSSF = false>
+static int launch_fwd_merged_cfg2(const FusedFwdArgs& a, hipStream_t s, const LossArgs* loss = nullptr) {
   constexpr int MT = 16 * MR, H = 128 * TPW;
-  const size_t lds = merged_lds<P>(H, OT, a.ks0v);
+  const size_t lds = merged_lds<P>(H, OT, a.ks0v) + (LOSSF ? fused_loss_lds(loss->pcfg.ft_denoising_steps) : 0);
   if (lds > 160 * 1024 || a.Kp0 > H || a.nb != 1) return -2;
+  if (LOSSF != (loss != nullptr)) return -4;
   static DevLatch attr;
   const int ntiles = (a.M + MT - 1) / MT;
+  if constexpr (LOSSF) {  // (its own kernel symbol: the same body under a register cap)
+    if (loss->pcfg.ft_denoising_steps > FUSED_LOSS_MAX_KFT) return -4;
+    raise_lds(fused_forward_merged_loss_kernel<P, TPW, MR, ACT, S1>, attr);
+    const bool probe = probe_begin(PROBE_FUSED_FWD, s);
+    hipLaunchKernelGGL((fused_forward_merged_loss_kernel<P, TPW, MR, ACT, S1>), dim3(ntiles < NUM_CUS ? ntiles : NUM_CUS), dim3(512), lds, s,
+                       a, *loss);
+    if (probe) probe_end(s, 2.0 * a.M * ((double)a.in_valid * H + 2.0 * a.nb * H * H + (double)H * a.out_dim));
+    return 0;
+  } else {
   raise_lds(fused_forward_merged_kernel<P, TPW, MR, OT, ACT, S1>, attr);
   const bool probe = probe_begin(PROBE_FUSED_FWD, s);
   hipLaunchKernelGGL((fused_forward_merged_kernel<P, TPW, MR, OT, ACT, S1>), dim3(ntiles < NUM_CUS ? ntiles : NUM_CUS), dim3(512),
                      lds, s, a);
   if (probe) probe_end(s, 2.0 * a.M * ((double)a.in_valid * H + 2.0 * a.nb * H * H + (double)H * a.out_dim));
   return 0;
+  }
 }
 template <class P, int TPW, int MR, int ACT>
-static int launch_fwd_merged_cfg(const FusedFwdArgs& a, hipStream_t s) {
+static int launch_fwd_merged_cfg(const FusedFwdArgs& a, hipStream_t s, const LossArgs* loss) {
+  if (loss != nullptr) {  // the policy loss in the epilogue: bf16 64-row tiles of H = 512, one out tile, compact walk (fused_loss_shape())
+    if constexpr (P::ESIZE == 2 && MR == 4 && TPW == 4 && ring_depth<TPW, MR>() == 4) {
+      if (a.out_dim <= 16 && fused_compact_on() && a.ks0v == 1) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 1, 1, true>(a, s, loss);
+      if (a.out_dim <= 16 && fused_compact_on() && a.ks0v == 2) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 2, 1, true>(a, s, loss);
+    }
+    return -4;
+  }
   if (a.out_dim > 16) {  // the wide head (fused_can_merge admitted it: hidden 512, compact walk, ks0v <= 3)
     if constexpr (TPW == 4) {
       if (a.ks0v == 1) return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 1, 4>(a, s);
@@ -1574,15 +1757,20 @@ static int launch_fwd_merged_cfg(const FusedFwdArgs& a, hipStream_t s) {
   return launch_fwd_merged_cfg2<P, TPW, MR, ACT, 0>(a, s);
 }
 
+// the fused policy loss exists for: bf16, hidden 512 (64-row tiles), a head of at most 16 outputs, at most two input k-steps
+bool fused_loss_shape(const dppo_net_desc& d, int Kft) {
+  return fused_compact_on() && d.hidden == 512 && d.out_dim <= 16 && d.in_dim <= 2 * BF16::KB && Kft <= FUSED_LOSS_MAX_KFT &&
+         fused_can_merge<BF16>(d) && pick_mr<BF16>(d.hidden) == 4;
+}
 template <class P>
-int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStream_t s) {
+int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStream_t s, const LossArgs* loss) {
   const int tpw = d.hidden / 128, mr = pick_mr<P>(d.hidden);
   const int nt = (d.out_dim + 15) / 16, ot = nt <= 1 ? 1 : (nt <= 4 ? 4 : (nt <= 8 ? 8 : 0));
   if (mr == 0 || ot == 0 || a.M <= 0) return -1;
   const bool relu = a.act == ACT_RELU;  // check_net admits ReLU and Mish only
   if (a.merge_top) {  // (the caller asked fused_can_merge() first)
 #define DPPO_FWDM(T, R) \
-  if (tpw == T && mr == R) return relu ? launch_fwd_merged_cfg<P, T, R, ACT_RELU>(a, s) : launch_fwd_merged_cfg<P, T, R, ACT_MISH>(a, s);
+  if (tpw == T && mr == R) return relu ? launch_fwd_merged_cfg<P, T, R, ACT_RELU>(a, s, loss) : launch_fwd_merged_cfg<P, T, R, ACT_MISH>(a, s, loss);
     if constexpr (P::ESIZE == 2) {
       DPPO_FWDM(2, 8) DPPO_FWDM(4, 4)
     } else {
@@ -1591,6 +1779,7 @@ int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStrea
 #undef DPPO_FWDM
     return -1;
   }
+  if (loss != nullptr) return -4;
   if constexpr (P::ESIZE == 2) {
     if (short_tiles<P>(d.hidden, a.use_ln, 1) && ot == 1)
       return relu ? launch_fwd_cfg<P, 4, 2, 1, false, ACT_RELU, 2>(a, s) : launch_fwd_cfg<P, 4, 2, 1, false, ACT_MISH, 2>(a, s);
@@ -1613,8 +1802,8 @@ int launch_fused_forward(const dppo_net_desc& d, const FusedFwdArgs& a, hipStrea
 #undef DPPO_FWD
   return -1;
 }
-template int launch_fused_forward<F32>(const dppo_net_desc&, const FusedFwdArgs&, hipStream_t);
-template int launch_fused_forward<BF16>(const dppo_net_desc&, const FusedFwdArgs&, hipStream_t);
+template int launch_fused_forward<F32>(const dppo_net_desc&, const FusedFwdArgs&, hipStream_t, const LossArgs*);
+template int launch_fused_forward<BF16>(const dppo_net_desc&, const FusedFwdArgs&, hipStream_t, const LossArgs*);
 
 template <class P, int TPW, int MR, bool LN, int ACT, int OCC = 1>
 static int launch_bwd_cfg(const FusedBwdArgs& a, hipStream_t s) {

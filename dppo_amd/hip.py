@@ -224,6 +224,7 @@ SYMBOLS = {
                                       C.POINTER(C.c_double)]),
     "dppo_tune_set": (_I, [_I, _I]),
     "dppo_backward_route": (_I, [_ND, _I, _L, _I, _I, C.POINTER(C.c_int)]),
+    "dppo_ppo_loss_route": (_I, [_ND, _ND, _I, _L, _I]),
     "dppo_gemm_nt_raw": (_I, [_I, _P, _P, _P, _L, _I, _I, _P, _P, _I, _I, _P]),
     "dppo_gemm_tn_raw": (_I, [_I, _P, _I, _I, _P, _I, _I, _L, _I, _P, _P, _P]),
     "dppo_gemm_nt_desc_raw": (_I, [_I, C.POINTER(GemmNTDesc), _P]),

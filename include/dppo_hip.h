@@ -518,6 +518,8 @@ int dppo_probe_collect_bytes(double* total_ms_host, int* launches_host, double* 
  * knob 41: with knob 38: the slab reductions of the actor's weight-gradient GEMMs and what depends on the two thin products among
  *          them (low-rank dW2, dWout, db2) are one launch -- the dependent workgroups poll the thin reductions' arrival -- (1,
  *          default) or two launches (0)
+ * knob 42: the policy half of the PPO loss runs in the epilogue of the actor's fused forward, spread over the workgroup, where
+ *          the call qualifies (dppo_ppo_loss_route()) (1, default) or is always a launch of its own (0); results are bit-identical
  * knob 30: minibatch rows per output column from which the top block's weight gradient is taken low-rank (knob 16) and the
  *          one-block backward (knob 23) runs: M >= value x out_dim (default 100)
  * knob 29: knob 27's kernel: sweeps a workgroup waits for its tile before it gives up (default 2^20; tests force a time-out
@@ -546,6 +548,12 @@ int dppo_tune_set(int knob, int value);
 #define DPPO_ROUTE_TAIL_POST 0x400 /* slab reductions and post-reduce parts behind the GEMMs in one launch (knob 41) */
 #define DPPO_ROUTE_POST_ONE 0x800  /* everything behind the slab reduction in one launch (knob 18) */
 int dppo_backward_route(const dppo_net_desc* net, int prec, int64_t M, int Kft, int flags, int* mask_out);
+/* Who evaluates the policy half of the PPO loss for a dppo_ppo_loss_fwd_bwd call of N samples under the current knobs: 1 = the
+ * actor's fused forward, in its epilogue (knob 42), 0 = the separate loss launch, < 0 = bad argument.  Pure host code, no GPU
+ * needed.  The fused route takes: bf16; a one-block actor on the merged forward (knob 22) with hidden 512 and a head of at most 16
+ * outputs; the value half on the critic's own stream (knob 2); no advantage-moment riders (knob 36: by default N > 16,384, or
+ * global_moments given).  The call itself additionally needs ft_denoising_steps <= 64, which every shipped cfg meets. */
+int dppo_ppo_loss_route(const dppo_net_desc* actor, const dppo_net_desc* critic, int prec, int64_t N, int has_global_moments);
 /* one bare layer GEMM: out[M][ldo] = act(X[M][Kp] . W[N][Kp]^T + bias) with elem = prec operands;
  * out_f32 and/or out_elem may be NULL; ldo >= round_up(N,16) */
 int dppo_gemm_nt_raw(int prec, const void* X, const void* W, const float* bias, int64_t M, int N, int Kp,
