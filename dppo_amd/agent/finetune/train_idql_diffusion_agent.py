@@ -29,8 +29,11 @@ from dppo_amd.util.scheduler import CosineAnnealingWarmupRestarts
 log = logging.getLogger(__name__)
 
 
-class TrainIDQLDiffusionAgent:
-    def __init__(self, cfg, venv=None):
+class OffPolicyDiffusionAgent:
+    """What the off-policy fine-tuning agents share (IDQL here, QSM in train_qsm_diffusion_agent.py): the reference's
+    ``TrainAgent`` set-up, the env reset, the checkpoint and the per-iteration episode statistics."""
+
+    def _init_train_agent(self, cfg, venv, who):
         self.cfg = cfg
         self.device = cfg.device
         self.seed = cfg.get("seed", 42)
@@ -55,7 +58,7 @@ class TrainIDQLDiffusionAgent:
         self.n_cond_step, self.obs_dim, self.action_dim = cfg.cond_steps, cfg.obs_dim, cfg.action_dim
         self.act_steps, self.horizon_steps = cfg.act_steps, cfg.horizon_steps
         # the stored action chunk is the actor loss's x_start (reference :298-301)
-        assert self.act_steps == self.horizon_steps, "IDQL needs act_steps == horizon_steps"
+        assert self.act_steps == self.horizon_steps, f"{who} needs act_steps == horizon_steps"
         self.reset_at_iteration = cfg.env.get("reset_at_iteration", True)
         self.batch_size = cfg.train.batch_size
         self.model = instantiate(cfg.model)
@@ -72,6 +75,40 @@ class TrainIDQLDiffusionAgent:
         self.log_freq = cfg.train.get("log_freq", 1)
         self.save_model_freq = cfg.train.save_model_freq
 
+    def reset_env_all(self, options_venv=None):
+        obs = self.venv.reset_arg(options_list=options_venv or [{} for _ in range(self.n_envs)])
+        if isinstance(obs, list):
+            obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
+        return obs
+
+    def save_model(self):
+        """checkpoint/state_{itr}.pt = {"itr", "model": state_dict} (train_agent.py:125-135)."""
+        path = os.path.join(self.checkpoint_dir, f"state_{self.itr}.pt")
+        torch.save({"itr": self.itr, "model": self.model.state_dict()}, path)
+        log.info("Saved model to %s", path)
+
+    def _episode_stats(self, firsts, reward_trajs):
+        """(average episode reward, average best reward, success rate) over the episodes that finish within the iteration
+        (reference :190-225)."""
+        ep_rewards, ep_best = [], []
+        for e in range(self.n_envs):
+            starts = np.where(firsts[:, e] == 1)[0]
+            for i in range(len(starts) - 1):
+                a, b = starts[i], starts[i + 1]
+                if b - a > 1:
+                    seg = reward_trajs[a:b, e]
+                    ep_rewards.append(seg.sum())
+                    ep_best.append(seg.max() / self.act_steps)
+        n_ep = len(ep_rewards)
+        avg_ep = float(np.mean(ep_rewards)) if n_ep else 0.0
+        avg_best = float(np.mean(ep_best)) if n_ep else 0.0
+        success = float(np.mean(np.array(ep_best) >= self.best_reward_threshold_for_success)) if n_ep else 0.0
+        return avg_ep, avg_best, success
+
+
+class TrainIDQLDiffusionAgent(OffPolicyDiffusionAgent):
+    def __init__(self, cfg, venv=None):
+        self._init_train_agent(cfg, venv, "IDQL")
         # ---- TrainIDQLDiffusionAgent (:26-96)
         self.gamma = cfg.train.gamma  # applied to the reward of every act_steps env steps
         self.n_critic_warmup_itr = cfg.train.n_critic_warmup_itr
@@ -96,18 +133,6 @@ class TrainIDQLDiffusionAgent:
         self.num_sample = cfg.train.eval_sample_num
         self.replay = DeviceReplay(self.buffer_size, self.n_envs, self.n_cond_step * self.obs_dim,
                                    self.act_steps * self.action_dim, self.device)
-
-    def reset_env_all(self, options_venv=None):
-        obs = self.venv.reset_arg(options_list=options_venv or [{} for _ in range(self.n_envs)])
-        if isinstance(obs, list):
-            obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
-        return obs
-
-    def save_model(self):
-        """checkpoint/state_{itr}.pt = {"itr", "model": state_dict} (train_agent.py:125-135)."""
-        path = os.path.join(self.checkpoint_dir, f"state_{self.itr}.pt")
-        torch.save({"itr": self.itr, "model": self.model.state_dict()}, path)
-        log.info("Saved model to %s", path)
 
     def load(self, itr):
         data = torch.load(os.path.join(self.checkpoint_dir, f"state_{itr}.pt"), weights_only=True)
@@ -186,19 +211,7 @@ class TrainIDQLDiffusionAgent:
             if hasattr(model, "check_sampler_health"):
                 model.check_sampler_health()
             # ---------------- episode statistics (:190-225)
-            ep_rewards, ep_best = [], []
-            for e in range(E):
-                starts = np.where(firsts[:, e] == 1)[0]
-                for i in range(len(starts) - 1):
-                    a, b = starts[i], starts[i + 1]
-                    if b - a > 1:
-                        seg = reward_trajs[a:b, e]
-                        ep_rewards.append(seg.sum())
-                        ep_best.append(seg.max() / self.act_steps)
-            n_ep = len(ep_rewards)
-            avg_ep = float(np.mean(ep_rewards)) if n_ep else 0.0
-            avg_best = float(np.mean(ep_best)) if n_ep else 0.0
-            success = float(np.mean(np.array(ep_best) >= self.best_reward_threshold_for_success)) if n_ep else 0.0
+            avg_ep, avg_best, success = self._episode_stats(firsts, reward_trajs)
             # ---------------- update (:227-309)
             if not eval_mode:
                 num_batch = int(S * E / self.batch_size * self.replay_ratio)

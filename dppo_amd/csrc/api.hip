@@ -11,6 +11,7 @@
 #include "gaussian.h"
 #include "gmm.h"
 #include "idql.h"
+#include "qsm.h"
 #include "unet.h"
 #include "sampler.h"
 
@@ -2823,6 +2824,211 @@ int dppo_polyak(float* target, const float* source, double tau, int64_t n, dppo_
   if (!(tau >= 0.0 && tau <= 1.0)) return fail(-1, "tau=%g outside [0, 1]", tau);
   launch_polyak(target, source, (float)(1.0 - tau), (float)tau, n, (hipStream_t)stream);
   return check_launch();
+}
+
+// ---- QSM (qsm.hip): the twin critic's action gradient as the actor's regression target, and the TD loss on the target twin ----
+static int check_qsm_q(const dppo_net_desc* q, int obs_dim) {
+  if (int e = check_idql_q(q)) return e;
+  if (obs_dim < 1 || obs_dim >= q->in_dim)
+    return fail(-1, "Q descriptor does not pair with obs_dim=%d: in_dim=%d must be obs_dim + the action width", obs_dim, q->in_dim);
+  return 0;
+}
+static int check_qsm_plain(const dppo_net_desc* q) {
+  if (!q->plain)
+    return fail(-1, "the action gradient dQ/da is built for plain Q trunks (a residual trunk, residual_tyle=True, is not; no shipped cfg has one)");
+  if (qsm_tail_rows(2 * q->hidden) < 1) return fail(-1, "hidden=%d too wide for the action-gradient tail", q->hidden);
+  return 0;
+}
+template <class P>
+struct QsmWs {
+  MlpBufs<P> Q1, Q2;
+  void *dza[2], *dzb[2];  // the chain's two alternating [N][H] buffers, per trunk
+  void* dhcat;            // [N][2H] elem: [dh_0 of Q1 | dh_0 of Q2]
+  void* w0a;              // [AD][2H] elem: the action columns of the two W0, stacked along K
+};
+// forward buffers with the pre-activations kept, and nothing of a parameter backward (no slab, no column-sum partials)
+template <class P>
+static size_t carve_qsm_target(Carver& c, const dppo_net_desc& q, int AD, int64_t N, QsmWs<P>& W) {
+  const size_t ES = P::ESIZE;
+  carve_mlp<P>(c, q, N, true, false, W.Q1);
+  carve_mlp<P>(c, q, N, true, false, W.Q2);
+  for (int i = 0; i < 2; ++i) {
+    W.dza[i] = c.take((size_t)N * q.hidden * ES);
+    W.dzb[i] = c.take((size_t)N * q.hidden * ES);
+  }
+  W.dhcat = c.take((size_t)N * 2 * q.hidden * ES);
+  W.w0a = c.take((size_t)AD * 2 * q.hidden * ES);
+  return al256(c.off);
+}
+int64_t dppo_qsm_actor_target_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
+  if (check_qsm_q(q, obs_dim) || check_qsm_plain(q) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    QsmWs<decltype(p)> W;
+    return carve_qsm_target<decltype(p)>(c, *q, q->in_dim - obs_dim, N, W);
+  });
+}
+// d q / d x of one plain trunk, data gradients only, down to dh_0 = d q / d (layer 0's pre-activation), written into its half
+// of dhcat (row stride 2H)
+template <class P>
+static void qsm_action_chain(const dppo_net_desc& q, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B, void* dza,
+                             void* dzb, void* dh0, hipStream_t s) {
+  const int H = q.hidden, nb = q.n_blocks;
+  launch_qsm_seed<P>(pk + L.Wout, B.z1[nb - 1], N, H, q.act, dza, s);
+  void* dz = dza;
+  void* other = dzb;
+  for (int b = nb - 1; b >= 0; --b) {  // dz <- (dz . W1_b) (.) act'(pre-activation below): backward_plain's step without its dW / db
+    GemmNT g;
+    memset(&g, 0, sizeof(g));
+    g.M = (int)N, g.N = H, g.Kp = H, g.ldx = H, g.ldw = H;
+    g.X = dz, g.W = pk + L.W1T[b], g.dsrc = b == 0 ? B.hpre[0] : B.z1[b - 1], g.dsrc_kind = 2, g.dsrc_ld = H, g.dact = q.act;
+    g.out_pre = b == 0 ? dh0 : other, g.ldo = b == 0 ? 2 * H : H;
+    launch_gemm_nt<P>(g, s);
+    void* t = dz;
+    dz = other, other = t;
+  }
+}
+template <class P>
+static int qsm_target_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const dppo_idql_batch& b,
+                           int OD, int64_t N, const float* noise, const int64_t* t, const float* sa, const float* sb, int K,
+                           double coeff, float* pairs, float* obs_out, float* g_out, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  QsmWs<P> W;
+  const int AD = q.in_dim - OD, H = q.hidden;
+  const size_t need = carve_qsm_target<P>(c, q, AD, N, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout L = pack_layout<P>(q, 0);
+  const ParamLayout pl = param_layout(q);
+  QsmRows r;
+  memset(&r, 0, sizeof(r));
+  r.ring = idql_rows_of(b, N, OD, AD);
+  r.noise = noise, r.t = t, r.sa = sa, r.sb = sb, r.K = K, r.pairs = pairs, r.obs_out = obs_out;
+  r.q1in = W.Q1.in, r.q2in = W.Q2.in, r.KpQ = L.Kp0;
+  launch_qsm_rows<P>(r, s);
+  // Q2's forward and chain on side stream 0 beside Q1's; the packing of the tail's weight operand rides in front of Q1's
+  hipStream_t s2 = fork_side(s, 0);
+  mlp_forward<P>(q, qp + pl.total, qk2, L, N, W.Q2, true, s2);
+  qsm_action_chain<P>(q, qk2, L, N, W.Q2, W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, s2);
+  launch_qsm_pack_w0a<P>(qp, pl.total, pl.W0, q.in_dim, OD, AD, H, W.w0a, s);
+  mlp_forward<P>(q, qp, qk1, L, N, W.Q1, true, s);
+  qsm_action_chain<P>(q, qk1, L, N, W.Q1, W.dza[0], W.dzb[0], W.dhcat, s);
+  if (s2 != s) join_side(s, s2, 0);
+  QsmTail tl;
+  memset(&tl, 0, sizeof(tl));
+  tl.dh = W.dhcat, tl.wa = W.w0a, tl.N = N, tl.H2 = 2 * H, tl.AD = AD, tl.rows = qsm_tail_rows(2 * H), tl.coeff = (float)coeff;
+  tl.pairs = pairs, tl.g_out = g_out;
+  launch_qsm_tail<P>(tl, s);
+  return check_launch();
+}
+int dppo_qsm_actor_target(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                          const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise, const int64_t* t,
+                          const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod, int K, double coeff,
+                          float* pairs, float* obs_out, float* g_out, void* workspace, int64_t workspace_bytes,
+                          dppo_stream_t stream) {
+  if (int e = check_qsm_q(q, obs_dim)) return e;
+  if (int e = check_qsm_plain(q)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!q_params || !q1_packed || !q2_packed || !noise || !t || !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || !pairs ||
+      !obs_out || !workspace)
+    return fail(-1, "null pointer");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_idql_batch(batch, N, false)) return e;
+  if (K < 1 || K > 1024) return fail(-1, "K=%d denoising steps outside [1, 1024]", K);
+  if (!(coeff >= 0.0 && coeff <= 3.0e38)) return fail(-1, "q_grad_coeff=%g must be finite and >= 0", coeff);
+#define CALL(P)                                                                                                              \
+  qsm_target_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, *batch, obs_dim, N, noise, t,             \
+                     sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, K, coeff, pairs, obs_out, g_out, workspace,         \
+                     workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+template <class P>
+struct QsmTdWs {
+  MlpBufs<P> Q1, Q2, T1, T2;
+  double* partial;
+  float *r, *term;
+};
+template <class P>
+static size_t carve_qsm_td(Carver& c, const dppo_net_desc& q, int64_t N, QsmTdWs<P>& W) {
+  W.partial = (double*)c.take((size_t)idql_blocks(N) * 4 * sizeof(double));
+  W.r = (float*)c.take((size_t)N * 4);
+  W.term = (float*)c.take((size_t)N * 4);
+  carve_mlp<P>(c, q, N, true, true, W.Q1);
+  carve_mlp<P>(c, q, N, true, true, W.Q2);
+  carve_mlp<P>(c, q, N, false, false, W.T1);
+  carve_mlp<P>(c, q, N, false, false, W.T2);
+  return al256(c.off);
+}
+int64_t dppo_qsm_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
+  if (check_qsm_q(q, obs_dim) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    QsmTdWs<decltype(p)> W;
+    return carve_qsm_td<decltype(p)>(c, *q, N, W);
+  });
+}
+template <class P>
+static int qsm_td_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const float* tp, const char* tk1,
+                       const char* tk2, const dppo_idql_batch& b, int OD, const float* next_actions, int64_t N, double gamma,
+                       float* qgrad, double* stats, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  QsmTdWs<P> W;
+  const size_t need = carve_qsm_td<P>(c, q, N, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout L = pack_layout<P>(q, 0);
+  const int64_t nq = param_layout(q).total;
+  QsmTdRows r;
+  memset(&r, 0, sizeof(r));
+  r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
+  r.next_actions = next_actions, r.q1in = W.Q1.in, r.q2in = W.Q2.in, r.t1in = W.T1.in, r.t2in = W.T2.in, r.KpQ = L.Kp0;
+  r.r_out = W.r, r.term_out = W.term;
+  launch_qsm_td_rows<P>(r, s);
+  // Q2 and the two target trunks on the three side streams beside Q1; the side streams are joined into the last one, so the
+  // caller's stream waits once before the loss (flush_slabs() has the reason)
+  hipStream_t s2 = fork_side(s, 0), s3 = fork_side(s, 1), s4 = fork_side(s, 2);
+  mlp_forward<P>(q, qp + nq, qk2, L, N, W.Q2, true, s2);
+  mlp_forward<P>(q, tp, tk1, L, N, W.T1, false, s3);
+  mlp_forward<P>(q, tp + nq, tk2, L, N, W.T2, false, s4);
+  mlp_forward<P>(q, qp, qk1, L, N, W.Q1, true, s);
+  if (s4 != s) {
+    if (s2 != s) join_side(s4, s2, 0);
+    if (s3 != s) join_side(s4, s3, 1);
+    join_side(s, s4, 2);
+  } else {
+    if (s2 != s) join_side(s, s2, 0);
+    if (s3 != s) join_side(s, s3, 1);
+  }
+  IdqlLoss l;
+  memset(&l, 0, sizeof(l));
+  l.q1 = W.Q1.out, l.q2 = W.Q2.out, l.ldq = W.Q1.ldout, l.v = W.T1.out, l.v2 = W.T2.out, l.ldv = W.T1.ldout, l.N = N;
+  l.reward = W.r, l.terminated = W.term, l.gamma = (float)gamma, l.d_a = W.Q1.d_out, l.d_b = W.Q2.d_out;
+  l.ldd = L.Kpo, l.partial = W.partial, l.stats = stats;
+  launch_idql_q_loss<P>(l, s);
+  s2 = fork_side(s, 0);
+  mlp_backward<P>(q, qp + nq, qk2, L, N, W.Q2, qgrad + nq, nullptr, nullptr, 0, s2);
+  mlp_backward<P>(q, qp, qk1, L, N, W.Q1, qgrad, nullptr, nullptr, 0, s);
+  if (s2 != s) join_side(s, s2, 0);
+  return check_launch();
+}
+int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                            const float* target_q_params, const void* target_q1_packed, const void* target_q2_packed,
+                            const dppo_idql_batch* batch, int obs_dim, const float* next_actions, int64_t N, double gamma,
+                            float* q_grad, double* stats, void* workspace, int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_qsm_q(q, obs_dim)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!q_params || !q1_packed || !q2_packed || !target_q_params || !target_q1_packed || !target_q2_packed || !next_actions ||
+      !q_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
+#define CALL(P)                                                                                                                \
+  qsm_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
+                 (const char*)target_q2_packed, *batch, obs_dim, next_actions, N, gamma, q_grad, stats, workspace,             \
+                 workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
 }
 
 // ---- optimiser ----------------------------------------------------------------------------------------

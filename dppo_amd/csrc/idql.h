@@ -26,9 +26,21 @@ struct IdqlRows {
 };
 template <class P>
 void launch_idql_rows(const IdqlRows& a, hipStream_t s);
+// Position in the ring's storage of the transition behind row n: logical index l = inds[n] (or n) counts "s e -> (s e)" over
+// the stored steps, oldest first; step s lives in slot (head + s) % cap.  An index outside the stored range is clamped into
+// it (the indices come from the host's generator; a stale one must not read outside the ring).
+__device__ __forceinline__ int64_t idql_ring_row(const IdqlRows& a, int64_t n) {
+  if (a.obs_mod > 0) return n;
+  int64_t l = a.inds != nullptr ? a.inds[n] : n;
+  const int64_t top = a.count * a.E - 1;
+  l = l < 0 ? 0 : (l > top ? top : l);
+  const int64_t st = l / a.E, e = l - st * a.E;
+  return ((a.head + st) % a.cap) * a.E + e;
+}
 
 struct IdqlLoss {
   const float *q1, *q2, *v;  // trunk outputs, column 0 of [N][ld]
+  const float* v2;           // Q loss, or null: the bootstrap value is min(v, v2) (a target twin on the next rows: qsm.h)
   int ldq, ldv;
   const float *reward, *terminated;  // [N] (Q loss)
   int64_t N;

@@ -7,18 +7,7 @@ namespace dppo {
 int idql_blocks(int64_t N) { return (int)((N + IDQL_RPB - 1) / IDQL_RPB); }
 
 // ---- row builder: one launch writes every operand image of a minibatch ------------------------------------------------------
-// Position in the ring's storage of the transition behind row n: logical index l = inds[n] (or n) counts "s e -> (s e)" over
-// the stored steps, oldest first; step s lives in slot (head + s) % cap.  An index outside the stored range is clamped into
-// it (the indices come from the host's generator; a stale one must not read outside the ring).
-__device__ __forceinline__ int64_t idql_ring_row(const IdqlRows& a, int64_t n) {
-  if (a.obs_mod > 0) return n;
-  int64_t l = a.inds != nullptr ? a.inds[n] : n;
-  const int64_t top = a.count * a.E - 1;
-  l = l < 0 ? 0 : (l > top ? top : l);
-  const int64_t st = l / a.E, e = l - st * a.E;
-  return ((a.head + st) % a.cap) * a.E + e;
-}
-
+// (idql_ring_row(), idql.h, maps row n to its position in the ring's storage)
 template <class P>
 __global__ __launch_bounds__(256) void idql_rows_kernel(const IdqlRows a) {
   typedef typename P::elem_t E;
@@ -142,7 +131,7 @@ void launch_idql_v_loss(const IdqlLoss& a, hipStream_t s) {
 template void launch_idql_v_loss<F32>(const IdqlLoss&, hipStream_t);
 template void launch_idql_v_loss<BF16>(const IdqlLoss&, hipStream_t);
 
-// loss_critic_q (diffusion_idql.py:63-87): target = r + gamma * v' * (1 - terminated);  loss = mean((q1 - target)^2) + mean((q2 - target)^2)
+// loss_critic_q (diffusion_idql.py:63-87; with v2, diffusion_qsm.py:65-95): target = r + gamma * v' * (1 - terminated);  loss = mean((q1 - target)^2) + mean((q2 - target)^2)
 template <class P>
 __global__ __launch_bounds__(256) void idql_q_loss_kernel(const IdqlLoss a) {
   __shared__ float g1[IDQL_RPB], g2[IDQL_RPB];
@@ -152,7 +141,9 @@ __global__ __launch_bounds__(256) void idql_q_loss_kernel(const IdqlLoss a) {
     const bool live = n < a.N;
     const int64_t nn = live ? n : a.N - 1;
     const float mask = 1.f - a.terminated[nn];
-    const float target = a.reward[nn] + (a.gamma * a.v[nn * a.ldv]) * mask;
+    float nv = a.v[nn * a.ldv];
+    if (a.v2 != nullptr) nv = fminf(nv, a.v2[nn * a.ldv]);
+    const float target = a.reward[nn] + (a.gamma * nv) * mask;
     const float q1 = a.q1[nn * a.ldq];
     const float e1 = q1 - target;
     float loss = e1 * e1;

@@ -181,6 +181,12 @@ SYMBOLS = {
     "dppo_idql_q_forward": (_I, [_ND, _I, _P, _P, _P, _P, _I, _L, _P, _L, _I, _P, _P, _P, _L, _P]),
     "dppo_idql_select": (_I, [_P, _P, _P, _I, _P, _P, _L, _I, _I, _I, _D, C.c_uint64, _P, _P, _P]),
     "dppo_polyak": (_I, [_P, _P, _D, _L, _P]),
+    # QSM: the twin critic's action gradient as the actor's regression target, TD loss on the target twin (csrc/qsm.hip)
+    "dppo_qsm_actor_target_workspace_bytes": (_L, [_ND, _I, _I, _L]),
+    "dppo_qsm_actor_target": (_I, [_ND, _I, _P, _P, _P, C.POINTER(IdqlBatch), _I, _L, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P, _L,
+                                   _P]),
+    "dppo_qsm_q_loss_workspace_bytes": (_L, [_ND, _I, _I, _L]),
+    "dppo_qsm_q_loss_fwd_bwd": (_I, [_ND, _I, _P, _P, _P, _P, _P, _P, C.POINTER(IdqlBatch), _I, _P, _L, _D, _P, _P, _P, _L, _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

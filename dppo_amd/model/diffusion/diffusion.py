@@ -330,6 +330,14 @@ class DiffusionModel(nn.Module):
         net = self.network
         vision = getattr(net, "is_vision", False)  # pixel network: encoder forward with a tape, its backward after the loss
         obs = net.encode_obs(cond, train=True) if vision else state.reshape(N, -1).float().contiguous()
+        return self._mse_on_pairs(pairs, kinds, obs, N)
+
+    def _mse_on_pairs(self, pairs, kinds, obs, N):
+        """p_losses' tail: mse(eps_theta(pairs[:, 0], kinds, obs), pairs[:, 1]) and its parameter gradients, for any regression
+        target (QSMDiffusion.loss_actor writes the critic's action gradient there).  pairs (N, 2, Ta*Da), kinds (N,) int64,
+        obs (N, .) contiguous fp32 on the device."""
+        net, dev = self.network, pairs.device
+        vision = getattr(net, "is_vision", False)
         lib, d = hip.load(), net.net_desc()
         flat = net.flat_params()
         grad = torch.empty_like(flat)

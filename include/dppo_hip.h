@@ -796,6 +796,40 @@ int dppo_idql_select(const float* q1, const float* q2, const float* v, int v_per
  * (update_target_critic's rounding).  16-byte accesses where both pointers are 16-byte aligned. */
 int dppo_polyak(float* target, const float* source, double tau, int64_t n, dppo_stream_t stream);
 
+/* ---- QSM: Q-score matching (off-policy fine-tuning of the diffusion policy by the critic's action gradient) --------------
+ * Replaces model/diffusion/diffusion_qsm.py:36-95 (QSMDiffusion.loss_actor / loss_critic; update_target_critic :97-103 is
+ * dppo_polyak) and the batch handling of agent/finetune/train_qsm_diffusion_agent.py:209-275.  The sampler is the plain K-step
+ * chain with the std rule of model/diffusion/diffusion_rwr.py:65-103.  The critic is the twin of the IDQL entries (one
+ * descriptor, flat image [Q1 | Q2], one packed image each; rows [obs | action], obs_dim = To*Do columns of observation) and
+ * always has both trunks: the reference's QSMDiffusion unpacks two outputs.  Batches are dppo_idql_batch.
+ *
+ * loss_actor :36-63 is mse(-eps_theta(x_t, t, s), c * g) = mse(eps_theta(x_t, t, s), -c * g) with g = mean(dQ1/da, dQ2/da) at
+ * (s, x_t): dppo_qsm_actor_target writes the operands of dppo_denoise_mse_fwd_bwd for that.  Per row n, with a the gathered
+ * action chunk:  pairs[n][0] = x_t = sqrt_alphas_cumprod[t[n]] * a + sqrt_one_minus_alphas_cumprod[t[n]] * noise[n] (two fp32
+ * products and one sum: torch's q_sample bit for bit; t clamped into [0, K));  pairs[n][1] = -(float)coeff * g;  obs_out[n] =
+ * the gathered observation;  g_out[n] = g (may be NULL).  pairs (N, 2, Ta*Da), obs_out (N, obs_dim), noise, g_out (N, Ta*Da)
+ * fp32, t (N,) int64, the two tables (K,) fp32, all on the device.  g comes from the data-gradient chain alone (no weight
+ * gradient, slab reduction or column sum is launched, no gradient buffer is touched): one row-builder launch, the two trunks'
+ * forwards and chains side by side on the library's side streams, and one launch for the K = 2*hidden product of
+ * [dh_0 of Q1 | dh_0 of Q2] with the stacked action columns of the two first layers, scaled and stored in its epilogue.  Each
+ * row's result depends on that row alone (two calls, and a gathered and a contiguous call, are bit-identical).  Plain trunks
+ * only (every shipped cfg: see CriticObsAct); a residual Q trunk is refused. */
+int64_t dppo_qsm_actor_target_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N);
+int dppo_qsm_actor_target(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                          const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise, const int64_t* t,
+                          const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod, int K, double coeff,
+                          float* pairs, float* obs_out, float* g_out, void* workspace, int64_t workspace_bytes,
+                          dppo_stream_t stream);
+/* loss_critic :65-95.  y = reward + (float)gamma * min(tq1, tq2) * (1 - terminated) in fp32, tq the TARGET twin (no gradient) on
+ * [next_obs | next_actions], next_actions (N, Ta*Da) contiguous (the policy's sample at next_obs);  loss = mean((q1 - y)^2) +
+ * mean((q2 - y)^2).  q_grad <- d loss / d [Q1 | Q2] params (flat, OVERWRITTEN);  stats[3] <- {loss, mean q1, mean y} (device
+ * doubles, per-block partials in double summed in block order).  Plain and residual trunks. */
+int64_t dppo_qsm_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N);
+int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                            const float* target_q_params, const void* target_q1_packed, const void* target_q2_packed,
+                            const dppo_idql_batch* batch, int obs_dim, const float* next_actions, int64_t N, double gamma,
+                            float* q_grad, double* stats, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
