@@ -12,6 +12,7 @@
 #include "gmm.h"
 #include "idql.h"
 #include "qsm.h"
+#include "dql.h"
 #include "unet.h"
 #include "sampler.h"
 
@@ -546,15 +547,17 @@ static void cond_encode(const dppo_net_desc& d, const float* prm, const char* pk
 
 template <class P>
 static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
-                        MlpBufs<P>& B, bool keep, hipStream_t s, const LossArgs* fuse_loss = nullptr) {
+                        MlpBufs<P>& B, bool keep, hipStream_t s, const LossArgs* fuse_loss = nullptr, bool layered = false) {
   // fuse_loss: the policy half of the PPO loss in the forward kernel's epilogue (fuse_loss_ok() held: the merged fused kernel runs)
+  // layered: the GEMM path even where the fused kernels cover the shape (the caller's backward reads the layered path's
+  // derivative sources: dql_impl)
   const ParamLayout pl = param_layout(d);
   const int H = d.hidden, nb = d.n_blocks;
   if (fuse_loss != nullptr && !(fused_ok<P>(d) && B.route.merged)) {
     g_fused_fault = -8;  // (fuse_loss_ok() and this function disagree)
     return;
   }
-  if (fused_ok<P>(d)) {
+  if (!layered && fused_ok<P>(d)) {
     FusedFwdArgs f;
     memset(&f, 0, sizeof(f));
     f.wstream = (const u32x4*)(pk + L.sstream), f.ostream = (const u32x4*)(pk + L.ostream), f.params = prm;
@@ -3027,6 +3030,229 @@ int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
   qsm_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
                  (const char*)target_q2_packed, *batch, obs_dim, next_actions, N, gamma, q_grad, stats, workspace,             \
                  workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+// ---- DQL (dql.hip): the actor loss whose gradient flows through the K-step sampling chain ----------------------------------------
+static int check_dql(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim) {
+  if (int e = check_net(a)) return e;
+  if (a->kind != 0) return fail(-1, "dppo_dql_actor_fwd_bwd needs an actor descriptor");
+  if (a->plain)
+    return fail(-1, "the gradient through the sampling chain is built for residual actors (a plain actor, residual_style=False, is not; no shipped cfg has one)");
+  if (a->use_layernorm) return fail(-1, "the gradient through the sampling chain runs on the layered GEMM path: LayerNorm blocks (fused kernels only) are not built");
+  if (int e = check_qsm_q(q, obs_dim)) return e;
+  if (int e = check_qsm_plain(q)) return e;
+  if (a->cond_dim != obs_dim || q->in_dim - obs_dim != a->act_flat)
+    return fail(-1, "actor / Q descriptors do not pair: actor cond_dim=%d, Ta*Da=%d against obs_dim=%d, Q in_dim=%d", a->cond_dim,
+                a->act_flat, obs_dim, q->in_dim);
+  if (qsm_tail_rows(a->hidden) < 1) return fail(-1, "hidden=%d too wide for the chain's link", a->hidden);
+  return 0;
+}
+static int check_dql_sizes(const dppo_net_desc* a, int64_t N, int K) {
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (K < 1 || K > 1024) return fail(-1, "K=%d denoising steps outside [1, 1024]", K);
+  if ((int64_t)(K + 1) * N > 0x7fffffff) return fail(-1, "(K + 1) * N out of range");
+  if ((int64_t)K * a->time_dim > 65536 || time_backward_lds_bytes(K, a->time_dim) > 156 * 1024)
+    return fail(-1, "K * time_dim = %d too large for the time-embedding backward (LDS)", K * a->time_dim);
+  return 0;
+}
+template <class P>
+struct DqlWs {
+  MlpBufs<P> A, Q1, Q2;
+  int32_t* krow;
+  void *dza, *dzb, *dhcat;  // the chosen Q trunk's data-gradient chain (qsm_action_chain)
+  void *w0x, *w0q;          // [AF][H] / [AF][Hq] elem: the x columns of the actor's W0, the action columns of the chosen trunk's
+  float *dx, *scale;
+  double* rowsum;
+  uint8_t* mask;
+  char* wimg;  // the actor's row-major GEMM operands (W and W^T), which dppo_pack_net leaves out where the fused kernels cover the shape
+};
+template <class P>
+static size_t carve_dql(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, int K, DqlWs<P>& W) {
+  const size_t ES = P::ESIZE;
+  const int64_t M = (int64_t)(K + 1) * N;
+  carve_mlp<P>(c, a, M, true, true, W.A);
+  carve_mlp<P>(c, q, N, true, false, W.Q1);
+  carve_mlp<P>(c, q, N, true, false, W.Q2);
+  W.krow = (int32_t*)c.take((size_t)M * 4);
+  W.dza = c.take((size_t)N * q.hidden * ES);
+  W.dzb = c.take((size_t)N * q.hidden * ES);
+  W.dhcat = c.take((size_t)N * 2 * q.hidden * ES);
+  W.w0x = c.take((size_t)a.act_flat * a.hidden * ES);
+  W.w0q = c.take((size_t)a.act_flat * q.hidden * ES);
+  W.dx = (float*)c.take((size_t)N * a.act_flat * 4);
+  W.scale = (float*)c.take(256);
+  W.rowsum = (double*)c.take((size_t)N * 8);
+  W.mask = (uint8_t*)c.take((size_t)N * K * a.act_flat);
+  W.wimg = (char*)c.take(pack_layout<P>(a, 0).total);
+  return al256(c.off);
+}
+int64_t dppo_dql_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int K) {
+  if (check_dql(actor, q, obs_dim) || check_prec(prec) || check_dql_sizes(actor, N, K)) return -1;
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    DqlWs<decltype(p)> W;
+    return carve_dql<decltype(p)>(c, *actor, *q, N, K, W);
+  });
+}
+// Data gradients of the residual trunk for rows [r0, r0 + N): d_out -> dh_all[nb] .. dh_all[0] and dz1_all[..], each kept at the
+// rows' own place (backward_layered's steps without their weight gradients; the derivative sources are the layered forward's)
+template <class P>
+static void dql_actor_chain(const dppo_net_desc& d, const char* pk, const PackLayout& L, int64_t N, int64_t r0, MlpBufs<P>& B,
+                            hipStream_t s) {
+  const size_t ES = P::ESIZE;
+  const int H = d.hidden, nb = d.n_blocks;
+  auto at = [&](const void* p, int ld, size_t es) { return (void*)((char*)p + (size_t)r0 * ld * es); };
+  GemmNT g;
+  memset(&g, 0, sizeof(g));
+  g.M = (int)N, g.N = H, g.Kp = L.Kpo, g.ldx = L.Kpo, g.ldw = L.Kpo, g.ldo = H;
+  g.X = at(B.d_out, L.Kpo, ES), g.W = pk + L.WoutT, g.out_pre = at(B.dh_all[nb], H, ES);
+  launch_gemm_nt<P>(g, s);
+  for (int b = nb - 1; b >= 0; --b) {
+    memset(&g, 0, sizeof(g));  // dz1 = (dh . W2) * act'(z1)
+    g.M = (int)N, g.N = H, g.Kp = H, g.ldx = H, g.ldw = H, g.ldo = H;
+    g.X = at(B.dh_all[b + 1], H, ES), g.W = pk + L.W2T[b], g.dsrc = at(B.z1[b], H, ES), g.dsrc_kind = 2, g.dsrc_ld = H, g.dact = d.act;
+    g.out_pre = at(B.dz1_all[b], H, ES);
+    launch_gemm_nt<P>(g, s);
+    memset(&g, 0, sizeof(g));  // dh_b = dh_{b+1} + (dz1 . W1) * act'(h_b)
+    g.M = (int)N, g.N = H, g.Kp = H, g.ldx = H, g.ldw = H, g.ldo = H;
+    g.X = at(B.dz1_all[b], H, ES), g.W = pk + L.W1T[b], g.dsrc = at(B.h[b], H, 4), g.dsrc_kind = 1, g.dsrc_ld = H, g.dact = d.act;
+    g.add = at(B.dh_all[b + 1], H, ES), g.ldadd = H, g.out_pre = at(B.dh_all[b], H, ES);
+    launch_gemm_nt<P>(g, s);
+  }
+}
+// Every parameter gradient from the stored per-row data gradients, once over all M rows
+template <class P>
+static void dql_weight_grads(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M, MlpBufs<P>& B,
+                             float* grad, const int32_t* krow, const dppo_step* tsteps, int K, hipStream_t s) {
+  const ParamLayout pl = param_layout(d);
+  const int H = d.hidden, nb = d.n_blocks;
+  weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.hE, H, H, M, B, grad + pl.Wout, H, s);
+  launch_colsum<P>(B.d_out, (int)M, d.out_dim, L.Kpo, B.part, REDUCE_BLOCKS, grad + pl.bout, 1.f, s);
+  for (int b = nb - 1; b >= 0; --b) {
+    weight_grad<P>(B.dh_all[b + 1], H, H, B.a2[b], H, H, M, B, grad + pl.l2w[b], H, s);
+    launch_colsum<P>(B.dh_all[b + 1], (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.l2b[b], 1.f, s);
+    weight_grad<P>(B.dz1_all[b], H, H, B.a1[b], H, H, M, B, grad + pl.l1w[b], H, s);
+    launch_colsum<P>(B.dz1_all[b], (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.l1b[b], 1.f, s);
+  }
+  weight_grad<P>(B.dh_all[0], H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s);
+  launch_colsum<P>(B.dh_all[0], (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.b0, 1.f, s);
+  time_embedding_grad<P>(d, prm, pk, L, M, B, B.dh_all[0], grad, krow, tsteps, K, s);
+  if (d.cond_hidden > 0) cond_backward<P>(d, prm, pk, L, M, B, B.dh_all[0], B.cin, grad, s);
+}
+template <class P>
+static int dql_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float* ap, const char* ak, const float* qp, const char* qk1,
+                    const char* qk2, const dppo_diffusion_cfg& cfg, const dppo_step* tsteps, int K, const dppo_idql_batch& b,
+                    int OD, int64_t N, const float* chains, const float* noise_bc, const int64_t* t_bc, const float* sa,
+                    const float* sb, double eta, int which, float* grad, double* stats, uint8_t* masks, float* d_a, void* ws,
+                    int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  DqlWs<P> W;
+  const size_t need = carve_dql<P>(c, a, q, N, K, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const size_t ES = P::ESIZE;
+  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const ParamLayout pla = param_layout(a), plq = param_layout(q);
+  const int64_t M = (int64_t)(K + 1) * N;
+  const int H = a.hidden, Hq = q.hidden, AF = a.act_flat;
+  uint8_t* mask = masks != nullptr ? masks : W.mask;
+  // d_out's padding columns are the K padding of the chain's first GEMM: zero; its data columns are written slab by slab below
+  if (hipMemsetAsync(W.A.d_out, 0, (size_t)M * LA.Kpo * ES, s) != hipSuccess) return fail(-2, "hipMemsetAsync failed");
+  DqlRows r;
+  memset(&r, 0, sizeof(r));
+  r.ring = idql_rows_of(b, N, OD, AF);
+  r.chains = chains, r.noise_bc = noise_bc, r.t_bc = t_bc, r.sa = sa, r.sb = sb, r.temb = (const float*)(ak + LA.temb);
+  r.K = K, r.AF = AF, r.td = a.time_dim, r.obs_in_a = a.cond_hidden > 0 ? 0 : 1, r.inA = W.A.in, r.KpA = LA.Kp0;
+  r.inC = a.cond_hidden > 0 ? W.A.cin : nullptr, r.KpC = LA.Kpc, r.krow = W.krow, r.q1in = W.Q1.in, r.q2in = W.Q2.in, r.KpQ = LQ.Kp0;
+  launch_dql_rows<P>(r, s);
+  // the twin's forwards and the chosen trunk's data-gradient chain on side stream 0 beside the actor's forward over all rows
+  hipStream_t sq = fork_side(s, 0);
+  mlp_forward<P>(q, qp, qk1, LQ, N, W.Q1, true, sq);
+  mlp_forward<P>(q, qp + plq.total, qk2, LQ, N, W.Q2, true, sq);
+  qsm_action_chain<P>(q, which ? qk2 : qk1, LQ, N, which ? W.Q2 : W.Q1, W.dza, W.dzb, W.dhcat, sq);
+  launch_dql_pack_cols<P>(qp + (which ? plq.total : 0) + plq.W0, q.in_dim, OD, AF, Hq, W.w0q, sq);
+  launch_dql_pack_cols<P>(ap + pla.W0, a.in_dim, 0, AF, H, W.w0x, s);
+  // The layered path's operands: part of the packed image only where the fused kernels do NOT cover the shape (pack_impl);
+  // otherwise cast / transposed here, into an image of the same layout (a dozen small launches, whatever K)
+  const char* wk = ak;
+  if (fused_ok<P>(a)) {
+    char* w = W.wimg;
+    launch_cast_pad<P>(ap + pla.W0, H, a.in_dim, a.in_dim, w + LA.W0, LA.Kp0, s);
+    for (int b = 0; b < a.n_blocks; ++b) {
+      launch_cast_pad<P>(ap + pla.l1w[b], H, H, H, w + LA.W1[b], H, s);
+      launch_cast_pad<P>(ap + pla.l2w[b], H, H, H, w + LA.W2[b], H, s);
+      launch_transpose_cast<P>(ap + pla.l1w[b], H, H, H, 0, w + LA.W1T[b], H, s);
+      launch_transpose_cast<P>(ap + pla.l2w[b], H, H, H, 0, w + LA.W2T[b], H, s);
+    }
+    launch_cast_pad<P>(ap + pla.Wout, a.out_dim, H, H, w + LA.Wout, H, s);
+    launch_transpose_cast<P>(ap + pla.Wout, a.out_dim, H, H, 0, w + LA.WoutT, LA.Kpo, s);
+    wk = w;
+  }
+  if (a.cond_hidden > 0) cond_encode<P>(a, ap, ak, LA, M, W.A.cin, W.A, W.A.in, nullptr, 0, true, s);
+  mlp_forward<P>(a, ap, wk, LA, M, W.A, true, s, nullptr, true);
+  DqlPost po;
+  memset(&po, 0, sizeof(po));
+  po.chains = chains, po.eps = W.A.out, po.lde = W.A.ldout, po.tsteps = tsteps, po.N = N, po.K = K, po.AF = AF;
+  po.has_clip = cfg.has_denoised_clip, po.clip = cfg.denoised_clip, po.mask = mask;
+  launch_dql_post(po, s);
+  DqlBc bc;
+  memset(&bc, 0, sizeof(bc));
+  bc.eps = W.A.out + (size_t)K * N * W.A.ldout, bc.lde = W.A.ldout, bc.noise = noise_bc, bc.N = N, bc.AF = AF;
+  bc.d_out = (char*)W.A.d_out + (size_t)K * N * LA.Kpo * ES, bc.ldd = LA.Kpo, bc.rowsum = W.rowsum;
+  launch_dql_bc<P>(bc, s);
+  dql_actor_chain<P>(a, wk, LA, N, (int64_t)K * N, W.A, s);
+  if (sq != s) join_side(s, sq, 0);
+  DqlStats st;
+  memset(&st, 0, sizeof(st));
+  st.q1 = W.Q1.out, st.q2 = W.Q2.out, st.ldq = W.Q1.ldout, st.rowsum = W.rowsum, st.N = N, st.AF = AF, st.which = which;
+  st.eta = eta, st.stats = stats, st.scale = W.scale;
+  launch_dql_stats(st, s);
+  // the seed: d a = scale * dQ_which/da + sa[t_bc] * (dh_0 of the BC slab . W0[:, :AF]), then through the final clamp
+  DqlLink lk;
+  memset(&lk, 0, sizeof(lk));
+  lk.N = N, lk.AF = AF, lk.dx = W.dx, lk.scale = W.scale, lk.t_bc = t_bc, lk.sa = sa, lk.a = chains + (size_t)K * AF, lk.K = K;
+  lk.final_clip = cfg.has_final_clip, lk.tsteps = tsteps, lk.mask = mask, lk.ldd = LA.Kpo;
+  lk.dh = W.dhcat, lk.ldh = 2 * Hq, lk.wa = W.w0q, lk.H = Hq, lk.rows = qsm_tail_rows(Hq), lk.mode = 0;
+  launch_dql_link<P>(lk, s);
+  auto slab = [&](const void* p, int ld, size_t es, int i) { return (void*)((char*)p + (size_t)i * N * ld * es); };
+  lk.wa = W.w0x, lk.H = H, lk.ldh = H, lk.rows = qsm_tail_rows(H);
+  lk.dh = slab(W.A.dh_all[0], H, ES, K), lk.mode = 1, lk.p = K, lk.d_a = d_a, lk.d_out_prev = slab(W.A.d_out, LA.Kpo, ES, K - 1);
+  launch_dql_link<P>(lk, s);
+  lk.mode = 2, lk.d_a = nullptr;
+  for (int p = K - 1; p >= 0; --p) {  // the only sequential part: one slab's data gradients, then the link to the slab before
+    dql_actor_chain<P>(a, wk, LA, N, (int64_t)p * N, W.A, s);
+    lk.dh = slab(W.A.dh_all[0], H, ES, p), lk.p = p, lk.d_out_prev = p > 0 ? slab(W.A.d_out, LA.Kpo, ES, p - 1) : nullptr;
+    launch_dql_link<P>(lk, s);
+  }
+  dql_weight_grads<P>(a, ap, ak, LA, M, W.A, grad, W.krow, tsteps, K, s);
+  return check_launch();
+}
+int dppo_dql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
+                           const void* actor_packed, const float* q_params, const void* q1_packed, const void* q2_packed,
+                           const dppo_diffusion_cfg* cfg, const dppo_step* tsteps, int K, const dppo_idql_batch* batch, int obs_dim,
+                           int64_t N, const float* chains, const float* noise_bc, const int64_t* t_bc,
+                           const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod, double eta, int which,
+                           float* actor_grad, double* stats, uint8_t* masks, float* d_a, void* workspace, int64_t workspace_bytes,
+                           dppo_stream_t stream) {
+  if (int e = check_dql(actor, q, obs_dim)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!actor_params || !actor_packed || !q_params || !q1_packed || !q2_packed || !cfg || !tsteps || !chains || !noise_bc || !t_bc ||
+      !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || !actor_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  if (int e = check_dql_sizes(actor, N, K)) return e;
+  if (!batch) return fail(-1, "null batch");
+  if (!batch->obs) return fail(-1, "null pointer in batch");
+  if (batch->cap < 1 || batch->n_envs < 1 || batch->count < 1 || batch->count > batch->cap || batch->head < 0 || batch->head >= batch->cap)
+    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
+  if (!batch->inds && N > batch->count * batch->n_envs)
+    return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N, (long long)(batch->count * batch->n_envs));
+  if (which != 0 && which != 1) return fail(-1, "which=%d must be 0 (-mean q1 / mean|q2|) or 1 (-mean q2 / mean|q1|)", which);
+  if (!(eta >= -3.0e38 && eta <= 3.0e38)) return fail(-1, "eta=%g must be finite", eta);
+  if (cfg->use_ddim) return fail(-1, "DQL does not support DDIM");
+#define CALL(P)                                                                                                                  \
+  dql_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, *cfg, \
+              tsteps, K, *batch, obs_dim, N, chains, noise_bc, t_bc, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, eta,     \
+              which, actor_grad, stats, masks, d_a, workspace, workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }

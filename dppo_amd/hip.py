@@ -105,6 +105,7 @@ class IdqlBatch(C.Structure):  # struct dppo_idql_batch
 
 
 IDQL_STAT_COUNT = 3
+DQL_STAT_COUNT = 5
 
 DP_HOOK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)  # void (*)(void* user, dppo_stream_t side)
 
@@ -187,6 +188,10 @@ SYMBOLS = {
                                    _P]),
     "dppo_qsm_q_loss_workspace_bytes": (_L, [_ND, _I, _I, _L]),
     "dppo_qsm_q_loss_fwd_bwd": (_I, [_ND, _I, _P, _P, _P, _P, _P, _P, C.POINTER(IdqlBatch), _I, _P, _L, _D, _P, _P, _P, _L, _P]),
+    # DQL: the actor loss differentiated through the K-step sampling chain (csrc/dql.hip)
+    "dppo_dql_actor_workspace_bytes": (_L, [_ND, _ND, _I, _I, _L, _I]),
+    "dppo_dql_actor_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, _P, C.POINTER(DiffusionCfg), _P, _I, C.POINTER(IdqlBatch), _I, _L,
+                                    _P, _P, _P, _P, _P, _D, _I, _P, _P, _P, _P, _P, _L, _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

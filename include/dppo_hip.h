@@ -830,6 +830,41 @@ int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
                             const dppo_idql_batch* batch, int obs_dim, const float* next_actions, int64_t N, double gamma,
                             float* q_grad, double* stats, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
 
+/* ---- DQL: Diffusion Q-learning (the actor loss whose gradient flows through the K-step sampling chain) ---------------------
+ * Replaces model/diffusion/diffusion_dql.py:74-88 (DQLDiffusion.loss_actor) with forward_train :141-179 differentiated by hand;
+ * loss_critic :43-72 is dppo_qsm_q_loss_fwd_bwd word for word, update_target_critic dppo_polyak.
+ *
+ * The call CONSUMES a chain, it does not sample: chains (N, K+1, Ta*Da) from dppo_sample_chain with every position kept
+ * (position s holds the input of the step at diffusion time K-1-s, position K the action a, already clamped to +-1 when
+ * cfg->has_final_clip).  tsteps: K device entries BY DIFFUSION TIME (entry t: t, c0 = sqrt(1/abar_t), c1 = sqrt(1/abar_t - 1),
+ * c2, c3 = the posterior mean's coefficients of x0 and x).  The observations come from `batch` (only obs, inds and the ring
+ * geometry are read).  noise_bc (N, Ta*Da), t_bc (N,) int64 (clamped into [0, K)) and the two (K,) q_sample tables belong to the
+ * behaviour-cloning term bc = mse(eps_theta(sa[t_bc] a + sb[t_bc] noise_bc, t_bc, obs), noise_bc).
+ *
+ * loss = bc + eta * q_loss, q_loss = -mean(q_i) / mean|q_j| at (obs, a) with i = which, j = 1 - which (which = 0 is the
+ * reference's `np.random.uniform() > 0.5` branch); mean|q_j| carries no gradient.  One forward over the (K + 1) N rows
+ * (K chain slabs step-major, then the BC slab) keeps the activations; masks[n][s][j] = 1 where the x0 clamp of the step at position
+ * s passes the gradient, |c0 x - c1 eps| <= cfg->denoised_clip (all ones without a clip).  Then only d loss / d x walks the chain,
+ * last step first: per slab the trunk's data-gradient GEMMs and one launch that multiplies dh_0 with the x columns of W0 (K = hidden,
+ * fp32 accumulate in index order, one output per thread), applies the posterior's two terms and writes d eps of the slab before.
+ * The weight-gradient GEMMs, column sums, the time-embedding gradient and the encoder's backward then run ONCE over all rows:
+ * their launch count does not grow with K.  The critic contributes dQ_which/da through its data-gradient chain alone (no
+ * parameter gradient of the critic is computed); its scale -eta / (N mean|q_j|) is read from device memory.  A row's d_a and
+ * masks depend on that row alone.
+ *
+ * actor_grad <- d loss / d actor params (flat, OVERWRITTEN); stats[5] <- {loss, bc, q_loss, mean q1, mean q2} (device doubles,
+ * fixed summation order); masks (N, K, Ta*Da) bytes and d_a (N, Ta*Da) = d loss / d a are optional (NULL).  Residual actors
+ * without LayerNorm, with or without cond_mlp, on the layered GEMM path whatever the shape; plain Q trunks (as dppo_qsm_actor_target). */
+#define DPPO_DQL_STAT_COUNT 5
+int64_t dppo_dql_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int K);
+int dppo_dql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
+                           const void* actor_packed, const float* q_params, const void* q1_packed, const void* q2_packed,
+                           const dppo_diffusion_cfg* cfg, const dppo_step* tsteps, int K, const dppo_idql_batch* batch, int obs_dim,
+                           int64_t N, const float* chains, const float* noise_bc, const int64_t* t_bc,
+                           const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod, double eta, int which,
+                           float* actor_grad, double* stats, uint8_t* masks, float* d_a, void* workspace, int64_t workspace_bytes,
+                           dppo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
