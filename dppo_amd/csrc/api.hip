@@ -1968,6 +1968,13 @@ static int check_gauss(const dppo_net_desc* actor, const dppo_gaussian_cfg* cfg,
   if (cfg->std_mode == 0 && !(cfg->fixed_std > 0)) return fail(-1, "fixed_std must be positive");
   return 0;
 }
+// what the two training entries (PPO, behaviour cloning) refuse on top of check_gauss(); the inference entries take any Ta*Da
+static int check_gauss_train(const dppo_net_desc* actor, const dppo_gaussian_cfg* cfg, const float* logvar_grad) {
+  if (cfg->std_mode == 1 && !logvar_grad) return fail(-1, "std_mode 1 needs logvar_grad");
+  if (cfg->std_mode == 1 && actor->out_dim > 768)
+    return fail(-1, "Ta * Da above 768 with a learned std (the logvar terms of one block live in shared memory)");
+  return 0;
+}
 template <class P>
 static size_t carve_gauss(Carver& c, const dppo_net_desc& a, const dppo_net_desc* cr, int64_t N, bool train, MlpBufs<P>& A,
                           MlpBufs<P>& Cb, double*& moments, double*& scratch, double*& partial) {
@@ -2091,7 +2098,7 @@ static int gauss_ppo_entry(const dppo_net_desc* actor, const dppo_net_desc* crit
   if (!actor_params || !actor_packed || !critic_params || !critic_packed || !obs || !actions || !returns || !oldvalues ||
       !adv || !oldlogp || !actor_grad || !critic_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  if (cfg->std_mode == 1 && !logvar_grad) return fail(-1, "std_mode 1 needs logvar_grad");
+  if (int e = check_gauss_train(actor, cfg, logvar_grad)) return e;
   if (N < 2 || N > 0x7fffffff) return fail(-1, "N out of range");
 #define CALL(P)                                                                                                          \
   gauss_ppo_impl<P>(*actor, *critic, actor_params, (const char*)actor_packed, critic_params, (const char*)critic_packed, *cfg, \
@@ -2163,10 +2170,8 @@ int dppo_gaussian_bc_loss_fwd_bwd(const dppo_net_desc* actor, int prec, const fl
   if (int e = check_gauss(actor, cfg, logvar)) return e;
   if (int e = check_prec(prec)) return e;
   if (!params || !packed || !obs || !actions || !grad || !loss_entropy || !workspace) return fail(-1, "null pointer");
-  if (cfg->std_mode == 1 && !logvar_grad) return fail(-1, "std_mode 1 needs logvar_grad");
+  if (int e = check_gauss_train(actor, cfg, logvar_grad)) return e;
   if (cfg->deterministic) return fail(-1, "the behaviour-cloning loss is not defined for deterministic = 1");
-  if (cfg->std_mode == 1 && actor->out_dim > 768)
-    return fail(-1, "Ta * Da above 768 with a learned std (the logvar terms of one block live in shared memory)");
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
 #define CALL(P)                                                                                                              \
   gauss_bc_impl<P>(*actor, params, (const char*)packed, *cfg, logvar, obs, actions, N, ent_coef, grad, logvar_grad, loss_entropy, \
@@ -2188,6 +2193,16 @@ static int check_gmm(const dppo_net_desc* mean, const dppo_net_desc* wts, const 
   if (mean->cond_dim != wts->cond_dim) return fail(-1, "the two trunks observe different cond_dim");
   if (cfg->std_mode != 0 && cfg->std_mode != 1) return fail(-1, "std_mode must be 0 or 1");
   if (cfg->std_mode == 1 && !logvar) return fail(-1, "std_mode 1 needs logvar");
+  return 0;
+}
+// what the two training entries (PPO, behaviour cloning) refuse on top of check_gmm(): carve_gmm() reserves GMM_MAX_MODES x 64
+// logvar columns per block of partials, and the loss kernels keep num_modes * Ta * Da floats per sample in shared memory
+// (action_dim <= 64 is conservative: the carve holds any num_modes * action_dim <= GMM_MAX_MODES * 64)
+static int check_gmm_train(const dppo_gmm_cfg* cfg, const float* logvar_grad) {
+  if (cfg->std_mode == 1 && !logvar_grad) return fail(-1, "std_mode 1 needs logvar_grad");
+  if (cfg->action_dim > 64) return fail(-1, "action_dim above 64 (the logvar partials hold %d x 64 columns)", GMM_MAX_MODES);
+  if ((int64_t)cfg->num_modes * cfg->horizon_steps * cfg->action_dim > 3072)
+    return fail(-1, "num_modes * Ta * Da above 3072 (the logvar terms of one block live in shared memory)");
   return 0;
 }
 template <class P>
@@ -2316,7 +2331,7 @@ int dppo_gmm_ppo_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* we
   if (!mean_params || !mean_packed || !weights_params || !weights_packed || !critic_params || !critic_packed || !obs || !actions ||
       !returns || !oldvalues || !adv || !oldlogp || !mean_grad || !weights_grad || !critic_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  if (cfg->std_mode == 1 && !logvar_grad) return fail(-1, "std_mode 1 needs logvar_grad");
+  if (int e = check_gmm_train(cfg, logvar_grad)) return e;
   if (N < 2 || N > 0x7fffffff) return fail(-1, "N out of range");
 #define CALL(P)                                                                                                                  \
   gmm_ppo_impl<P>(*mean, *weights, *critic, mean_params, (const char*)mean_packed, weights_params, (const char*)weights_packed,        \
@@ -2374,12 +2389,9 @@ int dppo_gmm_bc_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* wei
   if (!mean_params || !mean_packed || !weights_params || !weights_packed || !obs || !actions || !mean_grad || !weights_grad ||
       !loss_entropy || !workspace)
     return fail(-1, "null pointer");
-  if (cfg->std_mode == 1 && !logvar_grad) return fail(-1, "std_mode 1 needs logvar_grad");
+  if (int e = check_gmm_train(cfg, logvar_grad)) return e;
   if (cfg->std_mode == 0 && !(cfg->fixed_std > 0)) return fail(-1, "fixed_std must be positive");
   if (cfg->deterministic) return fail(-1, "the behaviour-cloning loss is not defined for deterministic = 1");
-  if (cfg->action_dim > 64) return fail(-1, "action_dim above 64 (the logvar partials hold %d x 64 columns)", GMM_MAX_MODES);
-  if ((int64_t)cfg->num_modes * cfg->horizon_steps * cfg->action_dim > 3072)
-    return fail(-1, "num_modes * Ta * Da above 3072 (the logvar terms of one block live in shared memory)");
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
 #define CALL(P)                                                                                                                   \
   gmm_bc_impl<P>(*mean, *weights, mean_params, (const char*)mean_packed, weights_params, (const char*)weights_packed, *cfg, logvar, \

@@ -317,7 +317,8 @@ int dppo_gaussian_logprob(const dppo_net_desc* actor, int prec, const float* par
                           int64_t N, float* logp, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
 /* obs (N,cond), actions (N,Ta*Da), returns / oldvalues / adv / oldlogp (N,).  global_moments as in
  * dppo_ppo_loss_fwd_bwd.  Writes d pg_loss / d actor params, d v_loss / d critic params, d pg_loss / d logvar (Da; only
- * std_mode 1, may be NULL otherwise) and stats[DPPO_GAUSS_STAT_COUNT]. */
+ * std_mode 1, may be NULL otherwise) and stats[DPPO_GAUSS_STAT_COUNT].  Built for Ta*Da <= 768 when the std is learned
+ * (refused otherwise, as by dppo_gaussian_bc_loss_fwd_bwd). */
 int dppo_gaussian_ppo_loss_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* critic, int prec,
                                    const float* actor_params, const void* actor_packed, const float* critic_params,
                                    const void* critic_packed, const dppo_gaussian_cfg* cfg, const float* logvar,
@@ -634,7 +635,8 @@ int dppo_gmm_logprob(const dppo_net_desc* mean, const dppo_net_desc* weights, in
                      const float* logvar, const float* obs, const float* actions, int64_t N, float* logp, void* workspace,
                      int64_t workspace_bytes, dppo_stream_t stream);
 /* stats as dppo_gaussian_ppo_loss_fwd_bwd (entropy = mean_b sum_m pi_m H_m, std = mean_b sum_m pi_m mean_j sigma_mj).
- * mean_grad / weights_grad / logvar_grad (num_modes*Da) <- d (pg_loss + ent_coef * entropy_loss), critic_grad <- d v_loss. */
+ * mean_grad / weights_grad / logvar_grad (num_modes*Da) <- d (pg_loss + ent_coef * entropy_loss), critic_grad <- d v_loss.
+ * Built for action_dim <= 64 and num_modes*Ta*Da <= 3072 (refused otherwise, as by dppo_gmm_bc_loss_fwd_bwd). */
 int dppo_gmm_ppo_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* weights, const dppo_net_desc* critic, int prec,
                               const float* mean_params, const void* mean_packed, const float* weights_params,
                               const void* weights_packed, const float* critic_params, const void* critic_packed,
