@@ -13,6 +13,7 @@
 #include "idql.h"
 #include "qsm.h"
 #include "dql.h"
+#include "sac.h"
 #include "unet.h"
 #include "sampler.h"
 
@@ -2883,13 +2884,12 @@ int64_t dppo_qsm_actor_target_workspace_bytes(const dppo_net_desc* q, int prec, 
     return carve_qsm_target<decltype(p)>(c, *q, q->in_dim - obs_dim, N, W);
   });
 }
-// d q / d x of one plain trunk, data gradients only, down to dh_0 = d q / d (layer 0's pre-activation), written into its half
-// of dhcat (row stride 2H)
+// The chain behind its seed: dza holds d q / d (pre-activation of the last hidden layer); data gradients only, down to dh_0 =
+// d q / d (layer 0's pre-activation), written into its half of dhcat (row stride 2H)
 template <class P>
-static void qsm_action_chain(const dppo_net_desc& q, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B, void* dza,
-                             void* dzb, void* dh0, hipStream_t s) {
+static void qsm_chain_gemms(const dppo_net_desc& q, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B, void* dza,
+                            void* dzb, void* dh0, hipStream_t s) {
   const int H = q.hidden, nb = q.n_blocks;
-  launch_qsm_seed<P>(pk + L.Wout, B.z1[nb - 1], N, H, q.act, dza, s);
   void* dz = dza;
   void* other = dzb;
   for (int b = nb - 1; b >= 0; --b) {  // dz <- (dz . W1_b) (.) act'(pre-activation below): backward_plain's step without its dW / db
@@ -2902,6 +2902,13 @@ static void qsm_action_chain(const dppo_net_desc& q, const char* pk, const PackL
     void* t = dz;
     dz = other, other = t;
   }
+}
+// d q / d x of one plain trunk: the seed (out_dim is 1, so Wout is broadcast), then the chain
+template <class P>
+static void qsm_action_chain(const dppo_net_desc& q, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B, void* dza,
+                             void* dzb, void* dh0, hipStream_t s) {
+  launch_qsm_seed<P>(pk + L.Wout, B.z1[q.n_blocks - 1], N, q.hidden, q.act, dza, s);
+  qsm_chain_gemms<P>(q, pk, L, N, B, dza, dzb, dh0, s);
 }
 template <class P>
 static int qsm_target_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const dppo_idql_batch& b,
@@ -3267,6 +3274,276 @@ int dppo_dql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, i
               which, actor_grad, stats, masks, d_a, workspace, workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
+}
+
+// ---- SAC (sac.hip): tanh-Gaussian actor with a state-dependent std, entropy-regularised twin-Q, temperature --------------------
+static int check_sac_actor(const dppo_net_desc* a) {
+  if (int e = check_net(a)) return e;
+  if (a->kind != 1 || !a->plain)
+    return fail(-1, "the SAC actor is a kind-1 plain trunk (Gaussian_MLP with fixed_std=None, residual_style=False); a residual actor is not built");
+  if (a->out_dim % 2) return fail(-1, "the SAC actor's out_dim=%d must be 2 * Ta*Da ([mean | raw logvar])", a->out_dim);
+  return 0;
+}
+static int check_sac_cfg(const dppo_net_desc* a, const dppo_sac_cfg* cfg) {
+  if (!cfg) return fail(-1, "null cfg");
+  if (cfg->horizon_steps < 1 || cfg->action_dim < 1 || 2 * cfg->horizon_steps * cfg->action_dim != a->out_dim)
+    return fail(-1, "2 * Ta*Da != actor out_dim");
+  if (!(cfg->logvar_min <= cfg->logvar_max)) return fail(-1, "logvar_min must not exceed logvar_max");
+  if (!(cfg->randn_clip >= 0.f)) return fail(-1, "randn_clip must be >= 0");
+  if ((cfg->deterministic != 0 && cfg->deterministic != 1) || (cfg->squash != 0 && cfg->squash != 1))
+    return fail(-1, "deterministic and squash must be 0 or 1");
+  return 0;
+}
+static SacHead sac_head_of(const dppo_sac_cfg& cfg, const float* out, int ldo, int AF, const float* noise, int64_t N) {
+  SacHead h;
+  memset(&h, 0, sizeof(h));
+  h.cfg = cfg, h.half_span = 0.5f * (cfg.logvar_max - cfg.logvar_min), h.out = out, h.ldo = ldo, h.AF = AF, h.noise = noise;
+  h.ring.N = N, h.ring.AD = AF;
+  return h;
+}
+template <class P>
+static size_t carve_sac_sample(Carver& c, const dppo_net_desc& a, int64_t B, MlpBufs<P>& A) {
+  carve_mlp<P>(c, a, B, false, false, A);
+  return al256(c.off);
+}
+int64_t dppo_sac_sample_workspace_bytes(const dppo_net_desc* actor, int prec, int64_t B) {
+  if (check_sac_actor(actor) || check_prec(prec)) return -1;
+  if (B < 1 || B > 0x7fffffff) return fail(-1, "B out of range");
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    MlpBufs<decltype(p)> A;
+    return carve_sac_sample<decltype(p)>(c, *actor, B, A);
+  });
+}
+template <class P>
+static int sac_sample_impl(const dppo_net_desc& d, const float* prm, const char* pk, const dppo_sac_cfg& cfg, const float* obs,
+                           const float* noise, int64_t B, float* actions, float* logp, float* u_out, void* ws, int64_t wsb,
+                           hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  MlpBufs<P> A;
+  const size_t need = carve_sac_sample<P>(c, d, B, A);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout L = pack_layout<P>(d, 0);
+  launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, d.cond_dim, B, A.in, L.Kp0, s);
+  mlp_forward<P>(d, prm, pk, L, B, A, false, s);
+  SacHead h = sac_head_of(cfg, A.out, A.ldout, d.out_dim / 2, noise, B);
+  h.actions = actions, h.logp = logp, h.u_out = u_out;
+  launch_sac_head<P>(h, s);
+  return check_launch();
+}
+int dppo_sac_sample(const dppo_net_desc* actor, int prec, const float* params, const void* packed, const dppo_sac_cfg* cfg,
+                    const float* obs, const float* noise, int64_t B, float* actions, float* logp, float* u_out, void* workspace,
+                    int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_sac_actor(actor)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (int e = check_sac_cfg(actor, cfg)) return e;
+  if (!params || !packed || !obs || !actions || !workspace) return fail(-1, "null pointer");
+  if (B < 1 || B > 0x7fffffff) return fail(-1, "B out of range");
+#define CALL(P)                                                                                                             \
+  sac_sample_impl<P>(*actor, params, (const char*)packed, *cfg, obs, noise, B, actions, logp, u_out, workspace, workspace_bytes, \
+                     (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+int64_t dppo_sac_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
+  return dppo_qsm_q_loss_workspace_bytes(q, prec, obs_dim, N);  // the same four trunks, partials and gathered rows
+}
+template <class P>
+static int sac_td_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const float* tp, const char* tk1,
+                       const char* tk2, const dppo_idql_batch& b, int OD, const float* next_actions, const float* next_logp,
+                       const double* alpha, int64_t N, double gamma, float* qgrad, double* stats, void* ws, int64_t wsb,
+                       hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  QsmTdWs<P> W;
+  const size_t need = carve_qsm_td<P>(c, q, N, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout L = pack_layout<P>(q, 0);
+  const int64_t nq = param_layout(q).total;
+  QsmTdRows r;
+  memset(&r, 0, sizeof(r));
+  r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
+  r.next_actions = next_actions, r.q1in = W.Q1.in, r.q2in = W.Q2.in, r.t1in = W.T1.in, r.t2in = W.T2.in, r.KpQ = L.Kp0;
+  r.r_out = W.r, r.term_out = W.term;
+  launch_qsm_td_rows<P>(r, s);
+  // the four trunks side by side and the joins as in qsm_td_impl
+  hipStream_t s2 = fork_side(s, 0), s3 = fork_side(s, 1), s4 = fork_side(s, 2);
+  mlp_forward<P>(q, qp + nq, qk2, L, N, W.Q2, true, s2);
+  mlp_forward<P>(q, tp, tk1, L, N, W.T1, false, s3);
+  mlp_forward<P>(q, tp + nq, tk2, L, N, W.T2, false, s4);
+  mlp_forward<P>(q, qp, qk1, L, N, W.Q1, true, s);
+  if (s4 != s) {
+    if (s2 != s) join_side(s4, s2, 0);
+    if (s3 != s) join_side(s4, s3, 1);
+    join_side(s, s4, 2);
+  } else {
+    if (s2 != s) join_side(s, s2, 0);
+    if (s3 != s) join_side(s, s3, 1);
+  }
+  IdqlLoss l;
+  memset(&l, 0, sizeof(l));
+  l.q1 = W.Q1.out, l.q2 = W.Q2.out, l.ldq = W.Q1.ldout, l.v = W.T1.out, l.v2 = W.T2.out, l.ldv = W.T1.ldout, l.N = N;
+  l.reward = W.r, l.terminated = W.term, l.gamma = (float)gamma, l.d_a = W.Q1.d_out, l.d_b = W.Q2.d_out;
+  l.ldd = L.Kpo, l.partial = W.partial, l.stats = stats;
+  l.next_logp = next_logp, l.alpha = alpha;  // the entropy term of the bootstrap
+  launch_idql_q_loss<P>(l, s);
+  s2 = fork_side(s, 0);
+  mlp_backward<P>(q, qp + nq, qk2, L, N, W.Q2, qgrad + nq, nullptr, nullptr, 0, s2);
+  mlp_backward<P>(q, qp, qk1, L, N, W.Q1, qgrad, nullptr, nullptr, 0, s);
+  if (s2 != s) join_side(s, s2, 0);
+  return check_launch();
+}
+int dppo_sac_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                            const float* target_q_params, const void* target_q1_packed, const void* target_q2_packed,
+                            const dppo_idql_batch* batch, int obs_dim, const float* next_actions, const float* next_logp,
+                            const double* alpha, int64_t N, double gamma, float* q_grad, double* stats, void* workspace,
+                            int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_qsm_q(q, obs_dim)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!q_params || !q1_packed || !q2_packed || !target_q_params || !target_q1_packed || !target_q2_packed || !next_actions ||
+      !next_logp || !alpha || !q_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
+#define CALL(P)                                                                                                                \
+  sac_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
+                 (const char*)target_q2_packed, *batch, obs_dim, next_actions, next_logp, alpha, N, gamma, q_grad, stats,      \
+                 workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+static int check_sac_pair(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim) {
+  if (int e = check_sac_actor(a)) return e;
+  if (int e = check_qsm_q(q, obs_dim)) return e;
+  if (int e = check_qsm_plain(q)) return e;
+  if (a->cond_dim != obs_dim || q->in_dim - obs_dim != a->out_dim / 2)
+    return fail(-1, "actor / Q descriptors do not pair: actor cond_dim=%d, Ta*Da=%d against obs_dim=%d, Q in_dim=%d", a->cond_dim,
+                a->out_dim / 2, obs_dim, q->in_dim);
+  return 0;
+}
+template <class P>
+struct SacWs {
+  MlpBufs<P> A, Q1, Q2;
+  void *dza[2], *dzb[2], *dhcat, *w0a;  // as QsmWs
+  float *actions, *logp, *sig, *qsel;
+  float* dout32;  // bf16 only: [N][2 AF] the head's gradient before its rounding to elem (SacTail::d_out32)
+  uint8_t* sel;
+};
+template <class P>
+static size_t carve_sac_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, SacWs<P>& W) {
+  const size_t ES = P::ESIZE;
+  const int AF = a.out_dim / 2;
+  carve_mlp<P>(c, a, N, true, true, W.A);
+  carve_mlp<P>(c, q, N, true, false, W.Q1);
+  carve_mlp<P>(c, q, N, true, false, W.Q2);
+  for (int i = 0; i < 2; ++i) {
+    W.dza[i] = c.take((size_t)N * q.hidden * ES);
+    W.dzb[i] = c.take((size_t)N * q.hidden * ES);
+  }
+  W.dhcat = c.take((size_t)N * 2 * q.hidden * ES);
+  W.w0a = c.take((size_t)AF * 2 * q.hidden * ES);
+  W.actions = (float*)c.take((size_t)N * AF * 4);
+  W.logp = (float*)c.take((size_t)N * 4);
+  W.sig = (float*)c.take((size_t)N * 4);
+  W.qsel = (float*)c.take((size_t)N * 4);
+  W.dout32 = ES == 4 ? nullptr : (float*)c.take((size_t)N * 2 * AF * 4);
+  W.sel = (uint8_t*)c.take((size_t)N);
+  return al256(c.off);
+}
+int64_t dppo_sac_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
+  if (check_sac_pair(actor, q, obs_dim) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    SacWs<decltype(p)> W;
+    return carve_sac_actor<decltype(p)>(c, *actor, *q, N, W);
+  });
+}
+template <class P>
+static int sac_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float* ap, const char* ak, const float* qp,
+                          const char* qk1, const char* qk2, const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N,
+                          const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
+                          uint8_t* sel_out, float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  SacWs<P> W;
+  const size_t need = carve_sac_actor<P>(c, a, q, N, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const ParamLayout plq = param_layout(q);
+  const int AF = a.out_dim / 2, H = q.hidden;
+  float* actions = actions_out != nullptr ? actions_out : W.actions;
+  float* logp = logp_out != nullptr ? logp_out : W.logp;
+  // the actor's rows [obs | 0], its forward with the activations kept, the head: sample, log-probability, the critic's rows
+  IdqlRows r = idql_rows_of(b, N, OD, AF);
+  r.vin = W.A.in, r.KpV = LA.Kp0;
+  launch_idql_rows<P>(r, s);
+  launch_qsm_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, H, W.w0a, s);
+  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
+  SacHead h = sac_head_of(cfg, W.A.out, W.A.ldout, AF, noise, N);
+  h.ring = idql_rows_of(b, N, OD, AF);
+  h.actions = actions, h.logp = logp, h.sig_row = W.sig, h.q1in = W.Q1.in, h.q2in = W.Q2.in, h.KpQ = LQ.Kp0;
+  launch_sac_head<P>(h, s);
+  // both Q forwards side by side; the choice of the twin per row seeds both data-gradient chains (the other trunk's seed is 0)
+  hipStream_t s2 = fork_side(s, 0);
+  mlp_forward<P>(q, qp + plq.total, qk2, LQ, N, W.Q2, true, s2);
+  mlp_forward<P>(q, qp, qk1, LQ, N, W.Q1, true, s);
+  if (s2 != s) join_side(s, s2, 0);
+  SacSelect sl;
+  memset(&sl, 0, sizeof(sl));
+  sl.q1 = W.Q1.out, sl.q2 = W.Q2.out, sl.ldq = W.Q1.ldout, sl.wout1 = qk1 + LQ.Wout, sl.wout2 = qk2 + LQ.Wout;
+  sl.z1 = W.Q1.z1[q.n_blocks - 1], sl.z2 = W.Q2.z1[q.n_blocks - 1], sl.N = N, sl.H = H, sl.act = q.act;
+  sl.dz1 = W.dza[0], sl.dz2 = W.dza[1], sl.sel = W.sel, sl.sel_out = sel_out, sl.qsel = W.qsel;
+  launch_sac_select<P>(sl, s);
+  s2 = fork_side(s, 0);
+  qsm_chain_gemms<P>(q, qk2, LQ, N, W.Q2, W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, s2);
+  qsm_chain_gemms<P>(q, qk1, LQ, N, W.Q1, W.dza[0], W.dzb[0], W.dhcat, s);
+  if (s2 != s) join_side(s, s2, 0);
+  SacTail tl;
+  memset(&tl, 0, sizeof(tl));
+  tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.H2 = 2 * H, tl.rows = qsm_tail_rows(2 * H), tl.alpha = alpha;
+  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
+  launch_sac_tail<P>(tl, s);
+  SacStats st;
+  memset(&st, 0, sizeof(st));
+  st.qsel = W.qsel, st.logp = logp, st.sig_row = W.sig, st.alpha = alpha, st.N = N, st.AF = AF, st.stats = stats;
+  launch_sac_stats(st, s);
+  mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s);
+  if (W.dout32 != nullptr)  // the two heads' bias gradient again, from the unrounded rows
+    launch_colsum<F32>(W.dout32, (int)N, 2 * AF, 2 * AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
+  return check_launch();
+}
+int dppo_sac_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
+                           const void* actor_packed, const float* q_params, const void* q1_packed, const void* q2_packed,
+                           const dppo_sac_cfg* cfg, const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise,
+                           const double* alpha, float* actor_grad, double* stats, float* d_a, float* logp_out, uint8_t* sel_out,
+                           float* actions_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_sac_pair(actor, q, obs_dim)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (int e = check_sac_cfg(actor, cfg)) return e;
+  if (cfg->deterministic) return fail(-1, "the actor loss samples: deterministic must be 0");
+  if (!actor_params || !actor_packed || !q_params || !q1_packed || !q2_packed || !alpha || !actor_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (!batch) return fail(-1, "null batch");
+  if (!batch->obs) return fail(-1, "null pointer in batch");
+  if (batch->cap < 1 || batch->n_envs < 1 || batch->count < 1 || batch->count > batch->cap || batch->head < 0 || batch->head >= batch->cap)
+    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
+  if (!batch->inds && N > batch->count * batch->n_envs)
+    return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N, (long long)(batch->count * batch->n_envs));
+#define CALL(P)                                                                                                                   \
+  sac_actor_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, \
+                    *cfg, *batch, obs_dim, N, noise, alpha, actor_grad, stats, d_a, logp_out, sel_out, actions_out, workspace,      \
+                    workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+int dppo_sac_alpha_loss(const float* logp, int64_t N, const double* log_alpha, double target_entropy, double* out,
+                        dppo_stream_t stream) {
+  if (!logp || !log_alpha || !out) return fail(-1, "null pointer");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (!(target_entropy >= -3.0e38 && target_entropy <= 3.0e38)) return fail(-1, "target_entropy=%g must be finite", target_entropy);
+  launch_sac_alpha_loss(logp, N, log_alpha, target_entropy, out, (hipStream_t)stream);
+  return check_launch();
 }
 
 // ---- optimiser ----------------------------------------------------------------------------------------

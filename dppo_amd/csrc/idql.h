@@ -41,6 +41,8 @@ __device__ __forceinline__ int64_t idql_ring_row(const IdqlRows& a, int64_t n) {
 struct IdqlLoss {
   const float *q1, *q2, *v;  // trunk outputs, column 0 of [N][ld]
   const float* v2;           // Q loss, or null: the bootstrap value is min(v, v2) (a target twin on the next rows: qsm.h)
+  const float* next_logp;    // Q loss, or null: [N]; the bootstrap value less alpha * next_logp[n] (the entropy term: sac.h)
+  const double* alpha;       // device scalar, read only with next_logp
   int ldq, ldv;
   const float *reward, *terminated;  // [N] (Q loss)
   int64_t N;

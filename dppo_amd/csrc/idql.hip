@@ -131,7 +131,7 @@ void launch_idql_v_loss(const IdqlLoss& a, hipStream_t s) {
 template void launch_idql_v_loss<F32>(const IdqlLoss&, hipStream_t);
 template void launch_idql_v_loss<BF16>(const IdqlLoss&, hipStream_t);
 
-// loss_critic_q (diffusion_idql.py:63-87; with v2, diffusion_qsm.py:65-95): target = r + gamma * v' * (1 - terminated);  loss = mean((q1 - target)^2) + mean((q2 - target)^2)
+// loss_critic_q (diffusion_idql.py:63-87; with v2, diffusion_qsm.py:65-95; with next_logp, gaussian_sac.py:31-59): target = r + gamma * v' * (1 - terminated);  loss = mean((q1 - target)^2) + mean((q2 - target)^2)
 template <class P>
 __global__ __launch_bounds__(256) void idql_q_loss_kernel(const IdqlLoss a) {
   __shared__ float g1[IDQL_RPB], g2[IDQL_RPB];
@@ -143,6 +143,10 @@ __global__ __launch_bounds__(256) void idql_q_loss_kernel(const IdqlLoss a) {
     const float mask = 1.f - a.terminated[nn];
     float nv = a.v[nn * a.ldv];
     if (a.v2 != nullptr) nv = fminf(nv, a.v2[nn * a.ldv]);
+    if (a.next_logp != nullptr) {
+      const float ent = (float)*a.alpha * a.next_logp[nn];
+      nv = nv - ent;
+    }
     const float target = a.reward[nn] + (a.gamma * nv) * mask;
     const float q1 = a.q1[nn * a.ldq];
     const float e1 = q1 - target;

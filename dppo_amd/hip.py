@@ -104,8 +104,15 @@ class IdqlBatch(C.Structure):  # struct dppo_idql_batch
                 ("head", C.c_int64), ("count", C.c_int64)]
 
 
+class SacCfg(C.Structure):  # struct dppo_sac_cfg
+    _fields_ = [("horizon_steps", C.c_int32), ("action_dim", C.c_int32), ("deterministic", C.c_int32), ("squash", C.c_int32),
+                ("logvar_min", C.c_float), ("logvar_max", C.c_float), ("randn_clip", C.c_float), ("pad", C.c_float),
+                ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
+
+
 IDQL_STAT_COUNT = 3
 DQL_STAT_COUNT = 5
+SAC_STAT_COUNT = 4
 
 DP_HOOK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)  # void (*)(void* user, dppo_stream_t side)
 
@@ -192,6 +199,17 @@ SYMBOLS = {
     "dppo_dql_actor_workspace_bytes": (_L, [_ND, _ND, _I, _I, _L, _I]),
     "dppo_dql_actor_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, _P, C.POINTER(DiffusionCfg), _P, _I, C.POINTER(IdqlBatch), _I, _L,
                                     _P, _P, _P, _P, _P, _D, _I, _P, _P, _P, _P, _P, _L, _P]),
+    # SAC: the two-headed tanh-Gaussian epilogue, the entropy-regularised TD loss, the actor loss through min(Q1, Q2), the
+    # temperature loss (csrc/sac.hip)
+    "dppo_sac_sample_workspace_bytes": (_L, [_ND, _I, _L]),
+    "dppo_sac_sample": (_I, [_ND, _I, _P, _P, C.POINTER(SacCfg), _P, _P, _L, _P, _P, _P, _P, _L, _P]),
+    "dppo_sac_q_loss_workspace_bytes": (_L, [_ND, _I, _I, _L]),
+    "dppo_sac_q_loss_fwd_bwd": (_I, [_ND, _I, _P, _P, _P, _P, _P, _P, C.POINTER(IdqlBatch), _I, _P, _P, _P, _L, _D, _P, _P, _P, _L,
+                                     _P]),
+    "dppo_sac_actor_workspace_bytes": (_L, [_ND, _ND, _I, _I, _L]),
+    "dppo_sac_actor_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, _P, C.POINTER(SacCfg), C.POINTER(IdqlBatch), _I, _L, _P, _P, _P,
+                                    _P, _P, _P, _P, _P, _P, _L, _P]),
+    "dppo_sac_alpha_loss": (_I, [_P, _L, _P, _D, _P, _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

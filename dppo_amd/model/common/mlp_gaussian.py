@@ -5,8 +5,10 @@ to [log std_min^2, log std_max^2]).  Parameter names match the reference state d
 fused trunk kernels); this class owns parameters only.
 
 Built: ``residual_style=True`` with ``fixed_std`` given -- the d3il / furniture fine-tuning cfgs (7 of the 10 shipped
-PPO_Gaussian cfgs).  Not built (raises): the state-dependent ``mlp_logvar`` head on a plain ``MLP`` base (``fixed_std=None``,
-the three gym ``scratch`` cfgs) and plain (non-residual) trunks.
+PPO_Gaussian cfgs) -- and the SAC actor: the state-dependent ``mlp_logvar`` head on a plain ``MLP`` base (``fixed_std=None``,
+``tanh_output=False``, ``residual_style=False``; reference :304-321, 370-379).  Not built (raises): the state-dependent head
+with ``tanh_output=True`` (walker2d pre-training, the three gym ``scratch`` PPO cfgs: no BC / PPO loss exists for it) and plain
+(non-residual) trunks with a fixed std.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import torch
 from torch import nn
 
 from dppo_amd import hip
-from dppo_amd.model.common.mlp import HipNet, ResidualMLP
+from dppo_amd.model.common.mlp import SUPPORTED_ACT, HipNet, ResidualMLP
 from dppo_amd.model.common.vit import VisionMixin
 
 
@@ -25,14 +27,19 @@ class Gaussian_MLP(HipNet):
                  tanh_output=True, residual_style=False, use_layernorm=False, dropout=0.0, fixed_std=None,
                  learn_fixed_std=False, std_min=0.01, std_max=1, precision="bf16"):
         super().__init__()
-        if fixed_std is None:
-            raise NotImplementedError("dppo_amd: Gaussian_MLP with a state-dependent logvar head (fixed_std=None) is not built")
-        if not residual_style:
+        if fixed_std is None and (tanh_output or residual_style):
+            raise NotImplementedError("dppo_amd: Gaussian_MLP with a state-dependent logvar head (fixed_std=None) is built for "
+                                      "tanh_output=False on a plain trunk only (the SAC actor); no BC / PPO loss exists for it")
+        if fixed_std is not None and not residual_style:
             raise NotImplementedError("dppo_amd: Gaussian_MLP needs residual_style=True (plain MLP trunk not built)")
         if dropout:
             raise NotImplementedError("Dropout not implemented for residual MLP!")
         self.action_dim, self.horizon_steps, self.cond_dim = action_dim, horizon_steps, cond_dim
         out_dim = action_dim * horizon_steps
+        if fixed_std is None:
+            self._init_state_dependent(cond_dim, list(mlp_dims), out_dim, activation_type, use_layernorm, std_min, std_max,
+                                       precision)
+            return
         self.mlp_mean = ResidualMLP([cond_dim] + list(mlp_dims) + [out_dim], activation_type=activation_type,
                                     out_activation_type="Identity", use_layernorm=use_layernorm)
         if learn_fixed_std:  # initialised to fixed_std (reference :331-336)
@@ -42,6 +49,38 @@ class Gaussian_MLP(HipNet):
         self.logvar_max = nn.Parameter(torch.log(torch.tensor(std_max ** 2)), requires_grad=False)
         self.use_fixed_std, self.fixed_std, self.learn_fixed_std = True, fixed_std, learn_fixed_std
         self.tanh_output = tanh_output
+        self.prec = hip.PREC_BY_NAME[precision]
+        self._cache_clamp_bounds()
+
+    def _init_state_dependent(self, cond_dim, mlp_dims, out_dim, activation_type, use_layernorm, std_min, std_max, precision):
+        """The state-dependent std (reference :304-321, 370-379): ``mlp_base`` = plain [cond] + mlp_dims with the hidden
+        activation on its last layer too, ``mlp_mean`` and ``mlp_logvar`` one Linear(H, Ta*Da) each.  To the library this is ONE
+        plain trunk with out_dim = 2 Ta*Da whose last layer is the two heads stacked (rows [0, AF) the mean's, [AF, 2 AF) the raw
+        logvar's); the squash of the SAMPLE and the log-probability are the caller's (``SAC_Gaussian``, csrc/sac.hip)."""
+        if use_layernorm:
+            raise NotImplementedError("dppo_amd: plain MLP with LayerNorm / dropout / appended inputs is not built")
+        H = mlp_dims[-1]
+        if len(mlp_dims) < 2 or any(d != H for d in mlp_dims) or H % 64:
+            raise NotImplementedError("dppo_amd: plain MLP needs >= 2 hidden layers of one width (a multiple of 64)")
+        if activation_type not in SUPPORTED_ACT:
+            raise NotImplementedError(f"dppo_amd: activation {activation_type!r} not built (ReLU, Mish are)")
+
+        def stack(dims):  # reference MLP's module names: moduleList.{i}.linear_1
+            m = nn.Module()
+            m.moduleList = nn.ModuleList()
+            for i in range(len(dims) - 1):
+                layer = nn.Module()
+                layer.linear_1 = nn.Linear(dims[i], dims[i + 1])
+                m.moduleList.append(layer)
+            return m
+        # (registration order is the reference's state-dict order: logvar_min, logvar_max come first there)
+        self.logvar_min = nn.Parameter(torch.log(torch.tensor(std_min ** 2)), requires_grad=False)
+        self.logvar_max = nn.Parameter(torch.log(torch.tensor(std_max ** 2)), requires_grad=False)
+        self.mlp_base = stack([cond_dim] + mlp_dims)
+        self.mlp_mean = stack([H, out_dim])
+        self.mlp_logvar = stack([H, out_dim])
+        self.hidden, self.n_blocks, self.act = H, len(mlp_dims) - 1, SUPPORTED_ACT[activation_type]
+        self.use_fixed_std, self.fixed_std, self.learn_fixed_std, self.tanh_output = False, None, False, False
         self.prec = hip.PREC_BY_NAME[precision]
         self._cache_clamp_bounds()
 
@@ -55,10 +94,18 @@ class Gaussian_MLP(HipNet):
         self._cache_clamp_bounds()  # a checkpoint carries logvar_min / logvar_max
 
     def trunk_parameters(self):
+        if not self.use_fixed_std:  # the plain layout wants W (2 AF x H) then b (2 AF): [..., Wm, Wl, bm, bl]
+            m, l = self.mlp_mean.moduleList[0].linear_1, self.mlp_logvar.moduleList[0].linear_1
+            return list(self.mlp_base.parameters()) + [m.weight, l.weight, m.bias, l.bias]
         return list(self.mlp_mean.parameters())
 
     def net_desc(self) -> hip.NetDesc:
         d = self.__dict__.get("_desc_cache")
+        if d is None and not self.use_fixed_std:
+            d = hip.NetDesc(kind=1, in_dim=self.cond_dim, hidden=self.hidden, n_blocks=self.n_blocks,
+                            out_dim=2 * self.action_dim * self.horizon_steps, act=self.act, time_dim=0, act_flat=0,
+                            cond_dim=self.cond_dim, cond_hidden=0, cond_out=0, use_layernorm=0, plain=1)
+            object.__setattr__(self, "_desc_cache", d)
         if d is None:
             m = self.mlp_mean
             d = hip.NetDesc(kind=1, in_dim=self.cond_dim, hidden=m.hidden, n_blocks=m.n_blocks, out_dim=m.out_dim, act=m.act,
@@ -67,7 +114,14 @@ class Gaussian_MLP(HipNet):
             object.__setattr__(self, "_desc_cache", d)
         return d
 
+    def sac_cfg(self, deterministic=False, randn_clip=10.0, squash=True) -> hip.SacCfg:
+        return hip.SacCfg(horizon_steps=self.horizon_steps, action_dim=self.action_dim, deterministic=int(bool(deterministic)),
+                          squash=int(bool(squash)), logvar_min=self._lv_bounds[0], logvar_max=self._lv_bounds[1],
+                          randn_clip=float(randn_clip), pad=0.0, seed_lo=0, seed_hi=0)
+
     def gaussian_cfg(self, deterministic=False, randn_clip=10.0) -> hip.GaussianCfg:
+        if not self.use_fixed_std:
+            raise NotImplementedError("dppo_amd: no BC / PPO loss exists for a state-dependent std (SAC_Gaussian samples it)")
         return hip.GaussianCfg(
             horizon_steps=self.horizon_steps, action_dim=self.action_dim, tanh_mean=int(bool(self.tanh_output)),
             std_mode=1 if self.learn_fixed_std else 0, norm_adv=1, has_vclip=0, deterministic=int(bool(deterministic)), pad=0,
@@ -82,6 +136,8 @@ class Gaussian_MLP(HipNet):
         """cond {"state": (B,To,Do)} -> (mean (B,Ta*Da), scale (B,Ta*Da)), like the reference's forward (inference only:
         the differentiable evaluation is fused into ``PPO_Gaussian.loss``)."""
         import ctypes as C
+        if not self.use_fixed_std:
+            raise NotImplementedError("dppo_amd: the state-dependent head is evaluated inside SAC_Gaussian (dppo_sac_sample)")
         state = cond["state"]
         hip.require_gpu(state, "Gaussian_MLP.forward")
         B = state.shape[0]

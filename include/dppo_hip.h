@@ -867,6 +867,68 @@ int dppo_dql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, i
                            float* actor_grad, double* stats, uint8_t* masks, float* d_a, void* workspace, int64_t workspace_bytes,
                            dppo_stream_t stream);
 
+/* ---- SAC: soft actor-critic (tanh-Gaussian actor with a state-dependent std, entropy-regularised twin-Q, temperature) --------
+ * Replaces model/rl/gaussian_sac.py:31-88 (SAC_Gaussian.loss_critic / loss_actor / loss_temperature; update_target_critic is
+ * dppo_polyak), the get_logprob / reparameterize / tanh_output branches of model/common/gaussian.py:85-120 and the mlp_logvar
+ * head of model/common/mlp_gaussian.py:304-321, 370-379.  State observations only.
+ *
+ * The actor is a kind-1 PLAIN descriptor with out_dim = 2 AF, AF = Ta*Da: mlp_base is its trunk, and its last layer is the two
+ * heads stacked -- rows [0, AF) of the weight are mlp_mean's, rows [AF, 2 AF) mlp_logvar's, the bias likewise.  Per element j of a
+ * row, with mu = out[j], raw = out[AF + j], z the draw (noise (B, AF), or NULL: Philox4x32-10 keyed by cfg->seed_lo / seed_hi,
+ * counter = element index, as dppo_gaussian_sample) and zc = clamp(z, +-randn_clip):
+ *   lv = logvar_min + (0.5f * (logvar_max - logvar_min)) * (tanh(raw) + 1);  sigma = exp(0.5 lv) (1e-4 when deterministic);
+ *   u = mu + sigma zc;  a = tanh(u) (squash) or u;
+ *   logp = SUM_j [-0.5 zc^2 - log sigma - 0.5 log 2 pi] - SUM_j log(1 - a^2 + 1e-6) (the second sum only with squash).
+ * 1 - a^2 is formed as 4 e / (1 + e)^2 with e = exp(-2 |u|): it does not cancel where 1 - tanhf(u)^2 is 0 in fp32.
+ * The critic is the twin of the IDQL / QSM entries (plain trunks for the actor loss); batches are dppo_idql_batch.  alpha and
+ * log_alpha are DEVICE doubles: no call reads the device on the host. */
+typedef struct dppo_sac_cfg {
+  int32_t horizon_steps, action_dim;
+  int32_t deterministic; /* sigma = 1e-4                                                       */
+  int32_t squash;        /* GaussianModel.tanh_output: tanh applied to the SAMPLE               */
+  float logvar_min, logvar_max; /* log std_min^2, log std_max^2                                 */
+  float randn_clip;
+  float pad;
+  uint32_t seed_lo, seed_hi;
+} dppo_sac_cfg;
+/* actions (B, AF) <- a;  logp (B,) and u_out (B, AF) optional (NULL).  One row builder, the trunk's forward, one epilogue launch. */
+int64_t dppo_sac_sample_workspace_bytes(const dppo_net_desc* actor, int prec, int64_t B);
+int dppo_sac_sample(const dppo_net_desc* actor, int prec, const float* params, const void* packed, const dppo_sac_cfg* cfg,
+                    const float* obs, const float* noise, int64_t B, float* actions, float* logp, float* u_out, void* workspace,
+                    int64_t workspace_bytes, dppo_stream_t stream);
+/* loss_critic: dppo_qsm_q_loss_fwd_bwd with the bootstrap min(tq1, tq2) - (float)alpha * next_logp:
+ * y = reward + ((float)gamma * that) * (1 - terminated) in fp32.  next_actions (N, AF) and next_logp (N,): the policy's sample at
+ * next_obs and its log-probability.  q_grad <- d loss / d [Q1 | Q2] params (flat, OVERWRITTEN); stats[3] <- {loss, mean q1, mean y}. */
+int64_t dppo_sac_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N);
+int dppo_sac_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                            const float* target_q_params, const void* target_q1_packed, const void* target_q2_packed,
+                            const dppo_idql_batch* batch, int obs_dim, const float* next_actions, const float* next_logp,
+                            const double* alpha, int64_t N, double gamma, float* q_grad, double* stats, void* workspace,
+                            int64_t workspace_bytes, dppo_stream_t stream);
+/* loss_actor = mean(-q_sel + (float)alpha * logp) on a reparameterised sample at the batch's observations (only obs, inds and the
+ * ring geometry are read), q_sel = min(q1, q2) per row (sel = 1 where q2 < q1; ties go to q1).  One call: the actor's forward with
+ * the activations kept, the head epilogue (which also writes the critic's rows [obs | a | 0]), both Q forwards side by side, one
+ * launch that picks sel and seeds both trunks' data-gradient chains (zero for the trunk a row did not select), the chains, one launch
+ * for the K = 2*hidden product with the stacked action columns whose epilogue is the head's backward
+ *   dL/du = (1/N) [-g s + alpha 2 a s / (s + 1e-6)], s = 1 - a^2;  dL/dmu = dL/du;  dL/dsigma = dL/du zc - alpha / (N sigma);
+ *   dL/draw = dL/dsigma 0.5 sigma 0.5 (logvar_max - logvar_min) (1 - tanh(raw)^2),
+ * then the plain trunk's backward.  The critic contributes g = dQ_sel/da through its data-gradient chain alone: no weight gradient,
+ * column sum or gradient buffer of the critic is touched.  actor_grad <- d loss / d actor params (flat, OVERWRITTEN);
+ * stats[4] <- {loss, mean q_sel, mean logp, mean sigma} (device doubles, fixed summation order).  Optional (NULL): d_a (N, AF) =
+ * d loss / d a through the critic, logp_out (N,), sel_out (N,) bytes, actions_out (N, AF).  A row's outputs depend on that row
+ * alone.  Plain actors and plain Q trunks only. */
+#define DPPO_SAC_STAT_COUNT 4
+int64_t dppo_sac_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N);
+int dppo_sac_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
+                           const void* actor_packed, const float* q_params, const void* q1_packed, const void* q2_packed,
+                           const dppo_sac_cfg* cfg, const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise,
+                           const double* alpha, float* actor_grad, double* stats, float* d_a, float* logp_out, uint8_t* sel_out,
+                           float* actions_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
+/* loss_temperature: out[2] <- {-alpha (mean logp + target_entropy), d/d log_alpha}, alpha = exp(*log_alpha); one block, doubles,
+ * fixed order. */
+int dppo_sac_alpha_loss(const float* logp, int64_t N, const double* log_alpha, double target_entropy, double* out,
+                        dppo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
