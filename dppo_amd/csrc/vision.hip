@@ -27,6 +27,13 @@ namespace {
 
 constexpr int MAX_DEPTH = 4;
 constexpr float LN_EPS = 1e-5f;
+// Dynamic LDS of the scalar attention kernels (one workgroup per (image, head), T tokens, head dimension HD).  A launch
+// above 64 KiB needs its limit raised (attn_attr); the limit asked for is a CU's whole LDS.
+constexpr size_t ATTN_LDS_DEFAULT = 64 * 1024, ATTN_LDS_MAX = 160 * 1024;
+constexpr size_t attn_fwd_lds(int T, int HD) { return (size_t)2 * T * HD * 4; }            // K, V
+constexpr size_t attn_bwd_lds(int T, int HD) { return ((size_t)4 * T * HD + 2 * T) * 4; }  // K, V, Q, dO, lse, Delta
+static_assert(attn_bwd_lds(240, 32) <= ATTN_LDS_MAX && attn_bwd_lds(158, 64) <= ATTN_LDS_MAX && attn_bwd_lds(159, 64) > ATTN_LDS_MAX,
+              "check_desc's message and include/dppo_hip.h state these ranges");
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -69,6 +76,10 @@ int check_desc(const dppo_vis_desc* d) {
   if (d->num_img < 1 || d->num_img > 2) return api_fail(-1, "vis: num_img must be 1 or 2");
   const int P = ((h1 - 3) / 2 + 1) * ((w1 - 3) / 2 + 1);
   if (P > 240) return api_fail(-1, "vis: more than 240 patches (the transposes and the attention keep one image's tokens in LDS)");
+  // the scalar attention backward is the largest launch (fp32 at any size; bf16 off the matrix-core path): head dimension 64
+  // fits 158 patches, 16 and 32 fit all 240
+  if (attn_bwd_lds(P, hd) > ATTN_LDS_MAX)
+    return api_fail(-1, "vis: too many patches for this head dimension (the attention backward keeps Q, K, V and dO of one head in LDS: at most 158 patches at head dimension 64)");
   return 0;
 }
 
@@ -844,7 +855,6 @@ __global__ __launch_bounds__(256) void vis_slab_out_kernel(const float* slab, in
 // ---------------------------------------------------------------------------------------------------------------------
 // runner: carves the workspace the same way for the forward and the backward call, so the tape is the workspace
 // ---------------------------------------------------------------------------------------------------------------------
-DevLatch g_attn_latch[2][3];
 int g_vis_mfma_attn = 1;  // tuning knob 20 (A/B against the scalar attention kernels)
 
 template <class P>
@@ -923,25 +933,27 @@ struct VisRunner {
   // bf16 with the shipped head geometry: attention on the matrix cores; otherwise (fp32 parity mode, other head sizes, more
   // than 128 tokens) the scalar kernels
   bool mfma_attn() const { return P::ESIZE == 2 && L.hd == 32 && L.P <= AT_T && g_vis_mfma_attn; }
-  template <class K>
-  void attn_attr(K kern, size_t lds, int which) {
-    const int hi = L.hd == 16 ? 0 : (L.hd == 32 ? 1 : 2);
-    if (lds > 64 * 1024 && g_attn_latch[which][hi].need()) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      g_attn_latch[which][hi].done();
+  // The limit belongs to ONE kernel function: vis_attn_{fwd,bwd}_kernel<P, HD> is a different function for each precision,
+  // head dimension and direction, so each instantiation of this template keeps its own per-device latch.
+  template <int HD, int BWD>
+  void attn_attr(const void* kern, size_t lds) {
+    static DevLatch latch;
+    if (lds > ATTN_LDS_DEFAULT && latch.need()) {
+      (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_LDS_MAX);
+      latch.done();
     }
   }
   template <int HD>
   void attn_fwd(int l) {
-    const size_t lds = (size_t)2 * L.P * HD * 4;
-    attn_attr(vis_attn_fwd_kernel<P, HD>, lds, 0);
+    const size_t lds = attn_fwd_lds(L.P, HD);
+    attn_attr<HD, 0>((const void*)vis_attn_fwd_kernel<P, HD>, lds);
     hipLaunchKernelGGL((vis_attn_fwd_kernel<P, HD>), dim3((unsigned)(NI * L.nh)), dim3(128), lds, s, qkv[l], L.P, L.D, L.nh,
                        1.f / sqrtf((float)HD), att[l], lse[l]);
   }
   template <int HD>
   void attn_bwd(int l, const float* datt) {
-    const size_t lds = ((size_t)4 * L.P * HD + 2 * L.P) * 4;
-    attn_attr(vis_attn_bwd_kernel<P, HD>, lds, 1);
+    const size_t lds = attn_bwd_lds(L.P, HD);
+    attn_attr<HD, 1>((const void*)vis_attn_bwd_kernel<P, HD>, lds);
     hipLaunchKernelGGL((vis_attn_bwd_kernel<P, HD>), dim3((unsigned)(NI * L.nh)), dim3(128), lds, s, qkv[l], att[l], datt, lse[l],
                        L.P, L.D, L.nh, 1.f / sqrtf((float)HD), dqkv);
   }

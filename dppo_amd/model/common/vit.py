@@ -126,7 +126,10 @@ class VisualEncoder(HipNet):
         return [p for m in self._mods for p in m.parameters()]
 
     def _abi_param_count(self) -> int:
-        return hip.load().dppo_vis_param_count(C.byref(self.desc))
+        n = hip.load().dppo_vis_param_count(C.byref(self.desc))
+        if n < 0:  # a refused descriptor: raise with the library's message
+            hip.check(int(n), "dppo_vis_param_count")
+        return n
 
     def _abi_packed_bytes(self, prec: int, n_time: int) -> int:
         return hip.load().dppo_vis_packed_bytes(C.byref(self.desc), prec)

@@ -715,7 +715,13 @@ int dppo_unet_denoise_mse_fwd_bwd_obs(const dppo_unet_desc* net, int prec, const
  * Flat parameter order = the reference's state dict: backbone.vit.{pos_embed, patch_embed.embed.0, .3, net.l.{layer_norm1,
  * mha.qkv_proj, mha.out_proj, layer_norm2, linear1, linear2}, norm}, then compress (or compress1, compress2).{weight,
  * input_proj.0, input_proj.1}.  Not built: embed_style "embed1", embed_norm, the Linear `compress` of spatial_emb = 0,
- * RandomShiftsAug inside the network (the host-side augmentation of dppo_amd shifts the images before the call). */
+ * RandomShiftsAug inside the network (the host-side augmentation of dppo_amd shifts the images before the call).
+ * Accepted descriptors (anything else is refused by message, by every entry, before a launch): in_ch 3..24 in threes;
+ * image sides 16..512 of the form 8 + 4 n whose first map Conv2d(k3, s2) tiles exactly, non-square allowed; embed_dim
+ * 64..512 in steps of 64; head dimension embed_dim / num_heads of 16, 32 or 64; depth 1..4; prop_dim 0..1024 (0: `state`
+ * may be null); spatial_emb 64..512 in steps of 64; num_img 1 or 2; at most 240 patches, and at head dimension 64 at most
+ * 158: the attention backward keeps Q, K, V and dO of one (image, head) in LDS as fp32, (4 P hd + 2 P) * 4 bytes of the
+ * CU's 160 KiB. */
 typedef struct dppo_vis_desc {
   int32_t in_ch;           /* 3 * img_cond_steps, per camera                                  */
   int32_t img_h, img_w;

@@ -1062,7 +1062,7 @@ def vis_features(p: Params, v: VisSpec, rgb: torch.Tensor, state: torch.Tensor) 
     (B, T_rgb, 3 * num_img, H, W) with T_rgb = img_cond_steps, state (B, To, Do) -> cat[feat, state] (B, feat_dim + To*Do)."""
     B, T, C, H, W = rgb.shape
     s = state.reshape(B, -1)
-    rgb = rgb.float()
+    rgb = rgb.to(p["backbone.vit.pos_embed"].dtype)  # float32 parameters: the reference's .float(); float64: the same in double
     if v.num_img > 1:
         imgs = rgb.reshape(B, T, v.num_img, 3, H, W).permute(0, 2, 1, 3, 4, 5).reshape(B, v.num_img, T * 3, H, W)
         feats = [spatial_emb_forward(p, c, vit_forward(p, v, imgs[:, i]), s) for i, c in enumerate(v.compress_names())]
