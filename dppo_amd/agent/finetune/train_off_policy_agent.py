@@ -1,0 +1,222 @@
+"""What the off-policy fine-tuning agents share (IDQL, QSM, DQL, SAC): the reference's ``TrainAgent`` set-up, the device-resident
+replay ring, one env step with its ``final_obs`` bootstrap and ring append, the episode statistics, the checkpoint, the logging
+tail, and the iteration of the replay-ratio agents (IDQL, QSM, DQL).  SAC's iteration is structured differently and stays in
+train_sac_agent.py; it uses the env step and the logging tail from here.
+
+A replay-ratio agent supplies its hyper-parameters and optimisers, ``nets`` and ``update_minibatch``; the defaults of
+``lr_schedulers``, ``log_line`` / ``log_keys``, ``_sample`` (how an action is drawn) and ``_metrics`` (the logged fields from the
+last minibatch's losses) are those of an agent with one actor and one critic optimiser (QSM, DQL).
+"""
+from __future__ import annotations
+
+import logging
+import os
+import pickle
+import random
+import time
+
+import numpy as np
+import torch
+
+from dppo_amd.cfg.loader import instantiate
+from dppo_amd.env.synthetic import make_venv
+from dppo_amd.util.replay import DeviceReplay
+from dppo_amd.util.scheduler import CosineAnnealingWarmupRestarts
+
+log = logging.getLogger(__name__)
+
+
+class OffPolicyAgent:
+    nets = ()  # the model's networks whose kernel images follow a loaded checkpoint
+    lr_schedulers = ("actor_lr_scheduler", "critic_lr_scheduler")  # stepped once per iteration, in this order
+    # a train iteration's log line after "itr: step |", and the record keys it prints
+    log_line = "loss actor %8.4f | loss critic %8.4f | reward %8.4f | t:%8.4f"
+    log_keys = ("loss_actor", "loss_critic", "train_episode_reward", "time")
+
+    def __init__(self, cfg, venv, who):
+        self.cfg = cfg
+        self.device = cfg.device
+        self.seed = cfg.get("seed", 42)
+        random.seed(self.seed)
+        np.random.seed(self.seed)
+        torch.manual_seed(self.seed)
+
+        # ---- TrainAgent (train_agent.py:21-120)
+        self.use_wandb = cfg.get("wandb", None) is not None
+        if self.use_wandb:
+            try:
+                import wandb
+                wandb.init(entity=cfg.wandb.entity, project=cfg.wandb.project, name=cfg.wandb.run, config=dict(cfg))
+                self._wandb = wandb
+            except ImportError:
+                log.warning("wandb is not installed; logging to the python logger and result.pkl only")
+                self.use_wandb = False
+        self.n_envs = cfg.env.n_envs
+        self.venv = venv if venv is not None else make_venv(cfg)
+        if hasattr(self.venv, "seed") and cfg.env.get("env_type", None) != "furniture":
+            self.venv.seed([self.seed + i for i in range(self.n_envs)])
+        self.n_cond_step, self.obs_dim, self.action_dim = cfg.cond_steps, cfg.obs_dim, cfg.action_dim
+        self.act_steps, self.horizon_steps = cfg.act_steps, cfg.horizon_steps
+        # the stored action chunk is the critic's action and the actor loss's x_start (reference IDQL :298-301, QSM :236-264)
+        assert self.act_steps == self.horizon_steps, f"{who} needs act_steps == horizon_steps"
+        self.reset_at_iteration = cfg.env.get("reset_at_iteration", True)
+        self.batch_size = cfg.train.batch_size
+        self.model = instantiate(cfg.model)
+        self.itr = 0
+        self.n_train_itr, self.val_freq = cfg.train.n_train_itr, cfg.train.val_freq
+        self.force_train = cfg.train.get("force_train", False)
+        self.n_steps = cfg.train.n_steps
+        self.best_reward_threshold_for_success = cfg.env.get("best_reward_threshold_for_success", 0)
+        self.max_grad_norm = cfg.train.get("max_grad_norm", None)
+        self.logdir = cfg.logdir
+        self.checkpoint_dir = os.path.join(self.logdir, "checkpoint")
+        self.result_path = os.path.join(self.logdir, "result.pkl")
+        os.makedirs(self.checkpoint_dir, exist_ok=True)
+        self.log_freq = cfg.train.get("log_freq", 1)
+        self.save_model_freq = cfg.train.save_model_freq
+        # ---- what every off-policy agent of the reference reads from cfg.train
+        self.gamma = cfg.train.gamma  # applied to the reward of every act_steps env steps
+        self.scale_reward_factor = cfg.train.scale_reward_factor
+        self.buffer_size = cfg.train.buffer_size
+        self.replay = DeviceReplay(self.buffer_size, self.n_envs, self.n_cond_step * self.obs_dim,
+                                   self.act_steps * self.action_dim, self.device)
+
+    @staticmethod
+    def _cosine(opt, sched_cfg, lr):
+        return CosineAnnealingWarmupRestarts(opt, first_cycle_steps=sched_cfg.first_cycle_steps, cycle_mult=1.0, max_lr=lr,
+                                             min_lr=sched_cfg.min_lr, warmup_steps=sched_cfg.warmup_steps, gamma=1.0)
+
+    def reset_env_all(self, options_venv=None):
+        obs = self.venv.reset_arg(options_list=options_venv or [{} for _ in range(self.n_envs)])
+        if isinstance(obs, list):
+            obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
+        return obs
+
+    def save_model(self):
+        """checkpoint/state_{itr}.pt = {"itr", "model": state_dict} (train_agent.py:125-135)."""
+        path = os.path.join(self.checkpoint_dir, f"state_{self.itr}.pt")
+        torch.save({"itr": self.itr, "model": self.model.state_dict()}, path)
+        log.info("Saved model to %s", path)
+
+    def load(self, itr):
+        data = torch.load(os.path.join(self.checkpoint_dir, f"state_{itr}.pt"), weights_only=True)
+        self.itr = data["itr"]
+        self.model.load_state_dict(data["model"])
+        for name in self.nets:
+            getattr(self.model, name).mark_updated()  # kernel images are rebuilt from the loaded weights on next use
+
+    def env_step(self, state, action, stored, eval_mode):
+        """One step of all envs with ``action`` (numpy).  Outside evaluation the transition goes into the ring: ``state`` (the
+        device observation the action was drawn at), ``stored`` as its action, the scaled reward, ``terminated``, and the next
+        observation -- for a truncated env its pre-reset ``final_obs`` (dict or bare array), so that the bootstrap sees the state
+        the episode ended in (reference IDQL :171-177).  The env's own array is copied before the first such write.
+        Returns (observation dict, reward, done)."""
+        obs, reward, terminated, truncated, info = self.venv.step(action)
+        if isinstance(obs, list):
+            obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
+        if not eval_mode:
+            nxt = obs["state"]
+            for i in np.where(truncated)[0]:
+                fin = info[i].get("final_obs") if isinstance(info[i], dict) else None
+                if fin is not None:
+                    if nxt is obs["state"]:
+                        nxt = nxt.copy()
+                    nxt[i] = fin["state"] if isinstance(fin, dict) else fin
+            self.replay.append(state, nxt, stored, np.asarray(reward) * self.scale_reward_factor,
+                               np.asarray(terminated).astype(np.float32))
+        return obs, reward, terminated | truncated
+
+    def _episode_stats(self, firsts, reward_trajs):
+        """(average episode reward, average best reward, success rate) over the episodes that finish within the iteration
+        (reference :190-225)."""
+        ep_rewards, ep_best = [], []
+        for e in range(self.n_envs):
+            starts = np.where(firsts[:, e] == 1)[0]
+            for i in range(len(starts) - 1):
+                a, b = starts[i], starts[i + 1]
+                if b - a > 1:
+                    seg = reward_trajs[a:b, e]
+                    ep_rewards.append(seg.sum())
+                    ep_best.append(seg.max() / self.act_steps)
+        n_ep = len(ep_rewards)
+        avg_ep = float(np.mean(ep_rewards)) if n_ep else 0.0
+        avg_best = float(np.mean(ep_best)) if n_ep else 0.0
+        success = float(np.mean(np.array(ep_best) >= self.best_reward_threshold_for_success)) if n_ep else 0.0
+        return avg_ep, avg_best, success
+
+    def log_record(self, run_results, rec, t_start, eval_mode, stats, train_fields):
+        """A logging iteration's tail: ``time`` and the evaluation's or the training's fields into ``rec``, the log line, wandb,
+        ``rec`` onto ``run_results`` and all of it into result.pkl."""
+        avg_ep, avg_best, success = stats
+        rec["time"] = time.time() - t_start
+        if eval_mode:
+            rec.update(eval_success_rate=success, eval_episode_reward=avg_ep, eval_best_reward=avg_best)
+            log.info("eval: success rate %8.4f | avg episode reward %8.4f | avg best reward %8.4f", success, avg_ep, avg_best)
+        else:
+            rec.update(train_episode_reward=avg_ep, **train_fields)
+            log.info("%d: step %8d | " + self.log_line, rec["itr"], rec["step"], *[rec.get(k, float("nan")) for k in self.log_keys])
+        if self.use_wandb:
+            self._wandb.log({k: v for k, v in rec.items() if k != "itr"}, step=self.itr)
+        run_results.append(rec)
+        with open(self.result_path, "wb") as f:
+            pickle.dump(run_results, f)
+
+    # ------------------------------------------------------------------------------------------------- IDQL, QSM, DQL
+    def _sample(self, state, eval_mode):
+        """The action chunk (n_envs, Ta, Da) at the device observations ``state``."""
+        return self.model(cond={"state": state}, deterministic=eval_mode)
+
+    def _metrics(self, lc, la):
+        """The train record's fields from the last minibatch's losses (host floats, as ``update_minibatch`` returns them)."""
+        return {"loss_actor": la, "loss_critic": lc, "actor_lr": self.actor_optimizer.param_groups[0]["lr"],
+                "critic_lr": self.critic_optimizer.param_groups[0]["lr"]}
+
+    def run(self):
+        model, dev = self.model, self.device
+        S, E = self.n_steps, self.n_envs
+        t_start = time.time()
+        run_results = []
+        cnt_train_step = 0
+        last_itr_eval = False
+        done_venv = np.zeros(E, dtype=bool)
+        prev_obs = None
+        metrics = {}
+        while self.itr < self.n_train_itr:
+            eval_mode = self.itr % self.val_freq == 0 and not self.force_train
+            model.eval() if eval_mode else model.train()
+            firsts = np.zeros((S + 1, E))
+            if self.reset_at_iteration or eval_mode or last_itr_eval or prev_obs is None:
+                prev_obs = self.reset_env_all()
+                firsts[0] = 1
+            else:
+                firsts[0] = done_venv
+            last_itr_eval = eval_mode
+            reward_trajs = np.zeros((S, E))
+            # ---------------- rollout: the sampler on the device, envs on the host
+            for step in range(S):
+                state = torch.from_numpy(prev_obs["state"]).float().to(dev)
+                samples = self._sample(state, eval_mode)
+                prev_obs, reward, done_venv = self.env_step(state, samples.cpu().numpy()[:, :self.act_steps],
+                                                            samples[:, :self.act_steps], eval_mode)
+                reward_trajs[step], firsts[step + 1] = reward, done_venv
+                if not eval_mode:
+                    cnt_train_step += E * self.act_steps
+            if hasattr(model, "check_sampler_health"):
+                model.check_sampler_health()
+            stats = self._episode_stats(firsts, reward_trajs)
+            # ---------------- update
+            if not eval_mode:
+                num_batch = int(S * E / self.batch_size * self.replay_ratio)
+                all_inds = self.replay.draw(num_batch, self.batch_size)  # one host draw, one upload
+                losses = [self.update_minibatch(all_inds[b]) for b in range(num_batch)]
+                if losses:
+                    metrics = self._metrics(*(float(x) for x in losses[-1]))  # the only device read of the update
+            # ---------------- schedules, checkpoint, logging
+            for name in self.lr_schedulers:
+                getattr(self, name).step()
+            if self.itr % self.save_model_freq == 0 or self.itr == self.n_train_itr - 1:
+                self.save_model()
+            if self.itr % self.log_freq == 0:
+                self.log_record(run_results, {"itr": self.itr, "step": cnt_train_step}, t_start, eval_mode, stats, metrics)
+            self.itr += 1
+        return run_results

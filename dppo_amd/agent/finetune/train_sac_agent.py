@@ -12,49 +12,35 @@ device float64 tensor stepped by ``torch.optim.Adam``.  State observations only,
 """
 from __future__ import annotations
 
-import logging
-import os
-import pickle
 import time
 
 import numpy as np
 import torch
 
-from dppo_amd.agent.finetune.train_idql_diffusion_agent import OffPolicyDiffusionAgent
+from dppo_amd.agent.finetune.train_off_policy_agent import OffPolicyAgent
 from dppo_amd.util.optim import FlatAdamW
-from dppo_amd.util.replay import DeviceReplay
-
-log = logging.getLogger(__name__)
 
 
-class TrainSACAgent(OffPolicyDiffusionAgent):
+class TrainSACAgent(OffPolicyAgent):
+    nets = ("network", "critic", "target_critic")
+    log_line = "loss actor %8.4f | loss critic %8.4f | reward %8.4f | alpha %8.4f | t %8.4f"
+    log_keys = ("loss_actor", "loss_critic", "train_episode_reward", "alpha", "time")
+
     def __init__(self, cfg, venv=None):
-        self._init_train_agent(cfg, venv, "SAC")
+        super().__init__(cfg, venv, "SAC")
         # ---- TrainSACAgent (:21-68); torch.optim.Adam there is AdamW without decay here
-        self.gamma = cfg.train.gamma  # applied to the reward of every act_steps env steps
         m = self.model
         self.actor_optimizer = FlatAdamW(m.network.flat_params(), lr=cfg.train.actor_lr, weight_decay=0)
         self.critic_optimizer = FlatAdamW(m.critic.flat_params(), lr=cfg.train.critic_lr, weight_decay=0)
         self.target_ema_rate = cfg.train.target_ema_rate
-        self.scale_reward_factor = cfg.train.scale_reward_factor
         self.critic_update_freq = int(cfg.train.batch_size / cfg.train.critic_replay_ratio)
         self.actor_update_freq = int(cfg.train.batch_size / cfg.train.actor_replay_ratio)
-        self.buffer_size = cfg.train.buffer_size
         self.n_eval_episode = cfg.train.n_eval_episode
         self.n_explore_steps = cfg.train.n_explore_steps
         self.log_alpha = torch.tensor(np.log(cfg.train.init_temperature), dtype=torch.float64, device=self.device,
                                       requires_grad=True)
         self.target_entropy = cfg.train.target_entropy
         self.log_alpha_optimizer = torch.optim.Adam([self.log_alpha], lr=cfg.train.critic_lr)
-        self.replay = DeviceReplay(self.buffer_size, self.n_envs, self.n_cond_step * self.obs_dim,
-                                   self.act_steps * self.action_dim, self.device)
-
-    def load(self, itr):
-        data = torch.load(os.path.join(self.checkpoint_dir, f"state_{itr}.pt"), weights_only=True)
-        self.itr = data["itr"]
-        self.model.load_state_dict(data["model"])
-        for net in (self.model.network, self.model.critic, self.model.target_critic):
-            net.mark_updated()  # kernel images are rebuilt from the loaded weights on next use
 
     def _explore_action(self):
         """Uniformly random actions (:121-122): the env's own ``action_space.sample()`` where it has one."""
@@ -119,28 +105,15 @@ class TrainSACAgent(OffPolicyDiffusionAgent):
                     action = self._explore_action()
                 else:
                     action = model(cond={"state": state}, deterministic=eval_mode).cpu().numpy()[:, :self.act_steps]
-                obs, reward, terminated, truncated, info = self.venv.step(action)
-                if isinstance(obs, list):
-                    obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
-                done_venv = terminated | truncated
+                prev_obs, reward, done_venv = self.env_step(state, action, action, eval_mode)
                 rewards.append(np.asarray(reward, dtype=np.float64))
                 firsts.append(done_venv.astype(np.float64))
                 if not eval_mode:
-                    nxt = obs["state"]
-                    for i in np.where(truncated)[0]:  # bootstrap from the pre-reset observation (:152-155)
-                        fin = info[i].get("final_obs") if isinstance(info[i], dict) else None
-                        if fin is not None:
-                            if nxt is obs["state"]:
-                                nxt = nxt.copy()
-                            nxt[i] = fin["state"] if isinstance(fin, dict) else fin
-                    self.replay.append(state, nxt, action, np.asarray(reward) * self.scale_reward_factor,
-                                       np.asarray(terminated).astype(np.float32))
                     cnt_train_step += E * self.act_steps
-                prev_obs = obs
                 cnt_episode += int(np.sum(done_venv))
                 if eval_mode and cnt_episode >= self.n_eval_episode:
                     break
-            avg_ep, avg_best, success = self._episode_stats(np.stack(firsts), np.stack(rewards))
+            stats = self._episode_stats(np.stack(firsts), np.stack(rewards))
             # ---------------- update (:209-280)
             if not eval_mode and self.itr > self.n_explore_steps and self.itr % self.critic_update_freq == 0:
                 inds = np.random.choice(len(self.replay), self.batch_size, replace=False)
@@ -151,24 +124,13 @@ class TrainSACAgent(OffPolicyDiffusionAgent):
                 self.save_model()
             rec = {"itr": self.itr, "step": cnt_train_step}
             if self.itr % self.log_freq == 0 and self.itr > self.n_explore_steps:
-                rec["time"] = time.time() - t_start
-                if eval_mode:
-                    rec.update(eval_success_rate=success, eval_episode_reward=avg_ep, eval_best_reward=avg_best)
-                    log.info("eval: success rate %8.4f | avg episode reward %8.4f | avg best reward %8.4f", success, avg_ep, avg_best)
-                else:
-                    rec["train_episode_reward"] = avg_ep
-                    if losses is not None:  # the only device reads of the loop, on logging iterations
-                        lc, la, _ = losses
-                        rec.update(loss_critic=float(lc), alpha=float(self.log_alpha.detach().exp()))
-                        if la is not None:
-                            rec["loss_actor"] = float(la)
-                    log.info("%d: step %8d | loss actor %8.4f | loss critic %8.4f | reward %8.4f | alpha %8.4f | t %8.4f", self.itr,
-                             cnt_train_step, rec.get("loss_actor", float("nan")), rec.get("loss_critic", float("nan")), avg_ep,
-                             rec.get("alpha", float("nan")), rec["time"])
-                if self.use_wandb:
-                    self._wandb.log({k: v for k, v in rec.items() if k != "itr"}, step=self.itr)
-                with open(self.result_path, "wb") as f:
-                    pickle.dump(run_results + [rec], f)
-            run_results.append(rec)
+                fields = {}
+                if not eval_mode and losses is not None:  # the only device reads of the loop, on logging iterations
+                    fields.update(loss_critic=float(losses[0]), alpha=float(self.log_alpha.detach().exp()))
+                    if losses[1] is not None:
+                        fields["loss_actor"] = float(losses[1])
+                self.log_record(run_results, rec, t_start, eval_mode, stats, fields)
+            else:
+                run_results.append(rec)
             self.itr += 1
         return run_results

@@ -2991,9 +2991,10 @@ int64_t dppo_qsm_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int ob
   });
 }
 template <class P>
-static int qsm_td_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const float* tp, const char* tk1,
-                       const char* tk2, const dppo_idql_batch& b, int OD, const float* next_actions, int64_t N, double gamma,
-                       float* qgrad, double* stats, void* ws, int64_t wsb, hipStream_t s) {
+static int twin_td_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const float* tp, const char* tk1,
+                        const char* tk2, const dppo_idql_batch& b, int OD, const float* next_actions, const float* next_logp,
+                        const double* alpha, int64_t N, double gamma, float* qgrad, double* stats, void* ws, int64_t wsb,
+                        hipStream_t s) {
   Carver c{(char*)ws, 0, (size_t)wsb};
   QsmTdWs<P> W;
   const size_t need = carve_qsm_td<P>(c, q, N, W);
@@ -3026,6 +3027,7 @@ static int qsm_td_impl(const dppo_net_desc& q, const float* qp, const char* qk1,
   l.q1 = W.Q1.out, l.q2 = W.Q2.out, l.ldq = W.Q1.ldout, l.v = W.T1.out, l.v2 = W.T2.out, l.ldv = W.T1.ldout, l.N = N;
   l.reward = W.r, l.terminated = W.term, l.gamma = (float)gamma, l.d_a = W.Q1.d_out, l.d_b = W.Q2.d_out;
   l.ldd = L.Kpo, l.partial = W.partial, l.stats = stats;
+  l.next_logp = next_logp, l.alpha = alpha;  // SAC's entropy term of the bootstrap; both null (QSM, DQL): none
   launch_idql_q_loss<P>(l, s);
   s2 = fork_side(s, 0);
   mlp_backward<P>(q, qp + nq, qk2, L, N, W.Q2, qgrad + nq, nullptr, nullptr, 0, s2);
@@ -3046,9 +3048,9 @@ int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
   if (int e = check_idql_batch(batch, N, true)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                \
-  qsm_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
-                 (const char*)target_q2_packed, *batch, obs_dim, next_actions, N, gamma, q_grad, stats, workspace,             \
-                 workspace_bytes, (hipStream_t)stream)
+  twin_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
+                  (const char*)target_q2_packed, *batch, obs_dim, next_actions, nullptr, nullptr, N, gamma, q_grad, stats,      \
+                  workspace, workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }
@@ -3348,50 +3350,6 @@ int dppo_sac_sample(const dppo_net_desc* actor, int prec, const float* params, c
 int64_t dppo_sac_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
   return dppo_qsm_q_loss_workspace_bytes(q, prec, obs_dim, N);  // the same four trunks, partials and gathered rows
 }
-template <class P>
-static int sac_td_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const float* tp, const char* tk1,
-                       const char* tk2, const dppo_idql_batch& b, int OD, const float* next_actions, const float* next_logp,
-                       const double* alpha, int64_t N, double gamma, float* qgrad, double* stats, void* ws, int64_t wsb,
-                       hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
-  QsmTdWs<P> W;
-  const size_t need = carve_qsm_td<P>(c, q, N, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
-  const PackLayout L = pack_layout<P>(q, 0);
-  const int64_t nq = param_layout(q).total;
-  QsmTdRows r;
-  memset(&r, 0, sizeof(r));
-  r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
-  r.next_actions = next_actions, r.q1in = W.Q1.in, r.q2in = W.Q2.in, r.t1in = W.T1.in, r.t2in = W.T2.in, r.KpQ = L.Kp0;
-  r.r_out = W.r, r.term_out = W.term;
-  launch_qsm_td_rows<P>(r, s);
-  // the four trunks side by side and the joins as in qsm_td_impl
-  hipStream_t s2 = fork_side(s, 0), s3 = fork_side(s, 1), s4 = fork_side(s, 2);
-  mlp_forward<P>(q, qp + nq, qk2, L, N, W.Q2, true, s2);
-  mlp_forward<P>(q, tp, tk1, L, N, W.T1, false, s3);
-  mlp_forward<P>(q, tp + nq, tk2, L, N, W.T2, false, s4);
-  mlp_forward<P>(q, qp, qk1, L, N, W.Q1, true, s);
-  if (s4 != s) {
-    if (s2 != s) join_side(s4, s2, 0);
-    if (s3 != s) join_side(s4, s3, 1);
-    join_side(s, s4, 2);
-  } else {
-    if (s2 != s) join_side(s, s2, 0);
-    if (s3 != s) join_side(s, s3, 1);
-  }
-  IdqlLoss l;
-  memset(&l, 0, sizeof(l));
-  l.q1 = W.Q1.out, l.q2 = W.Q2.out, l.ldq = W.Q1.ldout, l.v = W.T1.out, l.v2 = W.T2.out, l.ldv = W.T1.ldout, l.N = N;
-  l.reward = W.r, l.terminated = W.term, l.gamma = (float)gamma, l.d_a = W.Q1.d_out, l.d_b = W.Q2.d_out;
-  l.ldd = L.Kpo, l.partial = W.partial, l.stats = stats;
-  l.next_logp = next_logp, l.alpha = alpha;  // the entropy term of the bootstrap
-  launch_idql_q_loss<P>(l, s);
-  s2 = fork_side(s, 0);
-  mlp_backward<P>(q, qp + nq, qk2, L, N, W.Q2, qgrad + nq, nullptr, nullptr, 0, s2);
-  mlp_backward<P>(q, qp, qk1, L, N, W.Q1, qgrad, nullptr, nullptr, 0, s);
-  if (s2 != s) join_side(s, s2, 0);
-  return check_launch();
-}
 int dppo_sac_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
                             const float* target_q_params, const void* target_q1_packed, const void* target_q2_packed,
                             const dppo_idql_batch* batch, int obs_dim, const float* next_actions, const float* next_logp,
@@ -3406,9 +3364,9 @@ int dppo_sac_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
   if (int e = check_idql_batch(batch, N, true)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                \
-  sac_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
-                 (const char*)target_q2_packed, *batch, obs_dim, next_actions, next_logp, alpha, N, gamma, q_grad, stats,      \
-                 workspace, workspace_bytes, (hipStream_t)stream)
+  twin_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
+                  (const char*)target_q2_packed, *batch, obs_dim, next_actions, next_logp, alpha, N, gamma, q_grad, stats,      \
+                  workspace, workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }

@@ -324,7 +324,11 @@ class Workspace:
     def __init__(self):
         self.buf: Optional[torch.Tensor] = None
 
-    def get(self, nbytes: int, device) -> torch.Tensor:
+    def get(self, nbytes: int, device, what: Optional[str] = None) -> torch.Tensor:
+        """``nbytes`` as the library's ``<entry>_workspace_bytes`` returned it: a negative one is that query's refusal, raised
+        under the name ``what``."""
+        if nbytes < 0:
+            check(int(nbytes), what)
         if self.buf is None or self.buf.numel() < nbytes or self.buf.device != torch.device(device):
             # zero-filled: a sampling workspace begins with the sticky time-out word (include/dppo_hip.h, dppo_sample_chain)
             self.buf = torch.zeros(max(int(nbytes), 256), dtype=torch.uint8, device=device)

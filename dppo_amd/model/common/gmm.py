@@ -10,7 +10,8 @@ import logging
 import torch
 
 from dppo_amd import hip
-from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss  # (value, gradient views, *parameters) -> scalar with a backward
+# _FusedDenoiseLoss: (value, gradient views, *parameters) -> scalar with a backward
+from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss, flat_views
 
 log = logging.getLogger(__name__)
 
@@ -61,10 +62,7 @@ class GMMModel(torch.nn.Module):
         object.__setattr__(self, "last_loss_grad", grad)
         object.__setattr__(self, "last_logvar_grad", lv_grad)
         params = net.trunk_parameters()  # the flat image is their concatenation in this order
-        views, off = [], 0
-        for p in params:
-            views.append(grad[off:off + p.numel()].view(p.shape))
-            off += p.numel()
+        views = flat_views(grad, params)
         if lv_grad is not None:
             params, views = params + [net.logvar], views + [lv_grad]
         return _FusedDenoiseLoss.apply(out[0], views, *params), {"entropy": out[1].float()}

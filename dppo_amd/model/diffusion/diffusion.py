@@ -35,6 +35,15 @@ class _FusedDenoiseLoss(torch.autograd.Function):
         return (None, None, *[x * g for x in ctx.grads])
 
 
+def flat_views(grad, params):
+    """Per-parameter views into the flat gradient ``grad``, which is the concatenation of ``params``' gradients in this order."""
+    views, off = [], 0
+    for p in params:
+        views.append(grad[off:off + p.numel()].view(p.shape))
+        off += p.numel()
+    return views
+
+
 class DiffusionModel(nn.Module):
     def __init__(self, network, horizon_steps, obs_dim, action_dim, network_path=None, device="cuda:0",
                  denoised_clip_value=1.0, randn_clip_value=10, final_action_clip_value=None, eps_clip_value=None,
@@ -362,10 +371,7 @@ class DiffusionModel(nn.Module):
             hip.check(entry(*args), "dppo_denoise_mse_fwd_bwd")
         object.__setattr__(self, "last_loss_grad", grad)  # flat d loss / d parameters, for callers that step a flat optimiser
         params = net.trunk_parameters()  # the flat image is their concatenation in this order
-        views, off = [], 0
-        for p in params:
-            views.append(grad[off:off + p.numel()].view(p.shape))
-            off += p.numel()
+        views = flat_views(grad, params)
         if vision:  # + the encoder's parameters and gradients (its own flat buffer)
             object.__setattr__(self, "last_loss_grad_vis", vgrad)
             params = params + net.vis.trunk_parameters()

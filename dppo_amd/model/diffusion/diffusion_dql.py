@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from dppo_amd import hip
-from dppo_amd.model.diffusion.diffusion import DiffusionModel, _FusedDenoiseLoss
-from dppo_amd.util.replay import DeviceReplay
+from dppo_amd.model.common import off_policy
+from dppo_amd.model.diffusion.diffusion import DiffusionModel, _FusedDenoiseLoss, flat_views
 
 
 class DQLDiffusion(DiffusionModel):
@@ -35,30 +35,6 @@ class DQLDiffusion(DiffusionModel):
         self.min_sampling_denoising_std = min_sampling_denoising_std
         for name in ("_ws_actor", "_ws_q"):
             object.__setattr__(self, name, hip.Workspace())
-
-    @staticmethod
-    def _state(obs):
-        if isinstance(obs, dict):
-            if "rgb" in obs:
-                raise NotImplementedError("dppo_amd: DQL is built for state observations only (like the reference)")
-            obs = obs["state"]
-        return obs
-
-    def _batch(self, obs, inds=None, actions=None, next_obs=None, rewards=None, terminated=None):
-        """(dppo_idql_batch, N, tensors to keep alive, observations or None).  ``obs``: a ``DeviceReplay`` (rows ``inds``, or all
-        of it) or the reference's ``{"state": (N, To, Do)}`` with plain (N, ...) companions (any may be missing)."""
-        if isinstance(obs, DeviceReplay):
-            N = len(obs) if inds is None else inds.numel()
-            if inds is not None:
-                assert inds.dtype == torch.int64 and inds.is_contiguous() and inds.is_cuda
-            return obs.batch(inds), N, (inds,)
-        st = self._state(obs)
-        hip.require_gpu(st, type(self).__name__)
-        N = st.shape[0]
-        flat = lambda x, *s: None if x is None else x.reshape(N, *s).contiguous().float()
-        keep = [flat(st, -1), None if next_obs is None else flat(self._state(next_obs), -1), flat(actions, -1), flat(rewards),
-                flat(terminated)]
-        return hip.IdqlBatch(*[hip.ptr(k) for k in keep], None, N, 1, 0, N), N, keep
 
     def _tables(self, dev):
         """Per device: sqrt(abar), sqrt(1 - abar), and the dppo_step table by diffusion time (entry t: the DDPM coefficients)."""
@@ -87,33 +63,8 @@ class DQLDiffusion(DiffusionModel):
         """mean((q1 - y)^2) + mean((q2 - y)^2), y = r + gamma min(target q1, q2)(s', a') (1 - terminated), a' ~ forward(s') without
         gradient; d loss / d [Q1 | Q2] parameters in ``critic.flat_grads()``, ``last_stats``: {loss, mean q1, mean y}.
         ``next_actions`` / ``noise`` (K+1, N, Ta, Da) replace the sample / its draws."""
-        q, tq = self.critic, self.critic_target
-        batch, N, keep = self._batch(obs, inds, actions, next_obs, rewards, terminated)
-        dev = q.flat_params().device
-        if next_actions is None:
-            if isinstance(obs, DeviceReplay):
-                rows = torch.arange(len(obs), device=dev) if inds is None else inds
-                nxt = obs.gather(rows)[1]
-            else:
-                nxt = self._state(next_obs)
-            next_actions = self.forward({"state": nxt.reshape(N, -1)}, deterministic=False, noise=noise)
-        next_actions = next_actions.reshape(N, -1).contiguous().float()
-        lib, dq = hip.load(), q.net_desc()
-        OD = q.cond_dim
-        assert next_actions.shape[1] == dq.in_dim - OD, "next_actions must be (N, Ta, Da)"
-        wsb = lib.dppo_qsm_q_loss_workspace_bytes(C.byref(dq), self.prec, OD, N)
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_qsm_q_loss_workspace_bytes")
-        ws = self._ws_q.get(wsb, dev)
-        k1, k2 = q.packed(self.prec)
-        t1, t2 = tq.packed(self.prec)
-        stats = torch.empty(hip.IDQL_STAT_COUNT, dtype=torch.float64, device=dev)
-        hip.check(lib.dppo_qsm_q_loss_fwd_bwd(
-            C.byref(dq), self.prec, q.flat_params().data_ptr(), k1.data_ptr(), hip.ptr(k2), tq.flat_params().data_ptr(),
-            t1.data_ptr(), hip.ptr(t2), C.byref(batch), OD, next_actions.data_ptr(), N, float(gamma), q.flat_grads().data_ptr(),
-            stats.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_qsm_q_loss_fwd_bwd")
-        object.__setattr__(self, "last_stats", stats)
-        return _FusedDenoiseLoss.apply(stats[0], q.grad_views(), *q.trunk_parameters())
+        return off_policy.twin_td_loss(self, "DQL", self.critic, self.critic_target, obs, next_obs, actions, rewards, terminated, gamma,
+                                       inds, next_actions, noise)
 
     def loss_actor(self, obs, eta, act_steps, inds=None, noise=None, noise_bc=None, t_bc=None, which=None, chains=None,
                    want_masks=False):
@@ -127,17 +78,13 @@ class DQLDiffusion(DiffusionModel):
             raise NotImplementedError(f"dppo_amd: DQL's loss_actor is built for act_steps == horizon_steps (got {act_steps} and "
                                       f"{self.horizon_steps}); every shipped cfg has them equal")
         q, net = self.critic, self.network
-        batch, N, keep = self._batch(obs, inds)
+        batch, N, keep = off_policy.as_batch("DQL", obs, inds)
         dev = net.flat_params().device
         AF, K = self.horizon_steps * self.action_dim, self.denoising_steps
         if which is None:
             which = 0 if np.random.uniform() > 0.5 else 1
         if chains is None:
-            if isinstance(obs, DeviceReplay):
-                rows = torch.arange(len(obs), device=dev) if inds is None else inds
-                st = obs.gather(rows)[0]
-            else:
-                st = self._state(obs)
+            st = off_policy.rows_of("DQL", obs, inds)
             chains = self.forward_train({"state": st.reshape(N, -1)}, noise=noise, return_chain=True).chains
         chains = chains.reshape(N, K + 1, AF).contiguous().float()
         if noise_bc is None:
@@ -148,10 +95,8 @@ class DQLDiffusion(DiffusionModel):
         t_bc = t_bc.reshape(N).to(torch.int64).contiguous()
         lib, da, dq = hip.load(), net.net_desc(), q.net_desc()
         OD = q.cond_dim
-        wsb = lib.dppo_dql_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N, K)
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_dql_actor_workspace_bytes")
-        ws = self._ws_actor.get(wsb, dev)
+        ws = self._ws_actor.get(lib.dppo_dql_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N, K), dev,
+                                "dppo_dql_actor_workspace_bytes")
         k1, k2 = q.packed(self.prec)
         sa, sb, steps = self._tables(dev)
         cfg = self._train_cfg()
@@ -169,17 +114,10 @@ class DQLDiffusion(DiffusionModel):
                         ("last_chains", chains), ("last_which", which)):
             object.__setattr__(self, name, v)
         params = net.trunk_parameters()
-        views, off = [], 0
-        for p in params:
-            views.append(grad[off:off + p.numel()].view(p.shape))
-            off += p.numel()
-        return _FusedDenoiseLoss.apply(stats[0], views, *params)
+        return _FusedDenoiseLoss.apply(stats[0], flat_views(grad, params), *params)
 
     def update_target_critic(self, tau):
-        """target <- target * (1 - tau) + source * tau over the flat [Q1 | Q2] image, then the target's kernel images are stale."""
-        t, s = self.critic_target.flat_params(), self.critic.flat_params()
-        hip.check(hip.load().dppo_polyak(t.data_ptr(), s.data_ptr(), float(tau), t.numel(), hip.stream()), "dppo_polyak")
-        self.critic_target.mark_updated()
+        off_policy.polyak(self.critic_target, self.critic, tau)
 
     # ------------------------------------------------------------------ sampling (reference :100-179)
     @torch.no_grad()

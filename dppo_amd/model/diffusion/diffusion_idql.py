@@ -14,7 +14,8 @@ import ctypes as C
 import torch
 
 from dppo_amd import hip
-from dppo_amd.model.diffusion.diffusion import DiffusionModel, _FusedDenoiseLoss
+from dppo_amd.model.common import off_policy
+from dppo_amd.model.diffusion.diffusion import DiffusionModel
 from dppo_amd.util.replay import DeviceReplay
 
 
@@ -32,49 +33,14 @@ class IDQLDiffusion(DiffusionModel):
         object.__setattr__(self, "_ws_v", hip.Workspace())
         object.__setattr__(self, "_ws_q", hip.Workspace())
 
-    # ------------------------------------------------------------------ batches
-    @staticmethod
-    def _state(obs):
-        if isinstance(obs, dict):
-            if "rgb" in obs:
-                raise NotImplementedError("dppo_amd: IDQL is built for state observations only (like the reference)")
-            obs = obs["state"]
-        return obs
-
-    def _as_batch(self, obs, actions, next_obs=None, rewards=None, terminated=None, inds=None):
-        """(dppo_idql_batch, N, tensors to keep alive).  ``obs`` may be a ``DeviceReplay`` (rows ``inds`` of the ring, or all of
-        it) or the reference's ``{"state": (N,To,Do)}`` with plain (N, ...) companions."""
-        if isinstance(obs, DeviceReplay):
-            N = len(obs) if inds is None else inds.numel()
-            if inds is not None:
-                assert inds.dtype == torch.int64 and inds.is_contiguous() and inds.is_cuda
-            return obs.batch(inds), N, (inds,)
-        st = self._state(obs)
-        hip.require_gpu(st, type(self).__name__)
-        N = st.shape[0]
-        keep = [st.reshape(N, -1).contiguous().float(), actions.reshape(N, -1).contiguous().float()]
-        ptrs = [keep[0].data_ptr(), None, keep[1].data_ptr(), None, None]
-        if next_obs is not None:
-            keep += [self._state(next_obs).reshape(N, -1).contiguous().float(), rewards.reshape(N).contiguous().float(),
-                     terminated.reshape(N).contiguous().float()]
-            ptrs[1], ptrs[3], ptrs[4] = keep[2].data_ptr(), keep[3].data_ptr(), keep[4].data_ptr()
-        return hip.IdqlBatch(*ptrs, None, N, 1, 0, N), N, keep
-
-    def _shim(self, net, stats):
-        """The loss as a scalar whose ``.backward()`` hands every parameter of ``net`` its slice of ``net.flat_grads()``."""
-        object.__setattr__(self, "last_stats", stats)
-        return _FusedDenoiseLoss.apply(stats[0], net.grad_views(), *net.trunk_parameters())
-
     # ------------------------------------------------------------------ RL training (reference :42-95)
     def _v_call(self, obs, actions, inds, expectile, want_adv):
         q, v, tq = self.critic_q, self.critic_v, self.target_q
-        batch, N, keep = self._as_batch(obs, actions, inds=inds)
+        batch, N, keep = off_policy.as_batch("IDQL", obs, inds, actions)
         lib, dq, dv = hip.load(), q.net_desc(), v.net_desc()
         dev = v.flat_params().device
-        wsb = lib.dppo_idql_v_loss_workspace_bytes(C.byref(dq), C.byref(dv), self.prec, N, int(q.double_q))
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_idql_v_loss_workspace_bytes")
-        ws = self._ws_v.get(wsb, dev)
+        ws = self._ws_v.get(lib.dppo_idql_v_loss_workspace_bytes(C.byref(dq), C.byref(dv), self.prec, N, int(q.double_q)), dev,
+                            "dppo_idql_v_loss_workspace_bytes")
         k1, k2 = tq.packed(self.prec)
         stats = torch.empty(hip.IDQL_STAT_COUNT, dtype=torch.float64, device=dev)
         adv = torch.empty(N, dtype=torch.float32, device=dev) if want_adv else None
@@ -93,7 +59,7 @@ class IDQLDiffusion(DiffusionModel):
             rows = torch.arange(len(obs), device=obs.obs.device) if inds is None else inds
             st, _, actions, _, _ = obs.gather(rows)
         else:
-            st = self._state(obs)
+            st = off_policy.state_of(obs, "IDQL")
         st = st.reshape(st.shape[0], -1)
         qs = self.target_q(st, actions)
         q = torch.minimum(*qs) if self.target_q.double_q else qs
@@ -105,33 +71,28 @@ class IDQLDiffusion(DiffusionModel):
         ``last_adv``."""
         stats, adv = self._v_call(obs, actions, inds, expectile, want_adv)
         object.__setattr__(self, "last_adv", adv)
-        return self._shim(self.critic_v, stats)
+        return off_policy.critic_loss(self, self.critic_v, stats)
 
     def loss_critic_q(self, obs, next_obs, actions, rewards, terminated, gamma, inds=None):
         """mean((q1 - y)^2) + mean((q2 - y)^2), y = r + gamma V(s') (1 - terminated); d loss / d [Q1 | Q2] parameters in
         ``critic_q.flat_grads()``.  ``last_stats``: {loss, mean q1, mean y}."""
         q, v = self.critic_q, self.critic_v
-        batch, N, keep = self._as_batch(obs, actions, next_obs, rewards, terminated, inds=inds)
+        batch, N, keep = off_policy.as_batch("IDQL", obs, inds, actions, next_obs, rewards, terminated)
         lib, dq, dv = hip.load(), q.net_desc(), v.net_desc()
         dev = v.flat_params().device
-        wsb = lib.dppo_idql_q_loss_workspace_bytes(C.byref(dq), C.byref(dv), self.prec, N, int(q.double_q))
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_idql_q_loss_workspace_bytes")
-        ws = self._ws_q.get(wsb, dev)
+        ws = self._ws_q.get(lib.dppo_idql_q_loss_workspace_bytes(C.byref(dq), C.byref(dv), self.prec, N, int(q.double_q)), dev,
+                            "dppo_idql_q_loss_workspace_bytes")
         k1, k2 = q.packed(self.prec)
         stats = torch.empty(hip.IDQL_STAT_COUNT, dtype=torch.float64, device=dev)
         hip.check(lib.dppo_idql_q_loss_fwd_bwd(
             C.byref(dq), C.byref(dv), self.prec, q.flat_params().data_ptr(), k1.data_ptr(), hip.ptr(k2),
             v.flat_params().data_ptr(), v.packed(self.prec, 0).data_ptr(), C.byref(batch), N, float(gamma), int(q.double_q),
             q.flat_grads().data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_idql_q_loss_fwd_bwd")
-        return self._shim(q, stats)
+        return off_policy.critic_loss(self, q, stats)
 
     @torch.no_grad()
     def update_target_critic(self, tau):
-        """target <- target * (1 - tau) + source * tau over the flat [Q1 | Q2] image, then the target's kernel images are stale."""
-        t, s = self.target_q.flat_params(), self.critic_q.flat_params()
-        hip.check(hip.load().dppo_polyak(t.data_ptr(), s.data_ptr(), float(tau), t.numel(), hip.stream()), "dppo_polyak")
-        self.target_q.mark_updated()
+        off_policy.polyak(self.target_q, self.critic_q, tau)
 
     # ------------------------------------------------------------------ sampling (reference :125-188)
     @torch.no_grad()

@@ -15,9 +15,8 @@ import ctypes as C
 import torch
 
 from dppo_amd import hip
+from dppo_amd.model.common import off_policy
 from dppo_amd.model.diffusion.diffusion import DiffusionModel
-from dppo_amd.model.diffusion.diffusion_idql import IDQLDiffusion
-from dppo_amd.util.replay import DeviceReplay
 
 
 class QSMDiffusion(DiffusionModel):
@@ -35,19 +34,6 @@ class QSMDiffusion(DiffusionModel):
         object.__setattr__(self, "_ws_target", hip.Workspace())
         object.__setattr__(self, "_ws_q", hip.Workspace())
 
-    @staticmethod
-    def _state(obs):
-        if isinstance(obs, dict):
-            if "rgb" in obs:
-                raise NotImplementedError("dppo_amd: QSM is built for state observations only (like the reference)")
-            obs = obs["state"]
-        return obs
-
-    # batches, the loss shim and the Polyak target are IDQL's (same ring, same twin)
-    _as_batch = IDQLDiffusion._as_batch
-    _shim = IDQLDiffusion._shim
-    update_target_critic = IDQLDiffusion.update_target_critic
-
     def _tables(self, dev):
         """sqrt(abar), sqrt(1 - abar) on the device (the schedule is fixed after construction; one pair per device)."""
         cache = self.__dict__.setdefault("_qsample_cache", {})
@@ -64,7 +50,7 @@ class QSMDiffusion(DiffusionModel):
         (parity runs).  The flat actor gradient is left in ``last_loss_grad`` like ``DiffusionModel.loss``; ``want_grad``:
         g (N, Ta*Da) in ``last_q_grad``."""
         q = self.critic_q
-        batch, N, keep = self._as_batch(obs, actions, inds=inds)
+        batch, N, keep = off_policy.as_batch("QSM", obs, inds, actions)
         dev = q.flat_params().device
         AF, K = self.horizon_steps * self.action_dim, self.denoising_steps
         if noise is None:
@@ -77,10 +63,8 @@ class QSMDiffusion(DiffusionModel):
         t = t.reshape(N).to(torch.int64).contiguous()
         lib, dq = hip.load(), q.net_desc()
         OD = q.cond_dim
-        wsb = lib.dppo_qsm_actor_target_workspace_bytes(C.byref(dq), self.prec, OD, N)
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_qsm_actor_target_workspace_bytes")
-        ws = self._ws_target.get(wsb, dev)
+        ws = self._ws_target.get(lib.dppo_qsm_actor_target_workspace_bytes(C.byref(dq), self.prec, OD, N), dev,
+                                 "dppo_qsm_actor_target_workspace_bytes")
         k1, k2 = q.packed(self.prec)
         sa, sb = self._tables(dev)
         pairs = torch.empty(N, 2, AF, dtype=torch.float32, device=dev)
@@ -98,32 +82,11 @@ class QSMDiffusion(DiffusionModel):
         """mean((q1 - y)^2) + mean((q2 - y)^2), y = r + gamma min(target q1, q2)(s', a') (1 - terminated); d loss / d [Q1 | Q2]
         parameters in ``critic_q.flat_grads()``, ``last_stats``: {loss, mean q1, mean y}.  ``next_actions`` None: a' is sampled
         with ``forward`` at the gathered next observations (``noise`` (K+1, N, Ta, Da) replaces its draws)."""
-        q, tq = self.critic_q, self.target_q
-        batch, N, keep = self._as_batch(obs, actions, next_obs, rewards, terminated, inds=inds)
-        dev = q.flat_params().device
-        if next_actions is None:
-            if isinstance(obs, DeviceReplay):
-                rows = torch.arange(len(obs), device=dev) if inds is None else inds
-                nxt = obs.gather(rows)[1]
-            else:
-                nxt = self._state(next_obs)
-            next_actions = self.forward({"state": nxt.reshape(N, -1)}, deterministic=False, noise=noise)
-        next_actions = next_actions.reshape(N, -1).contiguous().float()
-        lib, dq = hip.load(), q.net_desc()
-        OD = q.cond_dim
-        assert next_actions.shape[1] == dq.in_dim - OD, "next_actions must be (N, Ta, Da)"
-        wsb = lib.dppo_qsm_q_loss_workspace_bytes(C.byref(dq), self.prec, OD, N)
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_qsm_q_loss_workspace_bytes")
-        ws = self._ws_q.get(wsb, dev)
-        k1, k2 = q.packed(self.prec)
-        t1, t2 = tq.packed(self.prec)
-        stats = torch.empty(hip.IDQL_STAT_COUNT, dtype=torch.float64, device=dev)
-        hip.check(lib.dppo_qsm_q_loss_fwd_bwd(
-            C.byref(dq), self.prec, q.flat_params().data_ptr(), k1.data_ptr(), hip.ptr(k2), tq.flat_params().data_ptr(),
-            t1.data_ptr(), hip.ptr(t2), C.byref(batch), OD, next_actions.data_ptr(), N, float(gamma), q.flat_grads().data_ptr(),
-            stats.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_qsm_q_loss_fwd_bwd")
-        return self._shim(q, stats)
+        return off_policy.twin_td_loss(self, "QSM", self.critic_q, self.target_q, obs, next_obs, actions, rewards, terminated, gamma,
+                                       inds, next_actions, noise)
+
+    def update_target_critic(self, tau):
+        off_policy.polyak(self.target_q, self.critic_q, tau)
 
     # ------------------------------------------------------------------ sampling (reference diffusion_rwr.py:65-103)
     @torch.no_grad()

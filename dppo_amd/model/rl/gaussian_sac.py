@@ -16,8 +16,9 @@ import ctypes as C
 import torch
 
 from dppo_amd import hip
+from dppo_amd.model.common import off_policy
 from dppo_amd.model.common.gaussian import GaussianModel
-from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss
+from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss, flat_views
 from dppo_amd.util.replay import DeviceReplay
 
 
@@ -37,30 +38,6 @@ class SAC_Gaussian(GaussianModel):
         self.target_critic = copy.deepcopy(self.critic).to(self.device)
         for name in ("_ws_s", "_ws_actor", "_ws_q"):
             object.__setattr__(self, name, hip.Workspace())
-
-    @staticmethod
-    def _state(obs):
-        if isinstance(obs, dict):
-            if "rgb" in obs:
-                raise NotImplementedError("dppo_amd: SAC is built for state observations only (like the reference)")
-            obs = obs["state"]
-        return obs
-
-    def _batch(self, obs, inds=None, actions=None, next_obs=None, rewards=None, terminated=None):
-        """(dppo_idql_batch, N, tensors to keep alive).  ``obs``: a ``DeviceReplay`` (rows ``inds``, or all of it) or the
-        reference's ``{"state": (N, To, Do)}`` with plain (N, ...) companions (any may be missing)."""
-        if isinstance(obs, DeviceReplay):
-            N = len(obs) if inds is None else inds.numel()
-            if inds is not None:
-                assert inds.dtype == torch.int64 and inds.is_contiguous() and inds.is_cuda
-            return obs.batch(inds), N, (inds,)
-        st = self._state(obs)
-        hip.require_gpu(st, type(self).__name__)
-        N = st.shape[0]
-        flat = lambda x, *s: None if x is None else x.reshape(N, *s).contiguous().float()
-        keep = [flat(st, -1), None if next_obs is None else flat(self._state(next_obs), -1), flat(actions, -1), flat(rewards),
-                flat(terminated)]
-        return hip.IdqlBatch(*[hip.ptr(k) for k in keep], None, N, 1, 0, N), N, keep
 
     @staticmethod
     def _dev_scalar(x, dev):
@@ -84,7 +61,7 @@ class SAC_Gaussian(GaussianModel):
         ``reparameterize`` changes nothing about the VALUE (the gradient through the sample is ``loss_actor``'s business).
         ``noise`` (B, Ta, Da) replaces the in-kernel draws; ``want_u``: the pre-squash sample in ``last_u``."""
         net = network_override if network_override is not None else self.network
-        state = self._state(cond)
+        state = off_policy.state_of(cond, "SAC")
         hip.require_gpu(state, type(self).__name__ + ".forward")
         B, dev = state.shape[0], state.device
         AF = net.action_dim * net.horizon_steps
@@ -96,10 +73,7 @@ class SAC_Gaussian(GaussianModel):
         actions = torch.empty(B, AF, device=dev)
         logp = torch.empty(B, device=dev) if get_logprob else None
         u = torch.empty(B, AF, device=dev) if want_u else None
-        wsb = lib.dppo_sac_sample_workspace_bytes(C.byref(d), self.prec, B)
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_sac_sample_workspace_bytes")
-        ws = self._ws_s.get(wsb, dev)
+        ws = self._ws_s.get(lib.dppo_sac_sample_workspace_bytes(C.byref(d), self.prec, B), dev, "dppo_sac_sample_workspace_bytes")
         hip.check(lib.dppo_sac_sample(
             C.byref(d), self.prec, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(), C.byref(cfg), obs.data_ptr(),
             hip.ptr(noise), B, actions.data_ptr(), hip.ptr(logp), hip.ptr(u), ws.data_ptr(), ws.numel(), hip.stream()),
@@ -107,15 +81,6 @@ class SAC_Gaussian(GaussianModel):
         object.__setattr__(self, "last_u", u)
         actions = actions.view(B, self.horizon_steps, -1)
         return (actions, logp) if get_logprob else actions
-
-    def _rows(self, obs, inds, which):
-        """The gathered observations (0) or next observations (1) of a minibatch as (N, Do*To)."""
-        if isinstance(obs, DeviceReplay):  # (one gather, not DeviceReplay.gather's five)
-            src = obs.next_obs if which else obs.obs
-            flat = src.reshape(obs.cap * obs.n_envs, -1)
-            return flat[:len(obs)] if inds is None and obs.head == 0 else flat[obs.slot_of(
-                torch.arange(len(obs), device=src.device) if inds is None else inds)]
-        return self._state(obs)
 
     # ------------------------------------------------------------------ RL training (reference gaussian_sac.py:31-88)
     def loss_critic(self, obs, next_obs, actions, rewards, terminated, gamma, alpha, inds=None, next_actions=None, next_logp=None,
@@ -125,10 +90,10 @@ class SAC_Gaussian(GaussianModel):
         mean q1, mean y}.  ``obs`` may be a ``DeviceReplay`` (rows ``inds``).  ``next_actions`` (N, Ta, Da) with ``next_logp``
         (N,), or ``noise`` (N, Ta, Da), replace the sample / its draws."""
         q, tq = self.critic, self.target_critic
-        batch, N, keep = self._batch(obs, inds, actions, next_obs, rewards, terminated)
+        batch, N, keep = off_policy.as_batch("SAC", obs, inds, actions, next_obs, rewards, terminated)
         dev = q.flat_params().device
         if next_actions is None:
-            nxt = self._rows(obs if isinstance(obs, DeviceReplay) else next_obs, inds, 1 if isinstance(obs, DeviceReplay) else 0)
+            nxt = off_policy.rows_of("SAC", obs, inds, nxt=True) if isinstance(obs, DeviceReplay) else off_policy.state_of(next_obs, "SAC")
             next_actions, next_logp = self.forward({"state": nxt.reshape(N, -1)}, deterministic=False, get_logprob=True, noise=noise)
         assert next_logp is not None, "next_actions needs next_logp"
         next_actions = next_actions.reshape(N, -1).contiguous().float()
@@ -137,10 +102,7 @@ class SAC_Gaussian(GaussianModel):
         lib, dq = hip.load(), q.net_desc()
         OD = q.cond_dim
         assert next_actions.shape[1] == dq.in_dim - OD, "next_actions must be (N, Ta, Da)"
-        wsb = lib.dppo_sac_q_loss_workspace_bytes(C.byref(dq), self.prec, OD, N)
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_sac_q_loss_workspace_bytes")
-        ws = self._ws_q.get(wsb, dev)
+        ws = self._ws_q.get(lib.dppo_sac_q_loss_workspace_bytes(C.byref(dq), self.prec, OD, N), dev, "dppo_sac_q_loss_workspace_bytes")
         k1, k2 = q.packed(self.prec)
         t1, t2 = tq.packed(self.prec)
         stats = torch.empty(hip.IDQL_STAT_COUNT, dtype=torch.float64, device=dev)
@@ -149,8 +111,7 @@ class SAC_Gaussian(GaussianModel):
             t1.data_ptr(), hip.ptr(t2), C.byref(batch), OD, next_actions.data_ptr(), next_logp.data_ptr(), alpha.data_ptr(), N,
             float(gamma), q.flat_grads().data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()),
             "dppo_sac_q_loss_fwd_bwd")
-        object.__setattr__(self, "last_stats", stats)
-        return _FusedDenoiseLoss.apply(stats[0], q.grad_views(), *q.trunk_parameters())
+        return off_policy.critic_loss(self, q, stats)
 
     def loss_actor(self, obs, alpha, inds=None, noise=None):
         """mean(-min(q1, q2)(s, a) + alpha logp(a)) on a reparameterised sample, and d loss / d actor parameters in
@@ -158,7 +119,7 @@ class SAC_Gaussian(GaussianModel):
         ``last_d_a`` (N, Ta*Da) = d loss / d a through the critic; ``last_logp`` (N,); ``last_sel`` (N,) bytes (1: Q2 was the
         smaller); ``last_actions`` (N, Ta*Da)."""
         q, net = self.critic, self.network
-        batch, N, keep = self._batch(obs, inds)
+        batch, N, keep = off_policy.as_batch("SAC", obs, inds)
         dev = net.flat_params().device
         AF = self.horizon_steps * net.action_dim
         cfg = self._cfg(False, noise)
@@ -167,10 +128,8 @@ class SAC_Gaussian(GaussianModel):
         alpha = self._dev_scalar(alpha, dev)
         lib, da, dq = hip.load(), net.net_desc(), q.net_desc()
         OD = q.cond_dim
-        wsb = lib.dppo_sac_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N)
-        if wsb < 0:
-            hip.check(int(wsb), "dppo_sac_actor_workspace_bytes")
-        ws = self._ws_actor.get(wsb, dev)
+        ws = self._ws_actor.get(lib.dppo_sac_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N), dev,
+                                "dppo_sac_actor_workspace_bytes")
         k1, k2 = q.packed(self.prec)
         grad = torch.empty_like(net.flat_params())
         stats = torch.empty(hip.SAC_STAT_COUNT, dtype=torch.float64, device=dev)
@@ -187,18 +146,14 @@ class SAC_Gaussian(GaussianModel):
                         ("last_actions", actions)):
             object.__setattr__(self, name, v)
         params = net.trunk_parameters()
-        views, off = [], 0
-        for p in params:
-            views.append(grad[off:off + p.numel()].view(p.shape))
-            off += p.numel()
-        return _FusedDenoiseLoss.apply(stats[0], views, *params)
+        return _FusedDenoiseLoss.apply(stats[0], flat_views(grad, params), *params)
 
     def loss_temperature(self, obs, log_alpha, target_entropy, inds=None, noise=None, logp=None):
         """-mean(alpha (logp + target_entropy)) with alpha = exp(log_alpha), logp of a fresh sample at ``obs`` without gradient
         (``logp`` (N,) given: that one).  ``log_alpha``: the device float64 leaf the reference exponentiates before the call;
         ``.backward()`` hands it d loss / d log_alpha, which also stays in ``last_alpha_out[1]``."""
         if logp is None:
-            st = self._rows(obs, inds, 0)
+            st = off_policy.rows_of("SAC", obs, inds)
             _, logp = self.forward({"state": st.reshape(st.shape[0], -1)}, deterministic=False, get_logprob=True, noise=noise)
         logp = logp.reshape(-1).contiguous().float()
         hip.require_gpu(logp, "SAC_Gaussian.loss_temperature")
@@ -211,7 +166,4 @@ class SAC_Gaussian(GaussianModel):
         return _FusedDenoiseLoss.apply(out[0], [out[1].reshape(log_alpha.shape)], log_alpha)
 
     def update_target_critic(self, tau):
-        """target <- target * (1 - tau) + source * tau over the flat [Q1 | Q2] image, then the target's kernel images are stale."""
-        t, s = self.target_critic.flat_params(), self.critic.flat_params()
-        hip.check(hip.load().dppo_polyak(t.data_ptr(), s.data_ptr(), float(tau), t.numel(), hip.stream()), "dppo_polyak")
-        self.target_critic.mark_updated()
+        off_policy.polyak(self.target_critic, self.critic, tau)
