@@ -14,6 +14,7 @@
 #include "qsm.h"
 #include "dql.h"
 #include "sac.h"
+#include "rlpd.h"
 #include "unet.h"
 #include "sampler.h"
 
@@ -58,6 +59,7 @@ static int check_launch() {
 struct ParamLayout {  // float offsets into the flat fp32 parameter / gradient buffer (state-dict order)
   int64_t te1_w, te1_b, te2_w, te2_b, c1w, c1b, c2w, c2b, W0, b0, l1w[MAX_BLOCKS], l1b[MAX_BLOCKS], l2w[MAX_BLOCKS], l2b[MAX_BLOCKS],
       n1w[MAX_BLOCKS], n1b[MAX_BLOCKS], n2w[MAX_BLOCKS], n2b[MAX_BLOCKS], Wout, bout, total;
+  int64_t n0w, n0b;  // plain trunk with LayerNorm: layer 0's norm_1 (the hidden layers' are n1w / n1b)
 };
 static ParamLayout param_layout(const dppo_net_desc& d) {
   ParamLayout L;
@@ -78,9 +80,18 @@ static ParamLayout param_layout(const dppo_net_desc& d) {
   }
   L.W0 = o, o += (int64_t)H * d.in_dim;
   L.b0 = o, o += H;
+  const bool plain_ln = d.plain && d.use_layernorm;  // linear_1.weight, linear_1.bias, norm_1.weight, norm_1.bias per hidden layer
+  if (plain_ln) {
+    L.n0w = o, o += H;
+    L.n0b = o, o += H;
+  }
   for (int b = 0; b < d.n_blocks; ++b) {
     L.l1w[b] = o, o += (int64_t)H * H;
     L.l1b[b] = o, o += H;
+    if (plain_ln) {
+      L.n1w[b] = o, o += H;
+      L.n1b[b] = o, o += H;
+    }
     if (d.plain) continue;  // a plain MLP's hidden layers are single Linear(H, H) modules (mlp.py:46-74)
     L.l2w[b] = o, o += (int64_t)H * H;
     L.l2b[b] = o, o += H;
@@ -165,14 +176,19 @@ static PackLayout pack_layout(const dppo_net_desc& d, int n_time) {
   return L;
 }
 
-static int check_net(const dppo_net_desc* d) {
+// ln_plain: the caller reads a plain kind-1 trunk with LayerNorm (rlpd.h); every other entry refuses one
+static int check_net(const dppo_net_desc* d, bool ln_plain = false) {
   if (!d) return fail(-1, "null net descriptor");
   if (d->kind != 0 && d->kind != 1) return fail(-1, "net.kind must be 0 (actor) or 1 (critic)");
   if (d->plain != 0 && d->plain != 1) return fail(-1, "plain must be 0 or 1");
   if (d->plain) {  // non-residual MLP trunk (model/common/mlp.py:27-81): layered GEMM path only
     if (d->hidden < 64 || d->hidden % 64) return fail(-1, "plain MLP: hidden=%d must be a positive multiple of 64", d->hidden);
     if (d->n_blocks < 1) return fail(-1, "plain MLP: at least two hidden widths (n_blocks = hidden-to-hidden layers >= 1)");
-    if (d->use_layernorm || d->cond_hidden || d->cond_out) return fail(-1, "plain MLP: LayerNorm / cond_mlp are not built");
+    if (d->cond_hidden || d->cond_out) return fail(-1, "plain MLP: cond_mlp is not built");
+    if (d->use_layernorm == 1 && d->kind == 0) return fail(-1, "plain MLP: LayerNorm is built for kind-1 (critic) trunks only");
+    if (d->use_layernorm == 1 && !ln_plain)
+      return fail(-1, "plain MLP with LayerNorm: this entry is not taught it; dppo_idql_q_forward with double_q = 0 and dppo_rlpd_q_loss_fwd_bwd read such a trunk");
+    if (d->use_layernorm == 1 && d->hidden > LN_MAX_H) return fail(-1, "plain MLP with LayerNorm: hidden=%d above %d", d->hidden, LN_MAX_H);
   } else if (d->hidden < 128 || d->hidden % 128) return fail(-1, "hidden=%d must be a positive multiple of 128", d->hidden);
   if (d->n_blocks < 0 || d->n_blocks > MAX_BLOCKS) return fail(-1, "n_blocks=%d out of [0,%d]", d->n_blocks, MAX_BLOCKS);
   if (d->act != DPPO_ACT_RELU && d->act != DPPO_ACT_MISH) return fail(-1, "activation %d unsupported", d->act);
@@ -194,7 +210,7 @@ static int check_net(const dppo_net_desc* d) {
   }
   if (d->in_dim < 1 || d->in_dim > 1024) return fail(-1, "in_dim=%d out of [1,1024]", d->in_dim);
   if (d->use_layernorm != 0 && d->use_layernorm != 1) return fail(-1, "use_layernorm must be 0 or 1");
-  if (d->use_layernorm && !(d->hidden == 256 || d->hidden == 512 || d->hidden == 1024))
+  if (d->use_layernorm && !d->plain && !(d->hidden == 256 || d->hidden == 512 || d->hidden == 1024))
     return fail(-1, "LayerNorm blocks need hidden in {256, 512, 1024} (fused kernels only), got %d", d->hidden);
   return 0;
 }
@@ -401,7 +417,8 @@ struct MlpBufs {  // activations of one network for M rows
   void* d_cz;    // [M][C1p]
   void* dh_all[MAX_BLOCKS + 1];  // fused backward: dh[b] = d loss / d h_b, elem [M][H]
   void* dz1_all[MAX_BLOCKS];
-  float* ln_stats;               // [nb][2][M][2] LayerNorm row statistics (training)
+  float* ln_stats;               // [nb][2][M][2] LayerNorm row statistics (training); a plain trunk uses [nb + 1][M][2] of it
+  float* ln_part;                // plain trunk with LayerNorm, backward: [ln_bwd_blocks(M)][2][H] partial parameter sums
   const void* dh0_final;         // where the last backward left d loss / d h_0
   void* w0T;                     // [cond_dim][H] elem: layer 0's observation columns, transposed (obs_grad)
   float* dobs;                   // [M][round_up(cond_dim, 16)]: obs_grad's GEMM output (the epilogue stores 16-column groups)
@@ -510,6 +527,7 @@ static void carve_mlp(Carver& c, const dppo_net_desc& d, int64_t M, bool keep, b
     B.tail_counter = (unsigned*)(B.post_counter + 1);
     B.w0T = c.take((size_t)round_up(d.cond_dim > 0 ? d.cond_dim : 1, 16) * H * ES);
     B.dobs = (float*)c.take((size_t)M * round_up(d.cond_dim > 0 ? d.cond_dim : 1, 16) * 4);
+    if (d.plain && d.use_layernorm) B.ln_part = (float*)c.take((size_t)ln_bwd_blocks(M) * 2 * H * 4);
     // the route of a caller that has nothing to add (no denoising steps, no zeroed counters, no side stream); the entry points
     // that do (BC, denoise-MSE, PPO) plan again with their own inputs before they build their rows
     plan_route<P>(d, M, 0, 0, B);
@@ -592,13 +610,30 @@ static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk
     memset(&q, 0, sizeof(q));
     q.M = (int)M, q.X = B.in, q.ldx = L.Kp0, q.W = pk + L.W0, q.ldw = L.Kp0, q.Kp = L.Kp0, q.N = H, q.bias = prm + pl.b0;
     q.ldo = H, q.act = d.act, q.out_act = B.a1[0], q.out_pre = keep ? B.hpre[0] : nullptr;
+    // LayerNorm (rlpd.h): the GEMM leaves its bias-added row in fp32 (B.h[.], carved for every trunk and unused by a plain one
+    // without LayerNorm), the row kernel writes act(z) and, kept, z where the GEMM's own epilogue would have
+    LnRows ln;
+    memset(&ln, 0, sizeof(ln));
+    ln.M = M, ln.H = H, ln.act = d.act, ln.ldx = H, ln.ldo = H;
+    if (d.use_layernorm) {
+      ln.x = B.h[0], ln.gamma = prm + pl.n0w, ln.beta = prm + pl.n0b, ln.out_act = q.out_act, ln.out_z = q.out_pre;
+      ln.stats = keep ? B.ln_stats : nullptr;
+      q.out_act = q.out_pre = nullptr, q.out_f32 = B.h[0], q.ldo32 = H;
+    }
     launch_gemm_nt<P>(q, s);
+    if (d.use_layernorm) launch_ln_rows<P>(ln, s);
     for (int b = 0; b < nb; ++b) {
       memset(&q, 0, sizeof(q));
       q.M = (int)M, q.N = H, q.Kp = H, q.ldx = H, q.ldw = H, q.ldo = H, q.act = d.act;
       q.X = b == 0 ? B.a1[0] : B.a2[b - 1], q.W = pk + L.W1[b], q.bias = prm + pl.l1b[b];
       q.out_pre = keep ? B.z1[b] : nullptr, q.out_act = B.a2[b];
+      if (d.use_layernorm) {
+        ln.x = B.h[b + 1], ln.gamma = prm + pl.n1w[b], ln.beta = prm + pl.n1b[b], ln.out_act = q.out_act, ln.out_z = q.out_pre;
+        ln.stats = keep ? B.ln_stats + (size_t)(b + 1) * M * 2 : nullptr;
+        q.out_act = q.out_pre = nullptr, q.out_f32 = B.h[b + 1], q.ldo32 = H;
+      }
       launch_gemm_nt<P>(q, s);
+      if (d.use_layernorm) launch_ln_rows<P>(ln, s);
     }
     memset(&q, 0, sizeof(q));
     q.M = (int)M, q.N = d.out_dim, q.Kp = H, q.ldx = H, q.ldw = H;
@@ -1110,7 +1145,16 @@ static void backward_plain(const dppo_net_desc& d, const float* prm, const char*
   launch_gemm_nt<P>(q, s);
   void* dz = B.dh;
   void* other = B.dz1;
+  // LayerNorm (rlpd.h): dz is d loss / d z here; in place it becomes d loss / d (the Linear's output), what the steps below read
+  LnBwd ln;
+  memset(&ln, 0, sizeof(ln));
+  ln.ld = H, ln.ldx = H, ln.M = M, ln.H = H, ln.partial = B.ln_part;
   for (int b = nb - 1; b >= 0; --b) {
+    if (d.use_layernorm) {
+      ln.dz = dz, ln.x = B.h[b + 1], ln.stats = B.ln_stats + (size_t)(b + 1) * M * 2, ln.gamma = prm + pl.n1w[b];
+      ln.dgamma = grad + pl.n1w[b], ln.dbeta = grad + pl.n1b[b];
+      launch_ln_bwd<P>(ln, s);
+    }
     weight_grad<P>(dz, H, H, b == 0 ? B.a1[0] : B.a2[b - 1], H, H, M, B, grad + pl.l1w[b], H, s);
     launch_colsum<P>(dz, (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.l1b[b], 1.f, s);
     memset(&q, 0, sizeof(q));
@@ -1120,6 +1164,10 @@ static void backward_plain(const dppo_net_desc& d, const float* prm, const char*
     launch_gemm_nt<P>(q, s);
     void* t = dz;
     dz = other, other = t;
+  }
+  if (d.use_layernorm) {
+    ln.dz = dz, ln.x = B.h[0], ln.stats = B.ln_stats, ln.gamma = prm + pl.n0w, ln.dgamma = grad + pl.n0w, ln.dbeta = grad + pl.n0b;
+    launch_ln_bwd<P>(ln, s);
   }
   weight_grad<P>(dz, H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s);
   launch_colsum<P>(dz, (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.b0, 1.f, s);
@@ -1205,12 +1253,12 @@ int dppo_version(void) { return 1; }
 const char* dppo_last_error(void) { return g_err; }
 
 int64_t dppo_net_param_count(const dppo_net_desc* net) {
-  if (check_net(net)) return -1;
+  if (check_net(net, true)) return -1;
   return param_layout(*net).total;
 }
 
 int64_t dppo_packed_bytes(const dppo_net_desc* net, int prec, int n_time) {
-  if (check_net(net) || check_prec(prec)) return -1;
+  if (check_net(net, true) || check_prec(prec)) return -1;
   if (n_time < 0) return fail(-1, "n_time < 0");
 #define CALL(P) (int64_t) pack_layout<P>(*net, n_time).total
   return DPPO_DISPATCH(prec, CALL);
@@ -1245,8 +1293,8 @@ static int pack_two_impl(const dppo_net_desc& d0, int t0, const float* p0, char*
 int dppo_pack_nets(const dppo_net_desc* net0, int n_time0, const float* params0, void* packed0,
                    const dppo_net_desc* net1, int n_time1, const float* params1, void* packed1, int prec,
                    dppo_stream_t stream) {
-  if (int e = check_net(net0)) return e;
-  if (int e = check_net(net1)) return e;
+  if (int e = check_net(net0, true)) return e;
+  if (int e = check_net(net1, true)) return e;
   if (int e = check_prec(prec)) return e;
   if (!params0 || !packed0 || !params1 || !packed1) return fail(-1, "null pointer");
   if ((net0->kind == 0 && n_time0 < 1) || (net1->kind == 0 && n_time1 < 1)) return fail(-1, "actor needs n_time >= 1");
@@ -1258,7 +1306,7 @@ int dppo_pack_nets(const dppo_net_desc* net0, int n_time0, const float* params0,
 
 int dppo_pack_net(const dppo_net_desc* net, int prec, int n_time, const float* params, void* packed,
                   dppo_stream_t stream) {
-  if (int e = check_net(net)) return e;
+  if (int e = check_net(net, true)) return e;
   if (int e = check_prec(prec)) return e;
   if (!params || !packed) return fail(-1, "null pointer");
   if (net->kind == 0 && n_time < 1) return fail(-1, "actor needs n_time >= 1");
@@ -2608,8 +2656,8 @@ int dppo_unet_denoise_mse_fwd_bwd_obs(const dppo_unet_desc* net, int prec, const
 }
 
 // ---- IDQL (idql.hip): twin-Q critics, expectile V, best-of-N selection, Polyak target -----------------------------------------
-static int check_idql_q(const dppo_net_desc* q) {
-  if (int e = check_net(q)) return e;
+static int check_idql_q(const dppo_net_desc* q, bool ln_plain = false) {
+  if (int e = check_net(q, ln_plain)) return e;
   if (q->kind != 1 || q->out_dim != 1) return fail(-1, "a Q trunk is a kind-1 descriptor with out_dim 1");
   return 0;
 }
@@ -2650,7 +2698,8 @@ static size_t carve_idql(Carver& c, const dppo_net_desc& q, const dppo_net_desc*
 }
 static int64_t idql_ws_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int prec, int64_t N, int double_q, bool train_q,
                              bool train_v) {
-  if ((v ? check_idql_pair(q, v) : check_idql_q(q)) || check_prec(prec)) return -1;
+  // (no V, no training: dppo_idql_q_forward, which reads one LayerNorm trunk -- a twin of them is not built)
+  if ((v ? check_idql_pair(q, v) : check_idql_q(q, !double_q && !train_q)) || check_prec(prec)) return -1;
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
   return ws_bytes(prec, [&](Carver& c, auto p) {
     IdqlWs<decltype(p)> W;
@@ -2804,7 +2853,7 @@ static int idql_fwd_impl(const dppo_net_desc& q, const float* qp, const char* qk
 int dppo_idql_q_forward(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
                         const float* obs, int obs_dim, int64_t obs_rows, const float* actions, int64_t N, int double_q,
                         float* q1_out, float* q2_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream) {
-  if (int e = check_idql_q(q)) return e;
+  if (int e = check_idql_q(q, !double_q)) return e;
   if (int e = check_prec(prec)) return e;
   if (!q_params || !q1_packed || !obs || !actions || !q1_out || !workspace || (double_q && (!q2_packed || !q2_out)))
     return fail(-1, "null pointer");
@@ -3051,6 +3100,108 @@ int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
   twin_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
                   (const char*)target_q2_packed, *batch, obs_dim, next_actions, nullptr, nullptr, N, gamma, q_grad, stats,      \
                   workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+// ---- RLPD (rlpd.hip): the TD loss of an ensemble of LayerNorm Q trunks -----------------------------------------------------------
+static int check_rlpd_q(const dppo_net_desc* q, int obs_dim, int E) {
+  if (int e = check_idql_q(q, true)) return e;
+  if (!q->plain || !q->use_layernorm) return fail(-1, "the ensemble's members are plain trunks with LayerNorm (plain = 1, use_layernorm = 1)");
+  if (obs_dim < 1 || obs_dim >= q->in_dim)
+    return fail(-1, "Q descriptor does not pair with obs_dim=%d: in_dim=%d must be obs_dim + the action width", obs_dim, q->in_dim);
+  if (E < 2 || E > RLPD_MAX_E) return fail(-1, "E=%d members out of [2, %d]", E, RLPD_MAX_E);
+  return 0;
+}
+template <class P>
+struct RlpdTdWs {
+  MlpBufs<P> Q[RLPD_MAX_E], T[2];
+  double* partial;
+  float *r, *term;
+};
+template <class P>
+static size_t carve_rlpd_td(Carver& c, const dppo_net_desc& q, int64_t N, int E, RlpdTdWs<P>& W) {
+  W.partial = (double*)c.take((size_t)E * rlpd_blocks(N) * 4 * sizeof(double));
+  W.r = (float*)c.take((size_t)N * 4);
+  W.term = (float*)c.take((size_t)N * 4);
+  for (int e = 0; e < E; ++e) carve_mlp<P>(c, q, N, true, true, W.Q[e]);
+  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, q, N, false, false, W.T[i]);
+  return al256(c.off);
+}
+int64_t dppo_rlpd_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
+  if (check_rlpd_q(q, obs_dim, E) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    RlpdTdWs<decltype(p)> W;
+    return carve_rlpd_td<decltype(p)>(c, *q, N, E, W);
+  });
+}
+template <class P>
+static int rlpd_td_impl(const dppo_net_desc& q, int E, const float* qp, const void* const* qk, const float* tp, const char* tk1,
+                        const char* tk2, int p0, int p1, const dppo_idql_batch& b, int OD, const float* next_actions,
+                        const float* next_logp, const double* alpha, int64_t N, double gamma, float* qgrad, double* stats, void* ws,
+                        int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  RlpdTdWs<P> W;
+  const size_t need = carve_rlpd_td<P>(c, q, N, E, W);
+  // every member's buffers sit at one stride: the loss kernel reaches member e's from member 0's
+  const int64_t q_stride = W.Q[1].out - W.Q[0].out, d_stride = (char*)W.Q[1].d_out - (char*)W.Q[0].d_out;
+  bool even = true;
+  for (int e = 1; e < E; ++e) even = even && W.Q[e].out - W.Q[0].out == e * q_stride && (char*)W.Q[e].d_out - (char*)W.Q[0].d_out == e * d_stride;
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (!even) return fail(-1, "members' workspaces are not evenly spaced");
+  const PackLayout L = pack_layout<P>(q, 0);
+  const int64_t nq = param_layout(q).total;
+  // every member reads the same rows [obs | a | 0], both targets the same [next_obs | next_a | 0]: one image each
+  QsmTdRows r;
+  memset(&r, 0, sizeof(r));
+  r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
+  r.next_actions = next_actions, r.q1in = r.q2in = W.Q[0].in, r.t1in = r.t2in = W.T[0].in, r.KpQ = L.Kp0;
+  r.r_out = W.r, r.term_out = W.term;
+  launch_qsm_td_rows<P>(r, s);
+  for (int e = 1; e < E; ++e) W.Q[e].in = W.Q[0].in;
+  W.T[1].in = W.T[0].in;
+  // the trunks take turns on the caller's stream and the three side streams
+  hipStream_t st[4] = {s, fork_side(s, 0), fork_side(s, 1), fork_side(s, 2)};
+  mlp_forward<P>(q, tp + p0 * nq, tk1, L, N, W.T[0], false, st[1]);
+  mlp_forward<P>(q, tp + p1 * nq, tk2, L, N, W.T[1], false, st[2]);
+  for (int e = 0; e < E; ++e) mlp_forward<P>(q, qp + e * nq, (const char*)qk[e], L, N, W.Q[e], true, st[(e + 3) & 3]);
+  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
+  RlpdLoss l;
+  memset(&l, 0, sizeof(l));
+  l.q = W.Q[0].out, l.q_stride = q_stride, l.ldq = W.Q[0].ldout, l.t1 = W.T[0].out, l.t2 = W.T[1].out, l.ldt = W.T[0].ldout;
+  l.reward = W.r, l.terminated = W.term, l.next_logp = next_logp, l.alpha = alpha, l.gamma = (float)gamma, l.N = N, l.E = E;
+  l.d_out = W.Q[0].d_out, l.d_stride = d_stride, l.ldd = L.Kpo, l.partial = W.partial, l.stats = stats;
+  launch_rlpd_loss<P>(l, s);
+  for (int i = 1; i < 4; ++i) st[i] = fork_side(s, i - 1);
+  for (int e = 0; e < E; ++e)
+    mlp_backward<P>(q, qp + e * nq, (const char*)qk[e], L, N, W.Q[e], qgrad + e * nq, nullptr, nullptr, 0, st[e & 3]);
+  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
+  launch_rlpd_out_bias(W.partial, N, E, qgrad, nq, param_layout(q).bout, s);
+  return check_launch();
+}
+int dppo_rlpd_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const float* q_params, const void* const* q_packed,
+                             const float* target_q_params, const void* const* target_q_packed, int pair0, int pair1,
+                             const dppo_idql_batch* batch, int obs_dim, const float* next_actions, const float* next_logp,
+                             const double* alpha, int64_t N, double gamma, float* q_grad, double* stats, void* workspace,
+                             int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_rlpd_q(q, obs_dim, E)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!q_params || !q_packed || !target_q_params || !target_q_packed || !next_actions || !q_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  if ((next_logp == nullptr) != (alpha == nullptr)) return fail(-1, "null pointer: next_logp and alpha go together (both null: no entropy backup)");
+  if (pair0 < 0 || pair0 >= E || pair1 < 0 || pair1 >= E || pair0 == pair1)
+    return fail(-1, "pair (%d, %d): two different members of [0, %d) are needed", pair0, pair1, E);
+  for (int e = 0; e < E; ++e)
+    if (!q_packed[e]) return fail(-1, "null pointer: kernel image of member %d", e);
+  if (!target_q_packed[pair0] || !target_q_packed[pair1]) return fail(-1, "null pointer: kernel image of a target member of the pair");
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
+#define CALL(P)                                                                                                                      \
+  rlpd_td_impl<P>(*q, E, q_params, q_packed, target_q_params, (const char*)target_q_packed[pair0], (const char*)target_q_packed[pair1], \
+                  pair0, pair1, *batch, obs_dim, next_actions, next_logp, alpha, N, gamma, q_grad, stats, workspace, workspace_bytes, \
+                  (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }

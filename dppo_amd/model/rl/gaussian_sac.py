@@ -25,12 +25,16 @@ from dppo_amd.util.replay import DeviceReplay
 class SAC_Gaussian(GaussianModel):
     _squash_built = True
 
-    def __init__(self, actor, critic, **kwargs):
+    @staticmethod
+    def _check_actor(actor):
         if getattr(actor, "is_vision", False):
             raise NotImplementedError("dppo_amd: SAC is built for state observations only (like the reference)")
         if getattr(actor, "use_fixed_std", True):
             raise NotImplementedError("dppo_amd: SAC needs the state-dependent std (Gaussian_MLP with fixed_std=None, "
                                       "tanh_output=False): every shipped SAC / RLPD / Cal-QL / IBRL cfg has it")
+
+    def __init__(self, actor, critic, **kwargs):
+        self._check_actor(actor)
         if not getattr(critic, "double_q", False):
             raise ValueError("SAC needs the twin critic (double_q=True): the reference's SAC_Gaussian unpacks two outputs")
         super().__init__(network=actor, **kwargs)

@@ -935,6 +935,25 @@ int dppo_sac_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, i
 int dppo_sac_alpha_loss(const float* logp, int64_t N, const double* log_alpha, double target_entropy, double* out,
                         dppo_stream_t stream);
 
+/* ---- RLPD: an ensemble of LayerNorm Q trunks (csrc/rlpd.h) ----------------------------------------------------------------------
+ * A plain kind-1 descriptor may set use_layernorm = 1 (hidden a multiple of 64, at most 1024): nn.LayerNorm(hidden), eps 1e-5,
+ * behind every Linear but the last and in front of the activation.  Flat order per hidden layer: linear_1.weight, linear_1.bias,
+ * norm_1.weight, norm_1.bias; the last layer is the Linear alone.  dppo_net_param_count, dppo_packed_bytes, dppo_pack_net(s),
+ * dppo_idql_q_forward with double_q = 0 (one member's Q) and the entry below read such a descriptor; every other entry refuses it.
+ *
+ * loss_critic (reference model/rl/gaussian_rlpd.py:64-103).  E members (2 <= E <= 16) share the descriptor: q_params and
+ * target_q_params are [E][P] flat fp32, q_packed / target_q_packed HOST arrays of E device pointers, one kernel image per member
+ * (of the targets only the pair's two are read).  (pair0, pair1): two different members, drawn by the caller.  With m = (float)gamma
+ * * (1 - terminated):  y = reward + m * min(tq_pair0, tq_pair1) [+ (m * (float)alpha) * (-next_logp)] in fp32;  next_logp (N,) and
+ * alpha (device double) are both given or both NULL (no entropy backup).  loss = mean over E N of (q_e - y)^2; q_grad <- d loss / d
+ * params of all members, [E][P] (OVERWRITTEN); stats[3] <- {loss, mean q over E N, mean y} (device doubles, fixed summation order). */
+int64_t dppo_rlpd_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E);
+int dppo_rlpd_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const float* q_params, const void* const* q_packed,
+                             const float* target_q_params, const void* const* target_q_packed, int pair0, int pair1,
+                             const dppo_idql_batch* batch, int obs_dim, const float* next_actions, const float* next_logp,
+                             const double* alpha, int64_t N, double gamma, float* q_grad, double* stats, void* workspace,
+                             int64_t workspace_bytes, dppo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

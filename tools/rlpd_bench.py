@@ -1,0 +1,139 @@
+"""Time RLPD's critic update (batch 256) at the shipped halfcheetah shape (E = 10, hidden [256, 256], Ta*Da = 6) and at the can shape
+(E = 5, hidden [256, 256, 256], Ta*Da = 7), bf16 and fp32:
+
+    python3 tools/rlpd_bench.py profiles/rlpd_update.json
+
+  critic  one critic update of RLPD_Gaussian out of plain tensors with the policy's sample at the next observations given:
+          loss_critic (dppo_rlpd_q_loss_fwd_bwd: two target members, all E members forward and backward), one FlatAdamW step over the
+          [E][P] image, one Polyak call;
+  eager   the same update as plain torch on the same GPU: the reference's arithmetic with torch.func.stack_module_state /
+          functional_call / vmap over the members, torch.optim.Adam over the stacked parameters, Polyak per parameter, fp32, and one
+          ``.item()`` per update as the reference agent takes;
+  E = 2   the critic arm again with two members, the fewest the call takes: how one update's time divides between the per-call part
+          and the per-member part, the evidence for or against a member-batched GEMM.
+The actor and temperature updates of a full RLPD iteration are not timed: the actor loss through the ensemble's mean is not built.
+Every arm is warmed, each pass times >= 0.5 s of work between two device events, the median of ten passes is reported
+(tools/idql_bench.timed).  First measurements of a new path: no threshold is set."""
+import copy
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+from torch import nn  # noqa: E402
+
+from tools.idql_bench import measured_on, timed  # noqa: E402
+
+DEV, N, GAMMA, ALPHA, TAU, LR = "cuda:0", 256, 0.99, 0.7, 0.005, 3e-4
+SHAPES = {"cheetah": dict(od=17, ta=1, da=6, dims=[256, 256], act="ReLU", E=10),
+          "can": dict(od=23, ta=1, da=7, dims=[256, 256, 256], act="ReLU", E=5)}
+
+
+def make_model(shape, prec, E):
+    from dppo_amd.model.common.critic import CriticObsAct
+    from dppo_amd.model.common.mlp_gaussian import Gaussian_MLP
+    from dppo_amd.model.rl.gaussian_rlpd import RLPD_Gaussian
+    s = SHAPES[shape]
+    actor = Gaussian_MLP(s["da"], s["ta"], s["od"], mlp_dims=s["dims"][:2], activation_type=s["act"], tanh_output=False, fixed_std=None,
+                         precision=prec)
+    critic = CriticObsAct(cond_dim=s["od"], mlp_dims=s["dims"], action_dim=s["da"], action_steps=s["ta"], activation_type=s["act"],
+                          use_layernorm=True, double_q=False, precision=prec)
+    return RLPD_Gaussian(actor=actor, critic=critic, n_critics=E, backup_entropy=True, horizon_steps=s["ta"], device=DEV,
+                         randn_clip_value=3.0, tanh_output=True)
+
+
+def batches(shape, count=16):
+    s = SHAPES[shape]
+    g = torch.Generator(device=DEV).manual_seed(0)
+    u = lambda *sz: torch.rand(*sz, device=DEV, generator=g) * 2 - 1
+    return [dict(obs=u(N, 1, s["od"]), next_obs=u(N, 1, s["od"]), actions=u(N, s["ta"], s["da"]), reward=u(N) + 1,
+                 terminated=(u(N) > 0.9).float(), next_actions=u(N, s["ta"], s["da"]), next_logp=u(N) - 1) for _ in range(count)]
+
+
+def hip_update(model, data):
+    from dppo_amd.util.optim import FlatAdamW
+    opt = FlatAdamW(model.critic_flat_params(), lr=LR, weight_decay=0.0)
+    alpha = torch.full((1,), ALPHA, dtype=torch.float64, device=DEV)
+    it = iter(range(10 ** 9))
+
+    def step():
+        b = data[next(it) % len(data)]
+        model.loss_critic({"state": b["obs"]}, {"state": b["next_obs"]}, b["actions"], b["reward"], b["terminated"], GAMMA, alpha,
+                          next_actions=b["next_actions"], next_logp=b["next_logp"])
+        opt.step(model.critic_flat_grads())
+        model.critics_updated()
+        model.update_target_critic(TAU)
+    return step
+
+
+class _Member(nn.Module):
+    def __init__(self, dims, act):
+        super().__init__()
+        layers = []
+        for i in range(len(dims) - 2):
+            layers += [nn.Linear(dims[i], dims[i + 1]), nn.LayerNorm(dims[i + 1]), getattr(nn, act)()]
+        self.net = nn.Sequential(*layers, nn.Linear(dims[-2], dims[-1]))
+
+    def forward(self, obs, act):
+        return self.net(torch.cat([obs.reshape(len(obs), -1), act.reshape(len(act), -1)], dim=-1)).squeeze(-1)
+
+
+def eager_update(shape, data):
+    s = SHAPES[shape]
+    dims = [s["od"] + s["ta"] * s["da"]] + s["dims"] + [1]
+    members = [_Member(dims, s["act"]).to(DEV) for _ in range(s["E"])]
+    targets = [copy.deepcopy(m) for m in members]
+    base = copy.deepcopy(members[0]).to("meta")
+    params, buffers = torch.func.stack_module_state(members)
+    params = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
+    opt = torch.optim.Adam(list(params.values()), lr=LR)
+    log_alpha = torch.tensor(0.0, device=DEV)
+    call = lambda p, bf, x: torch.func.functional_call(base, (p, bf), x)
+    it = iter(range(10 ** 9))
+
+    def step():
+        b = data[next(it) % len(data)]
+        alpha = log_alpha.exp().item()
+        i, j = torch.randperm(s["E"])[:2].tolist()
+        with torch.no_grad():
+            nq = torch.min(targets[i](b["next_obs"], b["next_actions"]), targets[j](b["next_obs"], b["next_actions"]))
+            y = b["reward"] + GAMMA * (1 - b["terminated"]) * nq
+            y = y + GAMMA * (1 - b["terminated"]) * alpha * (-b["next_logp"])
+        q = torch.vmap(call, in_dims=(0, 0, None))(params, buffers, (b["obs"], b["actions"]))
+        loss = torch.mean((q - y[None]) ** 2)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        with torch.no_grad():
+            for e, t in enumerate(targets):
+                for k, p in t.named_parameters():
+                    p.copy_(p * (1.0 - TAU) + params[k][e] * TAU)
+    return step
+
+
+def main(path):
+    out = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, measured_on=measured_on(), batch=N,
+               method="median of 10 passes of >= 0.5 s between device events, every arm warmed")
+    for shape, s in SHAPES.items():
+        data = batches(shape)
+        for prec in ("bf16", "fp32"):
+            for E in (s["E"], 2):
+                ms, reps = timed(hip_update(make_model(shape, prec, E), data))
+                out[f"{shape}/{prec}/E={E}"] = dict(ms_per_critic_update=ms, updates_per_pass=reps)
+                print(shape, prec, E, ms, flush=True)
+        eag, reps = timed(eager_update(shape, data))
+        out[f"{shape}/eager_torch_fp32/E={s['E']}"] = dict(ms_per_critic_update=eag, updates_per_pass=reps)
+        for prec in ("bf16", "fp32"):
+            out[f"{shape}/{prec}/E={s['E']}"]["eager_over_hip"] = eag / out[f"{shape}/{prec}/E={s['E']}"]["ms_per_critic_update"]
+        print(shape, "eager", eag, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])
