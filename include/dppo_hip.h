@@ -172,7 +172,13 @@ int dppo_critic_forward(const dppo_net_desc* net, int prec, const float* params,
  * run concurrently (different streams) must not share a workspace.  The first 32-bit word of an exchange block is 0, or
  * 1 + the largest denoising step at which a workgroup of ANY call since the host last cleared it gave up waiting for its
  * tile's other seven (bounded spin; the rows of `traj` and every chain slot that workgroup's tile owned are NaN then) --
- * never observed outside the test that forces it (knob 29). */
+ * never observed outside the test that forces it (knob 29).
+ * Refused by name, before the sampler kernel launches (an actor with a cond_mlp has run its encoder by then, which is a valid
+ * kernel at every accepted width and whose output nothing reads after the refusal): a hidden width the kernel is not
+ * instantiated for ("not instantiated": it is for 256, 512, 768 and 1024; check_net's other widths -- 128, 384, 640, 896, 1152 ... -- run every other entry on the layered GEMM chain and
+ * have no K-step sampler), and a network whose 16-row LDS image (input rows of round_up(in_dim) columns + two hidden images)
+ * exceeds the CU's 160 KiB ("LDS image exceeds 160 KiB": fp32 at hidden 1024 once in_dim passes about 500; bf16 fits up to in_dim
+ * 1024).  in_dim may exceed hidden: the input image is sized on its own (tests/test_mlp_specs.py, h256_in320). */
 int64_t dppo_sample_chain_workspace_bytes(const dppo_net_desc* actor, int prec, int64_t B);
 /* Bytes of the exchange block at the head of that workspace, 0 when the call will run one workgroup per tile: tells a caller
  * whether the workspace's first word is the time-out word described above (a host that already synchronises once per rollout
