@@ -1,0 +1,150 @@
+"""RLPD agent.
+
+Mirrors the reference's ``TrainRLPDAgent`` (agent/finetune/train_rlpd_agent.py:22-404): same cfg keys, same iteration structure
+(``n_steps`` env steps per iteration -- uniformly random actions for the first ``n_explore_steps`` iterations --, FIFO replay,
+evaluation by episode count every ``val_freq`` iterations FROM ``n_explore_steps`` on (``>=``, where SAC has ``>``); past the
+exploration phase ``critic_num_update`` critic updates per iteration, each on a fresh batch whose first half is drawn from the
+offline dataset and whose second half from the replay buffer (``np.random.choice`` with replacement, offline first) and each
+followed by the Polyak average, then ONE actor update and one temperature update on the LAST batch, with the temperature's last
+snapshot), same checkpoint format.  Both cosine schedules are stepped every iteration.
+
+The offline dataset and the replay buffer are device-resident; a batch is two gathers and one concatenation on the device.  Every
+loss, gradient, optimiser step and the Polyak average is a library call; the temperature's snapshot is a device scalar where the
+reference reads it back with ``.item()``: nothing in ``update_iteration`` reads the device.  ``log_alpha`` is a device float64 tensor
+stepped by ``torch.optim.Adam``.  The optimiser steps the flat [E][P] image of ``critic_networks`` (the reference steps stacked
+copies and leaves ``critic_networks`` at their initial values: model/rl/gaussian_rlpd.py).  State observations only.
+"""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+import torch
+
+from dppo_amd.agent.finetune.train_off_policy_agent import OffPolicyAgent
+from dppo_amd.agent.finetune.train_sac_agent import TrainSACAgent
+from dppo_amd.cfg.loader import instantiate
+from dppo_amd.util.optim import FlatAdamW
+
+
+class TrainRLPDAgent(OffPolicyAgent):
+    nets = ("network", "_ens", "_tens")  # the actor and both ensembles: load() refreshes every kernel image
+    log_line = "loss actor %8.4f | loss critic %8.4f | reward %8.4f | alpha %8.4f | t %8.4f"
+    log_keys = ("loss_actor", "loss_critic", "train_episode_reward", "alpha", "time")
+    _explore_action = TrainSACAgent._explore_action
+
+    def __init__(self, cfg, venv=None):
+        super().__init__(cfg, venv, "RLPD")
+        # ---- TrainRLPDAgent (:23-88), in its order
+        self.dataset_offline = instantiate(cfg.offline_dataset)
+        m = self.model
+        self.actor_optimizer = FlatAdamW(m.network.flat_params(), lr=cfg.train.actor_lr, weight_decay=cfg.train.actor_weight_decay)
+        self.actor_lr_scheduler = self._cosine(self.actor_optimizer, cfg.train.actor_lr_scheduler, cfg.train.actor_lr)
+        self.critic_optimizer = FlatAdamW(m.critic_flat_params(), lr=cfg.train.critic_lr, weight_decay=cfg.train.critic_weight_decay)
+        self.critic_lr_scheduler = self._cosine(self.critic_optimizer, cfg.train.critic_lr_scheduler, cfg.train.critic_lr)
+        self.target_ema_rate = cfg.train.target_ema_rate
+        self.critic_num_update = cfg.train.critic_num_update
+        self.n_eval_episode = cfg.train.n_eval_episode
+        self.n_explore_steps = cfg.train.n_explore_steps
+        self.log_alpha = torch.tensor(np.log(cfg.train.init_temperature), dtype=torch.float64, device=self.device,
+                                      requires_grad=True)
+        self.target_entropy = cfg.train.target_entropy
+        self.log_alpha_optimizer = torch.optim.Adam([self.log_alpha], lr=cfg.train.critic_lr)
+
+    # -------------------------------------------------------------------------------------------------
+    def draw_batch(self):
+        """One batch (:251-310): ``batch_size // 2`` offline transitions, then as many from the replay buffer, both drawn with
+        replacement from the global numpy generator in that order, gathered and concatenated on the device."""
+        half, dev = self.batch_size // 2, self.device
+        off_i = np.random.choice(len(self.dataset_offline), half)
+        on_i = np.random.choice(len(self.replay), half)
+        off = self.dataset_offline.gather(torch.from_numpy(off_i.astype(np.int64)).to(dev))
+        on = self.replay.gather(torch.from_numpy(on_i.astype(np.int64)).to(dev))
+        flat = lambda x: x.reshape(half, -1).float()
+        cat = lambda a, b: torch.cat([a, b], dim=0)
+        return dict(obs=cat(flat(off.conditions["state"]), flat(on[0])), next_obs=cat(flat(off.conditions["next_state"]), flat(on[1])),
+                    actions=cat(flat(off.actions), flat(on[2])), reward=cat(off.rewards.reshape(half).float(), on[3].reshape(half)),
+                    terminated=cat(off.dones.reshape(half).float(), on[4].reshape(half)))
+
+    def update_iteration(self, batches=None, pairs=None, next_actions=None, next_logp=None, sample_noise=None, actor_noise=None,
+                         temp_noise=None):
+        """One iteration's update in the reference's order (:246-347).  ``critic_num_update`` times: a batch (``batches[i]``, or
+        ``draw_batch()``), the temperature's snapshot, critic loss and step, Polyak.  Then ONE actor loss and step on the LAST
+        batch with the last snapshot, the temperature loss on a fresh sample at that batch and its step.  Nothing here reads the
+        device.  Returns (last critic loss, actor loss, temperature loss) as device scalars.  ``pairs[i]`` (the target pair),
+        ``next_actions[i]`` + ``next_logp[i]`` or ``sample_noise[i]`` (the critic loss's sample / its draws), ``actor_noise`` and
+        ``temp_noise`` replace the draws."""
+        m = self.model
+        pick = lambda x, i: None if x is None else x[i]
+        for i in range(self.critic_num_update):
+            b = batches[i] if batches is not None else self.draw_batch()
+            alpha = self.log_alpha.detach().exp()
+            loss_c = m.loss_critic({"state": b["obs"]}, {"state": b["next_obs"]}, b["actions"], b["reward"], b["terminated"], self.gamma,
+                                   alpha, next_actions=pick(next_actions, i), next_logp=pick(next_logp, i),
+                                   noise=pick(sample_noise, i), pair=pick(pairs, i)).detach()
+            self.critic_optimizer.step(m.critic_flat_grads())
+            m.critics_updated()
+            m.update_target_critic(self.target_ema_rate)
+        loss_a = m.loss_actor({"state": b["obs"]}, alpha, noise=actor_noise).detach()
+        self.actor_optimizer.step(m.last_loss_grad)
+        m.network.mark_updated()
+        self.log_alpha_optimizer.zero_grad()
+        lt = m.loss_temperature({"state": b["obs"]}, self.log_alpha, self.target_entropy, noise=temp_noise)
+        lt.backward()
+        self.log_alpha_optimizer.step()
+        return loss_c, loss_a, lt.detach()
+
+    def run(self):
+        model, dev = self.model, self.device
+        E = self.n_envs
+        t_start = time.time()
+        run_results = []
+        cnt_train_step = 0
+        done_venv = np.zeros(E, dtype=bool)
+        prev_obs = None
+        losses = None
+        while self.itr < self.n_train_itr:
+            eval_mode = self.itr % self.val_freq == 0 and self.itr >= self.n_explore_steps and not self.force_train
+            n_steps = self.n_steps if not eval_mode else int(1e5)  # an evaluation ends by its episode count
+            model.eval() if eval_mode else model.train()
+            firsts, rewards = [np.zeros(E)], []
+            if self.reset_at_iteration or eval_mode or self.itr == 0 or prev_obs is None:
+                prev_obs = self.reset_env_all()
+                firsts[0] = np.ones(E)
+            else:
+                firsts[0] = done_venv.astype(np.float64)
+            cnt_episode = 0
+            # ---------------- rollout (:154-207)
+            for step in range(n_steps):
+                state = torch.from_numpy(prev_obs["state"]).float().to(dev)
+                if self.itr < self.n_explore_steps:
+                    action = self._explore_action()
+                else:
+                    action = model(cond={"state": state}, deterministic=eval_mode).cpu().numpy()[:, :self.act_steps]
+                prev_obs, reward, done_venv = self.env_step(state, action, action, eval_mode)
+                rewards.append(np.asarray(reward, dtype=np.float64))
+                firsts.append(done_venv.astype(np.float64))
+                if not eval_mode:
+                    cnt_train_step += E * self.act_steps
+                cnt_episode += int(np.sum(done_venv))
+                if eval_mode and cnt_episode >= self.n_eval_episode:
+                    break
+            stats = self._episode_stats(np.stack(firsts), np.stack(rewards))
+            # ---------------- update (:246-347)
+            if not eval_mode and self.itr >= self.n_explore_steps:
+                losses = self.update_iteration()
+            # ---------------- schedules, checkpoint, logging (:349-404)
+            for name in self.lr_schedulers:
+                getattr(self, name).step()
+            if self.itr % self.save_model_freq == 0 or self.itr == self.n_train_itr - 1:
+                self.save_model()
+            rec = {"itr": self.itr, "step": cnt_train_step}
+            if self.itr % self.log_freq == 0 and self.itr > self.n_explore_steps:
+                fields = {}
+                if not eval_mode and losses is not None:  # the only device reads of the loop, on logging iterations
+                    fields.update(loss_actor=float(losses[1]), loss_critic=float(losses[0]), alpha=float(self.log_alpha.detach().exp()))
+                self.log_record(run_results, rec, t_start, eval_mode, stats, fields)
+            else:
+                run_results.append(rec)
+            self.itr += 1
+        return run_results

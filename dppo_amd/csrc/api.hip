@@ -3206,6 +3206,161 @@ int dppo_rlpd_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const floa
 #undef CALL
 }
 
+// The actor's loss through the ensemble's mean (rlpd.h).  The actor and its head are SAC's (checked further down).
+static int check_sac_actor(const dppo_net_desc* a);
+static int check_sac_cfg(const dppo_net_desc* a, const dppo_sac_cfg* cfg);
+static SacHead sac_head_of(const dppo_sac_cfg& cfg, const float* out, int ldo, int AF, const float* noise, int64_t N);
+static int check_rlpd_pair(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim, int E) {
+  if (int e = check_sac_actor(a)) return e;
+  if (int e = check_rlpd_q(q, obs_dim, E)) return e;
+  if (a->cond_dim != obs_dim || q->in_dim - obs_dim != a->out_dim / 2)
+    return fail(-1, "actor / Q descriptors do not pair: actor cond_dim=%d, Ta*Da=%d against obs_dim=%d, Q in_dim=%d", a->cond_dim,
+                a->out_dim / 2, obs_dim, q->in_dim);
+  return 0;
+}
+template <class P>
+struct RlpdActorWs {
+  MlpBufs<P> A, Q[RLPD_MAX_E];
+  void *dza[RLPD_MAX_E], *dzb[RLPD_MAX_E];  // member e's two alternating [N][H] chain buffers
+  void* dhcat;                              // [N][E H] elem: member e's dx_0 in columns [e H, (e + 1) H)
+  void* w0a;                                // [AF][E H] elem
+  float *actions, *logp, *sig;
+  float* dout32;  // bf16 only (SacTail::d_out32)
+};
+template <class P>
+static size_t carve_rlpd_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, int E, RlpdActorWs<P>& W) {
+  const size_t ES = P::ESIZE;
+  const int AF = a.out_dim / 2;
+  carve_mlp<P>(c, a, N, true, true, W.A);
+  for (int e = 0; e < E; ++e) {
+    carve_mlp<P>(c, q, N, true, false, W.Q[e]);
+    W.dza[e] = c.take((size_t)N * q.hidden * ES);
+    W.dzb[e] = c.take((size_t)N * q.hidden * ES);
+  }
+  W.dhcat = c.take((size_t)N * E * q.hidden * ES);
+  W.w0a = c.take((size_t)AF * E * q.hidden * ES);
+  W.actions = (float*)c.take((size_t)N * AF * 4);
+  W.logp = (float*)c.take((size_t)N * 4);
+  W.sig = (float*)c.take((size_t)N * 4);
+  W.dout32 = ES == 4 ? nullptr : (float*)c.take((size_t)N * 2 * AF * 4);
+  return al256(c.off);
+}
+int64_t dppo_rlpd_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
+  if (check_rlpd_pair(actor, q, obs_dim, E) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    RlpdActorWs<decltype(p)> W;
+    return carve_rlpd_actor<decltype(p)>(c, *actor, *q, N, E, W);
+  });
+}
+// d q / d (layer 0's Linear output) of one LayerNorm member, into its columns of dhcat (row stride ldh): the seed, then per hidden
+// layer from the top the LayerNorm backward without parameter sums and, except at layer 0, the data GEMM with the act' epilogue
+template <class P>
+static void rlpd_member_chain(const dppo_net_desc& q, const float* prm, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B,
+                              void* dza, void* dzb, void* dh0, int ldh, hipStream_t s) {
+  const ParamLayout pl = param_layout(q);
+  const int H = q.hidden, nb = q.n_blocks;
+  launch_qsm_seed<P>(pk + L.Wout, B.z1[nb - 1], N, H, q.act, dza, s);
+  LnBwd ln;
+  memset(&ln, 0, sizeof(ln));
+  ln.ld = H, ln.ldx = H, ln.M = N, ln.H = H;  // (partial stays null: a data-gradient chain)
+  void* dz = dza;
+  void* other = dzb;
+  for (int b = nb - 1; b >= 0; --b) {
+    ln.dz = dz, ln.x = B.h[b + 1], ln.stats = B.ln_stats + (size_t)(b + 1) * N * 2, ln.gamma = prm + pl.n1w[b];
+    launch_ln_bwd<P>(ln, s);
+    GemmNT g;
+    memset(&g, 0, sizeof(g));
+    g.M = (int)N, g.N = H, g.Kp = H, g.ldx = H, g.ldw = H;
+    g.X = dz, g.W = pk + L.W1T[b], g.dsrc = b == 0 ? B.hpre[0] : B.z1[b - 1], g.dsrc_kind = 2, g.dsrc_ld = H, g.dact = q.act;
+    g.out_pre = b == 0 ? dh0 : other, g.ldo = b == 0 ? ldh : H;
+    launch_gemm_nt<P>(g, s);
+    void* t = dz;
+    dz = other, other = t;
+  }
+  ln.dz = dh0, ln.ld = ldh, ln.x = B.h[0], ln.stats = B.ln_stats, ln.gamma = prm + pl.n0w;
+  launch_ln_bwd<P>(ln, s);
+}
+template <class P>
+static int rlpd_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, int E, const float* ap, const char* ak, const float* qp,
+                           const void* const* qk, const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N,
+                           const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
+                           float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  RlpdActorWs<P> W;
+  const size_t need = carve_rlpd_actor<P>(c, a, q, N, E, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const int64_t q_stride = W.Q[1].out - W.Q[0].out;
+  for (int e = 1; e < E; ++e)
+    if (W.Q[e].out - W.Q[0].out != e * q_stride) return fail(-1, "members' workspaces are not evenly spaced");
+  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const ParamLayout plq = param_layout(q);
+  const int AF = a.out_dim / 2, H = q.hidden;
+  float* actions = actions_out != nullptr ? actions_out : W.actions;
+  float* logp = logp_out != nullptr ? logp_out : W.logp;
+  // the actor's rows [obs | 0], its forward with the activations kept, the head: sample, log-probability and ONE image of the
+  // critic's rows [obs | a | 0] that every member reads
+  IdqlRows r = idql_rows_of(b, N, OD, AF);
+  r.vin = W.A.in, r.KpV = LA.Kp0;
+  launch_idql_rows<P>(r, s);
+  launch_rlpd_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, H, E, W.w0a, s);
+  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
+  SacHead h = sac_head_of(cfg, W.A.out, W.A.ldout, AF, noise, N);
+  h.ring = idql_rows_of(b, N, OD, AF);
+  h.actions = actions, h.logp = logp, h.sig_row = W.sig, h.q1in = h.q2in = W.Q[0].in, h.KpQ = LQ.Kp0;
+  launch_sac_head<P>(h, s);
+  for (int e = 1; e < E; ++e) W.Q[e].in = W.Q[0].in;
+  // the members take turns on the caller's stream and the three side streams: each runs its forward and its chain back to back
+  hipStream_t st[4] = {s, fork_side(s, 0), fork_side(s, 1), fork_side(s, 2)};
+  for (int e = 0; e < E; ++e) {
+    const float* prm = qp + e * plq.total;
+    mlp_forward<P>(q, prm, (const char*)qk[e], LQ, N, W.Q[e], true, st[e & 3]);
+    rlpd_member_chain<P>(q, prm, (const char*)qk[e], LQ, N, W.Q[e], W.dza[e], W.dzb[e], (char*)W.dhcat + (size_t)e * H * P::ESIZE,
+                         E * H, st[e & 3]);
+  }
+  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
+  RlpdTail tl;
+  memset(&tl, 0, sizeof(tl));
+  tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.K = E * H, tl.E = E, tl.alpha = alpha;
+  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
+  launch_rlpd_tail<P>(tl, s);
+  RlpdActorStats sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.q = W.Q[0].out, sa.q_stride = q_stride, sa.ldq = W.Q[0].ldout, sa.E = E, sa.logp = logp, sa.sig_row = W.sig, sa.alpha = alpha;
+  sa.N = N, sa.AF = AF, sa.stats = stats;
+  launch_rlpd_actor_stats(sa, s);
+  mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s);
+  if (W.dout32 != nullptr)  // the two heads' bias gradient again, from the unrounded rows
+    launch_colsum<F32>(W.dout32, (int)N, 2 * AF, 2 * AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
+  return check_launch();
+}
+int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int E, const float* actor_params,
+                            const void* actor_packed, const float* q_params, const void* const* q_packed, const dppo_sac_cfg* cfg,
+                            const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise, const double* alpha,
+                            float* actor_grad, double* stats, float* d_a, float* logp_out, float* actions_out, void* workspace,
+                            int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_rlpd_pair(actor, q, obs_dim, E)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (int e = check_sac_cfg(actor, cfg)) return e;
+  if (cfg->deterministic) return fail(-1, "the actor loss samples: deterministic must be 0");
+  if (!actor_params || !actor_packed || !q_params || !q_packed || !alpha || !actor_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  for (int e = 0; e < E; ++e)
+    if (!q_packed[e]) return fail(-1, "null pointer: kernel image of member %d", e);
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (!batch) return fail(-1, "null batch");
+  if (!batch->obs) return fail(-1, "null pointer in batch");
+  if (batch->cap < 1 || batch->n_envs < 1 || batch->count < 1 || batch->count > batch->cap || batch->head < 0 || batch->head >= batch->cap)
+    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
+  if (!batch->inds && N > batch->count * batch->n_envs)
+    return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N, (long long)(batch->count * batch->n_envs));
+#define CALL(P)                                                                                                                    \
+  rlpd_actor_impl<P>(*actor, *q, E, actor_params, (const char*)actor_packed, q_params, q_packed, *cfg, *batch, obs_dim, N, noise,   \
+                     alpha, actor_grad, stats, d_a, logp_out, actions_out, workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
 // ---- DQL (dql.hip): the actor loss whose gradient flows through the K-step sampling chain ----------------------------------------
 static int check_dql(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim) {
   if (int e = check_net(a)) return e;

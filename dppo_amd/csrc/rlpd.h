@@ -22,11 +22,26 @@
 //        + E backwards x [1 data GEMM + L x (2 LayerNorm backward + weight gradient + its slab reduce + 2 column sum) + (L - 1)
 //          data GEMMs + out layer's weight gradient, slab reduce and 2 column sum].
 // The members' GEMMs go through launch_gemm_nt / weight_grad once per member, spread over the side streams.
-// Not built: the actor's call through the ensemble's mean, a member-batched GEMM, weight gradients grouped across members.
+//
+// The actor's loss through the ensemble's mean (reference model/rl/gaussian_rlpd.py:100-112): with a_n, logp_n SAC's reparameterised
+// sample at obs_n,  loss = mean_n [-(1/E) sum_e q_e(obs_n, a_n) + alpha logp_n],  g_n = (1/E) sum_e dq_e/da.  The head writes ONE row
+// image [obs | a | 0]; every member runs its forward (z, mean, rstd kept) and its own data-gradient chain: the seed Wout (.) act'(z_L),
+// then per hidden layer from the top ln_bwd_kernel with no parameter sums and, except at layer 0, the data GEMM with the act' epilogue.
+// Member e's dx_0 lands in columns [e H, (e + 1) H) of one [N][E H] image; rlpd_tail_kernel multiplies it with the members' action
+// columns of W0, packed as [AF][E H], folds the 1/E in once and runs SAC's head backward with g in place of dQ_sel/da.
+//
+// Launches of dppo_rlpd_actor_fwd_bwd with L hidden layers per member (read off the code, not traced), side-stream events aside:
+//   1 row builder + 1 W0 pack + the actor's forward (3 GEMMs on the shipped two-layer actor) + 1 head epilogue
+//   + E x [L x (1 GEMM + 1 row kernel) + 1 GEMM]                  the members' forwards
+//   + E x [1 seed + L LayerNorm backwards + (L - 1) data GEMMs]   the members' chains
+//   + 1 tail / head backward + 1 statistics (bf16: + 2 for the heads' bias gradient from the unrounded d_out)
+//   + the actor's parameter backward.  Nothing of a critic's is written: no weight gradient, column sum or gradient buffer.
+//   Shipped halfcheetah (E = 10, L = 2): 4 + 3 + 10 x 5 + 10 x 4 + 2 = 99 before the actor's backward.
+// Not built: a member-batched GEMM, weight gradients grouped across members, Cal-QL's conservative term, IBRL.
 //
 // Launches of one forward of a trunk: L x (1 GEMM + 1 row kernel) + 1 GEMM.
 #pragma once
-#include "common.h"
+#include "sac.h"
 
 namespace dppo {
 
@@ -92,5 +107,45 @@ void launch_rlpd_loss(const RlpdLoss& a, hipStream_t s);
 // gradient rows.  The column sum of the elem rows costs that gradient 2^-9 per row in bf16 (at N = 1 all of it), more than
 // rounding every Linear's operands does; run behind the members' backwards, whose column sum it overwrites.
 void launch_rlpd_out_bias(const double* partial, int64_t N, int E, float* grad, int64_t stride, int64_t bout, hipStream_t s);
+
+// ---- the actor's loss through the ensemble's mean ---------------------------------------------------------------------------------
+// wa[a][e * H + h] = elem(W0 of member e [h][OD + a]) (member e's flat image starts at params + e * stride): [AF][E H]
+template <class P>
+void launch_rlpd_pack_w0a(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AF, int H, int E, void* wa,
+                          hipStream_t s);
+
+// The chains' tail and the head's backward in one launch.  K = E H is split over RLPD_TAIL_LANES lanes per output (n, j): lane l
+// takes the 4-element groups l, l + 16, ... of the row (so the members in index order), one fma per element, and the 16 partials
+// are added by a fixed xor butterfly.  Operands come straight from global memory: no LDS tile, so no ceiling on K.  An output
+// depends on its own row of dh alone and on nothing of the launch geometry: the same bits in every call, batch size and block.
+//   g[n][j] = (sum_k dh[n][k] wa[j][k]) / E,  then sac.h's dL/du, dL/dsigma, dL/draw with g in place of dQ_sel/da.
+constexpr int RLPD_TAIL_LANES = 16;
+struct RlpdTail {
+  SacHead head;    // cfg, out, noise, AF (its outputs are unused)
+  const void* dh;  // [N][K] elem, K = E H
+  const void* wa;  // [AF][K] elem
+  int K, E;
+  const double* alpha;  // device scalar
+  void* d_out;          // [N][ldd] elem: columns [0, 2 AF) set, the rest zeroed
+  int ldd;
+  float* d_out32;  // [N][2 AF] fp32 or null: the same before its rounding to elem (SacTail::d_out32)
+  float* d_a;      // [N][AF] = -g / N, or null
+};
+template <class P>
+void launch_rlpd_tail(const RlpdTail& a, hipStream_t s);
+
+// stats = {mean(-qm + alpha logp), mean qm, mean logp, mean sigma}, qm[n] = (q_0[n] + q_1[n] + ... in member order) / E in fp32;
+// thread i sums rows i, i + 256, ... in double, the 256 partials are added pairwise in a fixed tree (as sac_stats_kernel)
+struct RlpdActorStats {
+  const float* q;    // member e's Q: column 0 of [N][ldq] at q + e * q_stride
+  int64_t q_stride;  // floats
+  int ldq, E;
+  const float *logp, *sig_row;
+  const double* alpha;
+  int64_t N;
+  int AF;
+  double* stats;
+};
+void launch_rlpd_actor_stats(const RlpdActorStats& a, hipStream_t s);
 
 }  // namespace dppo

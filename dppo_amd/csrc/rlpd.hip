@@ -259,4 +259,114 @@ void launch_rlpd_loss(const RlpdLoss& a, hipStream_t s) {
 template void launch_rlpd_loss<F32>(const RlpdLoss&, hipStream_t);
 template void launch_rlpd_loss<BF16>(const RlpdLoss&, hipStream_t);
 
+// ---- the actor's loss through the ensemble's mean (gaussian_rlpd.py:100-112) ------------------------------------------------------
+template <class P>
+__global__ __launch_bounds__(256) void rlpd_pack_w0a_kernel(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD,
+                                                             int AF, int H, int E, typename P::elem_t* wa) {
+  const int K = E * H, total = AF * K;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int a = i / K, k = i - a * K;
+    const int e = k / H, h = k - e * H;
+    wa[i] = P::from_f32(params[e * stride + w0_off + (int64_t)h * in_dim + OD + a]);
+  }
+}
+template <class P>
+void launch_rlpd_pack_w0a(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AF, int H, int E, void* wa,
+                          hipStream_t s) {
+  const int blocks = (AF * E * H + 255) / 256;
+  hipLaunchKernelGGL((rlpd_pack_w0a_kernel<P>), dim3(blocks > 2048 ? 2048 : blocks), dim3(256), 0, s, params, stride, w0_off, in_dim,
+                     OD, AF, H, E, (typename P::elem_t*)wa);
+}
+template void launch_rlpd_pack_w0a<F32>(const float*, int64_t, int64_t, int, int, int, int, int, void*, hipStream_t);
+template void launch_rlpd_pack_w0a<BF16>(const float*, int64_t, int64_t, int, int, int, int, int, void*, hipStream_t);
+
+// 16 outputs per block, 16 lanes per output; every lane of a wave runs the product (an output past the end redoes the last one and
+// writes nothing), so the butterfly never meets an idle lane.  Lane 0 of an output then runs the head's backward.
+template <class P>
+__global__ __launch_bounds__(256) void rlpd_tail_kernel(const RlpdTail a) {
+  typedef typename P::elem_t E;
+  const SacHead& hd = a.head;
+  const int AF = hd.AF, sub = threadIdx.x & (RLPD_TAIL_LANES - 1);
+  const int64_t N = hd.ring.N, total = N * AF;
+  const int64_t o = (int64_t)blockIdx.x * (256 / RLPD_TAIL_LANES) + (threadIdx.x / RLPD_TAIL_LANES);
+  const bool live = o < total;
+  const int64_t oo = live ? o : total - 1;
+  const int64_t n = oo / AF;
+  const int j = (int)(oo - n * AF);
+  const E* x = (const E*)a.dh + n * a.K;
+  const E* w = (const E*)a.wa + (int64_t)j * a.K;
+  float acc = 0.f;
+  for (int k = 4 * sub; k < a.K; k += 4 * RLPD_TAIL_LANES) {
+    float xv[4], wv[4];
+    load4<P>(x + k, xv);
+    load4<P>(w + k, wv);
+    acc = __builtin_fmaf(xv[0], wv[0], acc);
+    acc = __builtin_fmaf(xv[1], wv[1], acc);
+    acc = __builtin_fmaf(xv[2], wv[2], acc);
+    acc = __builtin_fmaf(xv[3], wv[3], acc);
+  }
+#pragma unroll
+  for (int m = 1; m < RLPD_TAIL_LANES; m <<= 1) acc += __shfl_xor(acc, m);
+  if (!live) return;
+  if (j == 0) {  // the K padding of the backward's first GEMM
+    const int pad = a.ldd - 2 * AF;
+    for (int c = sub; c < pad; c += RLPD_TAIL_LANES) ((E*)a.d_out)[n * a.ldd + 2 * AF + c] = P::from_f32(0.f);
+  }
+  if (sub != 0) return;
+  const float g = acc / (float)a.E;  // the members' mean: 1/E once, behind the whole sum
+  const float alpha = (float)*a.alpha, fN = (float)N;
+  const SacElem e = sac_elem(hd, n, j);
+  float du = -(g * e.s);
+  if (hd.cfg.squash) {
+    const float t0 = (alpha * 2.f) * (e.a * e.s);
+    du = du + t0 / (e.s + 1e-6f);
+  }
+  du = du / fN;
+  const float t1 = du * e.zc;
+  const float dsig = t1 - alpha / (fN * e.sigma);
+  const float t2 = dsig * (0.5f * e.sigma);
+  const float draw = t2 * (hd.half_span * sac_sech2(e.raw));
+  ((E*)a.d_out)[n * a.ldd + j] = P::from_f32(du);
+  ((E*)a.d_out)[n * a.ldd + AF + j] = P::from_f32(draw);
+  if (a.d_out32 != nullptr) a.d_out32[n * 2 * AF + j] = du, a.d_out32[n * 2 * AF + AF + j] = draw;
+  if (a.d_a != nullptr) a.d_a[n * AF + j] = -g / fN;
+}
+template <class P>
+void launch_rlpd_tail(const RlpdTail& a, hipStream_t s) {
+  const int64_t total = a.head.ring.N * a.head.AF;
+  if (total < 1) return;
+  constexpr int OPB = 256 / RLPD_TAIL_LANES;
+  hipLaunchKernelGGL((rlpd_tail_kernel<P>), dim3((unsigned)((total + OPB - 1) / OPB)), dim3(256), 0, s, a);
+}
+template void launch_rlpd_tail<F32>(const RlpdTail&, hipStream_t);
+template void launch_rlpd_tail<BF16>(const RlpdTail&, hipStream_t);
+
+__global__ __launch_bounds__(256) void rlpd_actor_stats_kernel(const RlpdActorStats a) {
+  __shared__ double sh[4][256];
+  const float alpha = (float)*a.alpha;
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t n = threadIdx.x; n < a.N; n += 256) {
+    float q = 0.f;
+    for (int e = 0; e < a.E; ++e) q += a.q[e * a.q_stride + n * a.ldq];
+    q = q / (float)a.E;
+    const float lp = a.logp[n];
+    const float t = alpha * lp;
+    v[0] += (double)(-q + t), v[1] += q, v[2] += lp, v[3] += a.sig_row[n];
+  }
+  for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w)
+      for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double dn = (double)a.N;
+    a.stats[0] = sh[0][0] / dn, a.stats[1] = sh[1][0] / dn, a.stats[2] = sh[2][0] / dn, a.stats[3] = sh[3][0] / (dn * a.AF);
+  }
+}
+void launch_rlpd_actor_stats(const RlpdActorStats& a, hipStream_t s) {
+  hipLaunchKernelGGL(rlpd_actor_stats_kernel, dim3(1), dim3(256), 0, s, a);
+}
+
 }  // namespace dppo

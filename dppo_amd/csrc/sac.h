@@ -39,6 +39,43 @@ struct SacHead {
 template <class P>
 void launch_sac_head(const SacHead& a, hipStream_t s);
 
+// (shared by sac.hip and rlpd.hip: RLPD's actor head is this one)
+#define SAC_LOG_SQRT_2PI 0.91893853320467274178f
+
+// ---- the head, element by element -------------------------------------------------------------------------------------------
+// 1 - tanh(x)^2 without the cancellation
+__device__ __forceinline__ float sac_sech2(float x) {
+  const float e = expf(-2.f * fabsf(x));
+  const float d = 1.f + e;
+  return (4.f * e) / (d * d);
+}
+struct SacElem {
+  float zc, lv, sigma, u, a, s, raw;
+};
+__device__ __forceinline__ SacElem sac_elem(const SacHead& a, int64_t n, int j) {
+  const dppo_sac_cfg& c = a.cfg;
+  SacElem e;
+  const float mu = a.out[n * a.ldo + j];
+  e.raw = a.out[n * a.ldo + a.AF + j];
+  const int64_t i = n * a.AF + j;
+  const float z = a.noise != nullptr ? a.noise[i] : philox_normal((uint64_t)i, c.seed_lo, c.seed_hi);
+  e.zc = fminf(fmaxf(z, -c.randn_clip), c.randn_clip);
+  const float t1 = tanhf(e.raw) + 1.f;
+  const float t2 = a.half_span * t1;
+  e.lv = c.logvar_min + t2;
+  e.sigma = c.deterministic ? 1e-4f : expf(0.5f * e.lv);
+  const float p = e.sigma * e.zc;
+  e.u = mu + p;
+  if (c.squash) {
+    e.a = tanhf(e.u);
+    e.s = sac_sech2(e.u);
+  } else {
+    e.a = e.u;
+    e.s = 1.f;
+  }
+  return e;
+}
+
 // sel[n] = q2 < q1 (ties go to q1, like the first argument of torch.min);  qsel[n] = the smaller;  and the seed of both trunks'
 // data-gradient chains: dz_i[n][h] = elem(wout_i[h] * act'(z_i[n][h])) for the selected trunk i of row n, 0 for the other
 struct SacSelect {

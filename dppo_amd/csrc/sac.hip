@@ -4,8 +4,6 @@
 
 namespace dppo {
 
-#define SAC_LOG_SQRT_2PI 0.91893853320467274178f
-
 template <class P>
 union SacChunk {
   typename P::elem_t e[16 / P::ESIZE];
@@ -14,40 +12,6 @@ union SacChunk {
 static unsigned sac_grid(int64_t items) {
   const int64_t blocks = (items + 255) / 256;
   return (unsigned)(blocks > 2048 ? 2048 : (blocks < 1 ? 1 : blocks));
-}
-
-// ---- the head, element by element -------------------------------------------------------------------------------------------
-// 1 - tanh(x)^2 without the cancellation
-__device__ __forceinline__ float sac_sech2(float x) {
-  const float e = expf(-2.f * fabsf(x));
-  const float d = 1.f + e;
-  return (4.f * e) / (d * d);
-}
-struct SacElem {
-  float zc, lv, sigma, u, a, s, raw;
-};
-__device__ __forceinline__ SacElem sac_elem(const SacHead& a, int64_t n, int j) {
-  const dppo_sac_cfg& c = a.cfg;
-  SacElem e;
-  const float mu = a.out[n * a.ldo + j];
-  e.raw = a.out[n * a.ldo + a.AF + j];
-  const int64_t i = n * a.AF + j;
-  const float z = a.noise != nullptr ? a.noise[i] : philox_normal((uint64_t)i, c.seed_lo, c.seed_hi);
-  e.zc = fminf(fmaxf(z, -c.randn_clip), c.randn_clip);
-  const float t1 = tanhf(e.raw) + 1.f;
-  const float t2 = a.half_span * t1;
-  e.lv = c.logvar_min + t2;
-  e.sigma = c.deterministic ? 1e-4f : expf(0.5f * e.lv);
-  const float p = e.sigma * e.zc;
-  e.u = mu + p;
-  if (c.squash) {
-    e.a = tanhf(e.u);
-    e.s = sac_sech2(e.u);
-  } else {
-    e.a = e.u;
-    e.s = 1.f;
-  }
-  return e;
 }
 
 // 16 lanes per row: lane `sub` owns elements sub, sub + 16, ...; the row's log-probability is its lanes' partial sums added by

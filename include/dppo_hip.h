@@ -959,6 +959,21 @@ int dppo_rlpd_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const floa
                              const dppo_idql_batch* batch, int obs_dim, const float* next_actions, const float* next_logp,
                              const double* alpha, int64_t N, double gamma, float* q_grad, double* stats, void* workspace,
                              int64_t workspace_bytes, dppo_stream_t stream);
+/* loss_actor (reference model/rl/gaussian_rlpd.py:100-112) = mean_n [-(1/E) sum_e q_e(obs_n, a_n) + (float)alpha * logp_n] on SAC's
+ * reparameterised sample (dppo_sac_actor_fwd_bwd's actor, head, cfg, noise and batch arguments; deterministic must be 0).  One call:
+ * the actor's forward, the head (ONE image of the critic's rows, read by all members), E LayerNorm forwards, E data-gradient chains
+ * through LayerNorm, one launch for the K = E*hidden product with the members' action columns of W0 whose epilogue is SAC's head
+ * backward with g = (1/E) sum_e dq_e/da in place of dQ_sel/da, then the actor's backward.  actor_grad <- d loss / d actor params
+ * (flat, OVERWRITTEN); stats[4] <- {loss, mean over n of the members' mean q, mean logp, mean sigma} (device doubles, fixed
+ * summation order).  Optional (NULL): d_a (N, AF) = -g / N, logp_out (N,), actions_out (N, AF).  A row's outputs depend on that row
+ * alone and are the same bits in every call.  No weight gradient, column sum or gradient buffer of any member is written.  The
+ * actor as dppo_sac_actor_fwd_bwd's; q and E as dppo_rlpd_q_loss_fwd_bwd's (every hidden up to 1024 and every E up to 16 runs). */
+int64_t dppo_rlpd_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E);
+int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int E, const float* actor_params,
+                            const void* actor_packed, const float* q_params, const void* const* q_packed, const dppo_sac_cfg* cfg,
+                            const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise, const double* alpha,
+                            float* actor_grad, double* stats, float* d_a, float* logp_out, float* actions_out, void* workspace,
+                            int64_t workspace_bytes, dppo_stream_t stream);
 
 #ifdef __cplusplus
 }
