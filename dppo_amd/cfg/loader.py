@@ -150,11 +150,21 @@ def get_class(target: str):
 
 
 def instantiate(node: Any, **extra):
-    """Recursive ``_target_`` instantiation (hydra.utils.instantiate, reference train_agent.py:84)."""
+    """Recursive ``_target_`` instantiation (hydra.utils.instantiate, reference train_agent.py:84).  A target class may declare
+    defaults for its children's nodes in a class attribute ``child_node_defaults = {child: {key: value}}``: they are merged into a
+    child that is itself a ``_target_`` node and lacks the key, before it is built (``CalQL_Gaussian`` asks its critic for the
+    LayerNorm twin this way, so that a shipped cfg builds with its text unchanged).  A class that declares nothing behaves as before."""
     if isinstance(node, dict) and "_target_" in node:
-        kwargs = {k: instantiate(v) for k, v in node.items() if k != "_target_"}
+        cls = get_class(node["_target_"])
+        defaults = getattr(cls, "child_node_defaults", None) or {}
+
+        def child(k, v):
+            if k in defaults and isinstance(v, dict) and "_target_" in v:
+                v = dict(v, **{dk: dv for dk, dv in defaults[k].items() if dk not in v})
+            return instantiate(v)
+        kwargs = {k: child(k, v) for k, v in node.items() if k != "_target_"}
         kwargs.update(extra)
-        return get_class(node["_target_"])(**kwargs)
+        return cls(**kwargs)
     if isinstance(node, dict):
         return Cfg({k: instantiate(v) for k, v in node.items()})
     if isinstance(node, list):

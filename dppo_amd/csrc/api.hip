@@ -15,6 +15,7 @@
 #include "dql.h"
 #include "sac.h"
 #include "rlpd.h"
+#include "calql.h"
 #include "unet.h"
 #include "sampler.h"
 
@@ -187,7 +188,7 @@ static int check_net(const dppo_net_desc* d, bool ln_plain = false) {
     if (d->cond_hidden || d->cond_out) return fail(-1, "plain MLP: cond_mlp is not built");
     if (d->use_layernorm == 1 && d->kind == 0) return fail(-1, "plain MLP: LayerNorm is built for kind-1 (critic) trunks only");
     if (d->use_layernorm == 1 && !ln_plain)
-      return fail(-1, "plain MLP with LayerNorm: this entry is not taught it; dppo_idql_q_forward with double_q = 0 and dppo_rlpd_q_loss_fwd_bwd read such a trunk");
+      return fail(-1, "plain MLP with LayerNorm: this entry is not taught it; dppo_idql_q_forward with double_q = 0, dppo_rlpd_q_loss_fwd_bwd and dppo_calql_q_loss_fwd_bwd read such a trunk");
     if (d->use_layernorm == 1 && d->hidden > LN_MAX_H) return fail(-1, "plain MLP with LayerNorm: hidden=%d above %d", d->hidden, LN_MAX_H);
   } else if (d->hidden < 128 || d->hidden % 128) return fail(-1, "hidden=%d must be a positive multiple of 128", d->hidden);
   if (d->n_blocks < 0 || d->n_blocks > MAX_BLOCKS) return fail(-1, "n_blocks=%d out of [0,%d]", d->n_blocks, MAX_BLOCKS);
@@ -3357,6 +3358,120 @@ int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, 
 #define CALL(P)                                                                                                                    \
   rlpd_actor_impl<P>(*actor, *q, E, actor_params, (const char*)actor_packed, q_params, q_packed, *cfg, *batch, obs_dim, N, noise,   \
                      alpha, actor_grad, stats, d_a, logp_out, actions_out, workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+// ---- Cal-QL (calql.hip): the conservative critic loss on a twin of LayerNorm Q trunks --------------------------------------------
+static int check_calql_q(const dppo_net_desc* q, int obs_dim, int64_t N, int R, int S) {
+  if (int e = check_idql_q(q, true)) return e;
+  if (!q->plain || !q->use_layernorm)
+    return fail(-1, "Cal-QL's twin is two plain trunks with LayerNorm (plain = 1, use_layernorm = 1); a twin without LayerNorm trains through dppo_sac_q_loss_fwd_bwd");
+  if (obs_dim < 1 || obs_dim >= q->in_dim)
+    return fail(-1, "Q descriptor does not pair with obs_dim=%d: in_dim=%d must be obs_dim + the action width", obs_dim, q->in_dim);
+  if (R < 1 || R > CALQL_MAX_SAMPLES) return fail(-1, "n_random=%d random actions per row out of [1, %d]", R, CALQL_MAX_SAMPLES);
+  if (S < 1 || S > CALQL_MAX_SAMPLES) return fail(-1, "n_next=%d policy samples per next observation out of [1, %d]", S, CALQL_MAX_SAMPLES);
+  if (N < 1 || N * (R + 3) > 0x7fffffff || N * S > 0x7fffffff) return fail(-1, "N out of range");
+  return 0;
+}
+template <class P>
+struct CalqlWs {
+  MlpBufs<P> Q[2], T[2];
+  double *partial, *partial_d;
+  float *r, *term, *y, *lse;
+};
+template <class P>
+static size_t carve_calql(Carver& c, const dppo_net_desc& q, int64_t N, int R, int S, CalqlWs<P>& W) {
+  W.partial = (double*)c.take((size_t)2 * rlpd_blocks(N) * 4 * sizeof(double));
+  W.partial_d = (double*)c.take((size_t)2 * rlpd_blocks(N) * sizeof(double));
+  W.r = (float*)c.take((size_t)N * 4);
+  W.term = (float*)c.take((size_t)N * 4);
+  W.y = (float*)c.take((size_t)N * 4);
+  W.lse = (float*)c.take(2 * 4);
+  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, q, N * (R + 3), true, true, W.Q[i]);
+  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, q, N * S, false, false, W.T[i]);
+  return al256(c.off);
+}
+int64_t dppo_calql_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int n_random, int n_next) {
+  if (check_calql_q(q, obs_dim, N, n_random, n_next) || check_prec(prec)) return -1;
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    CalqlWs<decltype(p)> W;
+    return carve_calql<decltype(p)>(c, *q, N, n_random, n_next, W);
+  });
+}
+template <class P>
+static int calql_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const float* tp, const char* tk1,
+                      const char* tk2, const dppo_calql_cfg& cfg, const dppo_idql_batch& b, int OD, const float* returns,
+                      const float* next_actions, const float* pi_actions, const float* log_pi, const float* pi_next_actions,
+                      const float* log_pi_next, const float* random_actions, int64_t N, double gamma, float* qgrad, double* stats,
+                      float* y_out, float* random_out, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  CalqlWs<P> W;
+  const int R = cfg.n_random, S = cfg.n_next;
+  const int64_t M = N * (R + 3), MT = N * S;
+  const size_t need = carve_calql<P>(c, q, N, R, S, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout L = pack_layout<P>(q, 0);
+  const int64_t nq = param_layout(q).total;
+  // both trunks read the same M rows, both targets the same N S rows: one image each
+  CalqlRows r;
+  memset(&r, 0, sizeof(r));
+  r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
+  r.random_actions = random_actions, r.pi_actions = pi_actions, r.pi_next_actions = pi_next_actions, r.next_actions = next_actions;
+  r.R = R, r.S = S, r.seed_lo = cfg.seed_lo, r.seed_hi = cfg.seed_hi, r.qin = W.Q[0].in, r.tin = W.T[0].in, r.KpQ = L.Kp0;
+  r.r_out = W.r, r.term_out = W.term, r.random_out = random_out;
+  launch_calql_rows<P>(r, s);
+  W.Q[1].in = W.Q[0].in, W.T[1].in = W.T[0].in;
+  // Q2 and the two target trunks on the three side streams beside Q1 (and the L, L' reduction in front of it)
+  hipStream_t s2 = fork_side(s, 0), s3 = fork_side(s, 1), s4 = fork_side(s, 2);
+  mlp_forward<P>(q, tp, tk1, L, MT, W.T[0], false, s3);
+  mlp_forward<P>(q, tp + nq, tk2, L, MT, W.T[1], false, s4);
+  mlp_forward<P>(q, qp + nq, qk2, L, M, W.Q[1], true, s2);
+  if (!cfg.per_row_logpi) launch_calql_lse(log_pi, log_pi_next, N, W.lse, s);
+  mlp_forward<P>(q, qp, qk1, L, M, W.Q[0], true, s);
+  if (s2 != s) join_side(s, s2, 0);
+  if (s3 != s) join_side(s, s3, 1);
+  if (s4 != s) join_side(s, s4, 2);
+  launch_calql_target(W.T[0].out, W.T[1].out, W.T[0].ldout, W.r, W.term, (float)gamma, N, S, W.y, y_out, s);
+  CalqlLoss l;
+  memset(&l, 0, sizeof(l));
+  l.q = W.Q[0].out, l.q_stride = W.Q[1].out - W.Q[0].out, l.ldq = W.Q[0].ldout, l.y = W.y, l.returns = returns;
+  l.log_pi = log_pi, l.log_pi_next = log_pi_next, l.lse = W.lse, l.per_row = cfg.per_row_logpi ? 1 : 0;
+  l.w = cfg.min_q_weight, l.clip_min = cfg.clip_diff_min, l.clip_max = cfg.clip_diff_max, l.c = cfg.log_rand_pi, l.N = N, l.R = R;
+  l.d_out = W.Q[0].d_out, l.d_stride = (char*)W.Q[1].d_out - (char*)W.Q[0].d_out, l.ldd = L.Kpo;
+  l.partial = W.partial, l.partial_d = W.partial_d, l.stats = stats;
+  launch_calql_loss<P>(l, s);
+  s2 = fork_side(s, 0);
+  mlp_backward<P>(q, qp + nq, qk2, L, M, W.Q[1], qgrad + nq, nullptr, nullptr, 0, s2);
+  mlp_backward<P>(q, qp, qk1, L, M, W.Q[0], qgrad, nullptr, nullptr, 0, s);
+  if (s2 != s) join_side(s, s2, 0);
+  // (rlpd.h has the reason: the column sum of the elem rows loses the bias gradient in bf16; partial's fourth sum is unrounded)
+  launch_rlpd_out_bias(W.partial, N, 2, qgrad, nq, param_layout(q).bout, s);
+  return check_launch();
+}
+int dppo_calql_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                              const float* target_q_params, const void* target_q1_packed, const void* target_q2_packed,
+                              const dppo_calql_cfg* cfg, const dppo_idql_batch* batch, int obs_dim, const float* returns,
+                              const float* next_actions, const float* pi_actions, const float* log_pi, const float* pi_next_actions,
+                              const float* log_pi_next, const float* random_actions, int64_t N, double gamma, float* q_grad,
+                              double* stats, float* y_out, float* random_out, void* workspace, int64_t workspace_bytes,
+                              dppo_stream_t stream) {
+  if (!cfg) return fail(-1, "null pointer: cfg");
+  if (int e = check_calql_q(q, obs_dim, N, cfg->n_random, cfg->n_next)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!(cfg->clip_diff_min <= cfg->clip_diff_max))
+    return fail(-1, "clip_diff_min=%g must not exceed clip_diff_max=%g", (double)cfg->clip_diff_min, (double)cfg->clip_diff_max);
+  if (!(cfg->min_q_weight >= 0.f && cfg->min_q_weight <= 3.0e38f)) return fail(-1, "min_q_weight=%g must be finite and >= 0", (double)cfg->min_q_weight);
+  if (!q_params || !q1_packed || !q2_packed || !target_q_params || !target_q1_packed || !target_q2_packed || !returns ||
+      !next_actions || !pi_actions || !log_pi || !pi_next_actions || !log_pi_next || !q_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
+#define CALL(P)                                                                                                                     \
+  calql_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed,       \
+                (const char*)target_q2_packed, *cfg, *batch, obs_dim, returns, next_actions, pi_actions, log_pi, pi_next_actions,   \
+                log_pi_next, random_actions, N, gamma, q_grad, stats, y_out, random_out, workspace, workspace_bytes,               \
+                (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }

@@ -1,7 +1,8 @@
 // LayerNorm in a PLAIN Q trunk: the reference's MLP with use_layernorm (model/common/mlp.py:46-74) puts
 // nn.LayerNorm(o_dim) -- eps 1e-5, NOT the residual blocks' 1e-6 (tile_ln.h) -- behind every Linear but the last and in front
 // of the activation:  x -> act(LN(W0 x + b0)) -> act(LN(W_b . + b_b)) ... -> Wout . + bout.  This is the critic of every RLPD,
-// Cal-QL and IBRL cfg the reference ships (CriticObsAct, use_layernorm: True, double_q: False).
+// Cal-QL and IBRL cfg the reference ships (CriticObsAct, use_layernorm: True; double_q: False in RLPD's, True -- a twin, calql.h -- in
+// all 16 of Cal-QL's).
 //
 // Forward.  The hidden layer's GEMM (launch_gemm_nt, unchanged) writes its bias-added row in fp32 with no activation;
 // ln_rows_kernel then normalises the unrounded row and applies the activation.  It keeps what the backward needs: z = xhat * gamma
@@ -37,7 +38,7 @@
 //   + 1 tail / head backward + 1 statistics (bf16: + 2 for the heads' bias gradient from the unrounded d_out)
 //   + the actor's parameter backward.  Nothing of a critic's is written: no weight gradient, column sum or gradient buffer.
 //   Shipped halfcheetah (E = 10, L = 2): 4 + 3 + 10 x 5 + 10 x 4 + 2 = 99 before the actor's backward.
-// Not built: a member-batched GEMM, weight gradients grouped across members, Cal-QL's conservative term, IBRL.
+// Not built: a member-batched GEMM, weight gradients grouped across members, IBRL.  (Cal-QL's conservative term: calql.h.)
 //
 // Launches of one forward of a trunk: L x (1 GEMM + 1 row kernel) + 1 GEMM.
 #pragma once

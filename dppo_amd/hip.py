@@ -110,7 +110,14 @@ class SacCfg(C.Structure):  # struct dppo_sac_cfg
                 ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
 
 
+class CalqlCfg(C.Structure):  # struct dppo_calql_cfg
+    _fields_ = [("n_random", C.c_int32), ("n_next", C.c_int32), ("per_row_logpi", C.c_int32), ("pad", C.c_int32),
+                ("min_q_weight", C.c_float), ("clip_diff_min", C.c_float), ("clip_diff_max", C.c_float), ("log_rand_pi", C.c_float),
+                ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
+
+
 IDQL_STAT_COUNT = 3
+CALQL_STAT_COUNT = 6
 DQL_STAT_COUNT = 5
 SAC_STAT_COUNT = 4
 
@@ -218,6 +225,10 @@ SYMBOLS = {
     "dppo_rlpd_actor_workspace_bytes": (_L, [_ND, _ND, _I, _I, _L, _I]),
     "dppo_rlpd_actor_fwd_bwd": (_I, [_ND, _ND, _I, _I, _P, _P, _P, C.POINTER(C.c_void_p), C.POINTER(SacCfg), C.POINTER(IdqlBatch), _I,
                                      _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    # Cal-QL: the conservative critic loss on a twin of LayerNorm Q trunks (csrc/calql.hip)
+    "dppo_calql_q_loss_workspace_bytes": (_L, [_ND, _I, _I, _L, _I, _I]),
+    "dppo_calql_q_loss_fwd_bwd": (_I, [_ND, _I, _P, _P, _P, _P, _P, _P, C.POINTER(CalqlCfg), C.POINTER(IdqlBatch), _I, _P, _P, _P, _P,
+                                       _P, _P, _P, _L, _D, _P, _P, _P, _P, _P, _L, _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

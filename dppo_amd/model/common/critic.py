@@ -87,13 +87,17 @@ class CriticObsAct(HipNet):
     is_composite = True  # two kernel images
 
     def __init__(self, cond_dim, mlp_dims, action_dim, action_steps=1, activation_type="Mish", use_layernorm=False,
-                 residual_tyle=False, double_q=True, precision="bf16", **kwargs):
+                 residual_tyle=False, double_q=True, precision="bf16", twin_layernorm=False, **kwargs):
         super().__init__()
         self.cond_dim, self.act_flat = cond_dim, action_dim * action_steps
         dims = [cond_dim + self.act_flat] + list(mlp_dims) + [1]
         model = ResidualMLP if residual_tyle else MLP
-        if use_layernorm and not residual_tyle and double_q:  # (the library reads one LayerNorm trunk, not a twin: csrc/rlpd.h)
-            raise NotImplementedError("dppo_amd: plain MLP with LayerNorm is built for CriticObsAct(double_q=False) only")
+        # A twin of LayerNorm trunks is read by Cal-QL's critic loss alone (csrc/calql.h): every other twin entry of the library
+        # refuses a LayerNorm descriptor, so the combination is opt-in (``twin_layernorm=True``; CalQL_Gaussian's cfg node asks for it)
+        if use_layernorm and not residual_tyle and double_q and not twin_layernorm:
+            raise NotImplementedError("dppo_amd: plain MLP with LayerNorm is built for CriticObsAct(double_q=False), and as a twin "
+                                      "for Cal-QL only (twin_layernorm=True)")
+        self.twin_layernorm = bool(twin_layernorm and use_layernorm and not residual_tyle and double_q)
         self.Q1 = model(dims, activation_type=activation_type, out_activation_type="Identity", use_layernorm=use_layernorm)
         if double_q:
             self.Q2 = model(dims, activation_type=activation_type, out_activation_type="Identity", use_layernorm=use_layernorm)
@@ -161,6 +165,15 @@ class CriticObsAct(HipNet):
         k1, k2 = self.packed(self.prec)
         q1 = torch.empty(N, dtype=torch.float32, device=state.device)
         q2 = torch.empty(N, dtype=torch.float32, device=state.device) if self.double_q else None
+        if self.twin_layernorm:  # one trunk per call: the double_q = 1 query refuses a LayerNorm descriptor
+            wsb = lib.dppo_idql_q_forward_workspace_bytes(C.byref(d), self.prec, N, 0)
+            ws, flat = self._ws.get(wsb, state.device, "dppo_idql_q_forward_workspace_bytes"), self.flat_params()
+            P = flat.numel() // 2
+            for i, (k, out) in enumerate(((k1, q1), (k2, q2))):
+                hip.check(lib.dppo_idql_q_forward(C.byref(d), self.prec, flat.data_ptr() + 4 * i * P, k.data_ptr(), None,
+                                                  state.data_ptr(), state.shape[1], B, action.data_ptr(), N, 0, out.data_ptr(), None,
+                                                  ws.data_ptr(), ws.numel(), hip.stream()), "dppo_idql_q_forward")
+            return q1, q2
         wsb = lib.dppo_idql_q_forward_workspace_bytes(C.byref(d), self.prec, N, int(self.double_q))
         if wsb < 0:
             hip.check(int(wsb), "dppo_idql_q_forward_workspace_bytes")

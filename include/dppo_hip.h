@@ -945,7 +945,8 @@ int dppo_sac_alpha_loss(const float* logp, int64_t N, const double* log_alpha, d
  * A plain kind-1 descriptor may set use_layernorm = 1 (hidden a multiple of 64, at most 1024): nn.LayerNorm(hidden), eps 1e-5,
  * behind every Linear but the last and in front of the activation.  Flat order per hidden layer: linear_1.weight, linear_1.bias,
  * norm_1.weight, norm_1.bias; the last layer is the Linear alone.  dppo_net_param_count, dppo_packed_bytes, dppo_pack_net(s),
- * dppo_idql_q_forward with double_q = 0 (one member's Q) and the entry below read such a descriptor; every other entry refuses it.
+ * dppo_idql_q_forward with double_q = 0 (one member's Q), the entries below and dppo_calql_q_loss_fwd_bwd (a twin of such trunks)
+ * read such a descriptor; every other entry refuses it.
  *
  * loss_critic (reference model/rl/gaussian_rlpd.py:64-103).  E members (2 <= E <= 16) share the descriptor: q_params and
  * target_q_params are [E][P] flat fp32, q_packed / target_q_packed HOST arrays of E device pointers, one kernel image per member
@@ -974,6 +975,45 @@ int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, 
                             const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise, const double* alpha,
                             float* actor_grad, double* stats, float* d_a, float* logp_out, float* actions_out, void* workspace,
                             int64_t workspace_bytes, dppo_stream_t stream);
+
+/* ---- Cal-QL: the conservative critic loss on a TWIN of LayerNorm Q trunks (csrc/calql.h) -----------------------------------------
+ * loss_critic (reference model/rl/gaussian_calql.py:56-171).  q: the LayerNorm descriptor dppo_rlpd_q_loss_fwd_bwd accepts; q_params,
+ * target_q_params and q_grad are [2][P] flat fp32 ([Q1 | Q2]), one kernel image per trunk.  With R = n_random, S = n_next, AF =
+ * in_dim - obs_dim, all arithmetic in fp32:
+ *   target (no gradient)   next_q[n] = max_s min(tq1, tq2)(next_obs_n, next_actions[n S + s]),
+ *                          y[n] = reward + ((float)gamma * (1 - terminated)) * next_q[n]
+ *   per trunk i            qd = q_i(obs, actions),  td_i = mean((qd - y)^2)
+ *                          q_rand[n][r] = q_i(obs_n, random_actions[n R + r]) - log_rand_pi    (the caller passes 0.5^AF: the literal
+ *                                         value the reference subtracts, not a logarithm)
+ *                          A[n] = max(q_i(obs_n, pi_actions_n), returns_n),  A'[n] = max(q_i(next_obs_n, pi_next_actions_n), returns_n)
+ *                          ood[n] = logsumexp([q_rand[n][:], A[n] + o_n, A'[n] + o'_n])         (max subtracted)
+ *                          diff_i = clamp(ood - qd, clip_diff_min, clip_diff_max)               (infinities allowed)
+ *   loss = td_1 + td_2 + min_q_weight * mean(diff_1) + min_q_weight * mean(diff_2)
+ * per_row_logpi = 0 (the reference's arithmetic): o_n = L = logsumexp_m(-log_pi[m]) and o'_n = L' = logsumexp_m(-log_pi_next[m]), two
+ * scalars per batch.  The reference subtracts log_pi (N,) from A[:, None] (N, 1): the broadcast is (N, N), row n of its (N, R + 2 N)
+ * matrix holds A[n] - log_pi[m] for EVERY m, and logsumexp_m(A_n - lp_m) = A_n + L.  per_row_logpi = 1: o_n = -log_pi[n], o'_n =
+ * -log_pi_next[n], the Cal-QL paper's importance weights.
+ * Gradient of the output rows, g = min_q_weight / N where clip_diff_min <= ood - qd <= clip_diff_max and 0 elsewhere, p the softmax of
+ * the R + 2 entries: data row 2 (qd - y) / N - g; random row r: g p_r; pi row: g p_R where q > returns, half of it at equality, 0
+ * below; pi_next row likewise with p_{R+1}.  log_pi, log_pi_next and every action are read as data: nothing reaches an actor.
+ * random_actions (N R, AF), or NULL: drawn uniform in [-1, 1) from Philox4x32-10 keyed by (seed_lo, seed_hi), counter = element
+ * index, and written to random_out where that is given.  q_grad <- d loss / d params of both trunks (OVERWRITTEN); stats[6] <- {loss,
+ * td_1 + td_2, mean diff_1, mean diff_2, mean q1 on the data rows, mean y} (device doubles, fixed summation order).  Optional
+ * (NULL): y_out (N,), random_out (N R, AF).  1 <= n_random, n_next <= 64; N (n_random + 3) and N n_next below 2^31. */
+typedef struct dppo_calql_cfg {
+  int32_t n_random, n_next, per_row_logpi, pad;
+  float min_q_weight, clip_diff_min, clip_diff_max, log_rand_pi;
+  uint32_t seed_lo, seed_hi;
+} dppo_calql_cfg;
+#define DPPO_CALQL_STAT_COUNT 6
+int64_t dppo_calql_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int n_random, int n_next);
+int dppo_calql_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_params, const void* q1_packed, const void* q2_packed,
+                              const float* target_q_params, const void* target_q1_packed, const void* target_q2_packed,
+                              const dppo_calql_cfg* cfg, const dppo_idql_batch* batch, int obs_dim, const float* returns,
+                              const float* next_actions, const float* pi_actions, const float* log_pi, const float* pi_next_actions,
+                              const float* log_pi_next, const float* random_actions, int64_t N, double gamma, float* q_grad,
+                              double* stats, float* y_out, float* random_out, void* workspace, int64_t workspace_bytes,
+                              dppo_stream_t stream);
 
 #ifdef __cplusplus
 }
