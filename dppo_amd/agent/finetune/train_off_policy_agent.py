@@ -28,6 +28,7 @@ log = logging.getLogger(__name__)
 
 class OffPolicyAgent:
     nets = ()  # the model's networks whose kernel images follow a loaded checkpoint
+    replay_cls = DeviceReplay  # the ring's class (Cal-QL's carries each transition's return)
     lr_schedulers = ("actor_lr_scheduler", "critic_lr_scheduler")  # stepped once per iteration, in this order
     # a train iteration's log line after "itr: step |", and the record keys it prints
     log_line = "loss actor %8.4f | loss critic %8.4f | reward %8.4f | t:%8.4f"
@@ -78,7 +79,7 @@ class OffPolicyAgent:
         self.gamma = cfg.train.gamma  # applied to the reward of every act_steps env steps
         self.scale_reward_factor = cfg.train.scale_reward_factor
         self.buffer_size = cfg.train.buffer_size
-        self.replay = DeviceReplay(self.buffer_size, self.n_envs, self.n_cond_step * self.obs_dim,
+        self.replay = self.replay_cls(self.buffer_size, self.n_envs, self.n_cond_step * self.obs_dim,
                                    self.act_steps * self.action_dim, self.device)
 
     @staticmethod

@@ -3254,14 +3254,14 @@ int64_t dppo_rlpd_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_n
     return carve_rlpd_actor<decltype(p)>(c, *actor, *q, N, E, W);
   });
 }
-// d q / d (layer 0's Linear output) of one LayerNorm member, into its columns of dhcat (row stride ldh): the seed, then per hidden
-// layer from the top the LayerNorm backward without parameter sums and, except at layer 0, the data GEMM with the act' epilogue
+// d q / d (layer 0's Linear output) of one LayerNorm trunk, into its columns of dhcat (row stride ldh), from a seed d q / d z_L that
+// is already in dza: per hidden layer from the top the LayerNorm backward without parameter sums and, except at layer 0, the data
+// GEMM with the act' epilogue.  (RLPD's members seed with Wout (.) act'(z_L); Cal-QL's twin with calql_select_kernel's weighted one.)
 template <class P>
-static void rlpd_member_chain(const dppo_net_desc& q, const float* prm, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B,
-                              void* dza, void* dzb, void* dh0, int ldh, hipStream_t s) {
+static void rlpd_chain_from_seed(const dppo_net_desc& q, const float* prm, const char* pk, const PackLayout& L, int64_t N,
+                                 MlpBufs<P>& B, void* dza, void* dzb, void* dh0, int ldh, hipStream_t s) {
   const ParamLayout pl = param_layout(q);
   const int H = q.hidden, nb = q.n_blocks;
-  launch_qsm_seed<P>(pk + L.Wout, B.z1[nb - 1], N, H, q.act, dza, s);
   LnBwd ln;
   memset(&ln, 0, sizeof(ln));
   ln.ld = H, ln.ldx = H, ln.M = N, ln.H = H;  // (partial stays null: a data-gradient chain)
@@ -3281,6 +3281,13 @@ static void rlpd_member_chain(const dppo_net_desc& q, const float* prm, const ch
   }
   ln.dz = dh0, ln.ld = ldh, ln.x = B.h[0], ln.stats = B.ln_stats, ln.gamma = prm + pl.n0w;
   launch_ln_bwd<P>(ln, s);
+}
+// ... with the seed of one member's own Q in front: Wout (.) act'(z_L)
+template <class P>
+static void rlpd_member_chain(const dppo_net_desc& q, const float* prm, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B,
+                              void* dza, void* dzb, void* dh0, int ldh, hipStream_t s) {
+  launch_qsm_seed<P>(pk + L.Wout, B.z1[q.n_blocks - 1], N, q.hidden, q.act, dza, s);
+  rlpd_chain_from_seed<P>(q, prm, pk, L, N, B, dza, dzb, dh0, ldh, s);
 }
 template <class P>
 static int rlpd_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, int E, const float* ap, const char* ak, const float* qp,
@@ -3472,6 +3479,135 @@ int dppo_calql_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_p
                 (const char*)target_q2_packed, *cfg, *batch, obs_dim, returns, next_actions, pi_actions, log_pi, pi_next_actions,   \
                 log_pi_next, random_actions, N, gamma, q_grad, stats, y_out, random_out, workspace, workspace_bytes,               \
                 (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+// The actor's loss through the minimum of the LayerNorm twin (calql.h).  The actor and its head are SAC's.
+static int check_calql_pair(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim, int64_t N) {
+  if (int e = check_sac_actor(a)) return e;
+  if (int e = check_calql_q(q, obs_dim, N, 1, 1)) return e;
+  if (a->cond_dim != obs_dim || q->in_dim - obs_dim != a->out_dim / 2)
+    return fail(-1, "actor / Q descriptors do not pair: actor cond_dim=%d, Ta*Da=%d against obs_dim=%d, Q in_dim=%d", a->cond_dim,
+                a->out_dim / 2, obs_dim, q->in_dim);
+  return 0;
+}
+template <class P>
+struct CalqlActorWs {
+  MlpBufs<P> A, Q[2];
+  void *dza[2], *dzb[2];  // trunk i's two alternating [N][H] chain buffers; dza[i] takes the seed
+  void* dhcat;            // [N][2H] elem: trunk i's dx_0 in columns [i H, (i + 1) H)
+  void* w0a;              // [AF][2H] elem
+  float *actions, *logp, *sig, *qsel;
+  float* dout32;  // bf16 only (SacTail::d_out32)
+  uint8_t* sel;
+};
+template <class P>
+static size_t carve_calql_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, CalqlActorWs<P>& W) {
+  const size_t ES = P::ESIZE;
+  const int AF = a.out_dim / 2;
+  carve_mlp<P>(c, a, N, true, true, W.A);
+  for (int i = 0; i < 2; ++i) {
+    carve_mlp<P>(c, q, N, true, false, W.Q[i]);
+    W.dza[i] = c.take((size_t)N * q.hidden * ES);
+    W.dzb[i] = c.take((size_t)N * q.hidden * ES);
+  }
+  W.dhcat = c.take((size_t)N * 2 * q.hidden * ES);
+  W.w0a = c.take((size_t)AF * 2 * q.hidden * ES);
+  W.actions = (float*)c.take((size_t)N * AF * 4);
+  W.logp = (float*)c.take((size_t)N * 4);
+  W.sig = (float*)c.take((size_t)N * 4);
+  W.qsel = (float*)c.take((size_t)N * 4);
+  W.dout32 = ES == 4 ? nullptr : (float*)c.take((size_t)N * 2 * AF * 4);
+  W.sel = (uint8_t*)c.take((size_t)N);
+  return al256(c.off);
+}
+int64_t dppo_calql_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
+  if (check_calql_pair(actor, q, obs_dim, N) || check_prec(prec)) return -1;
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    CalqlActorWs<decltype(p)> W;
+    return carve_calql_actor<decltype(p)>(c, *actor, *q, N, W);
+  });
+}
+template <class P>
+static int calql_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float* ap, const char* ak, const float* qp,
+                            const char* qk1, const char* qk2, const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N,
+                            const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
+                            uint8_t* sel_out, float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  CalqlActorWs<P> W;
+  const size_t need = carve_calql_actor<P>(c, a, q, N, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const ParamLayout plq = param_layout(q);
+  const int AF = a.out_dim / 2, H = q.hidden;
+  float* actions = actions_out != nullptr ? actions_out : W.actions;
+  float* logp = logp_out != nullptr ? logp_out : W.logp;
+  uint8_t* sel = sel_out != nullptr ? sel_out : W.sel;
+  // as rlpd_actor_impl: the actor's rows [obs | 0], the W0 action columns of both trunks as [AF][2H], the actor's forward, the head
+  // with ONE image of the critic's rows [obs | a | 0]
+  IdqlRows r = idql_rows_of(b, N, OD, AF);
+  r.vin = W.A.in, r.KpV = LA.Kp0;
+  launch_idql_rows<P>(r, s);
+  launch_rlpd_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, H, 2, W.w0a, s);
+  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
+  SacHead h = sac_head_of(cfg, W.A.out, W.A.ldout, AF, noise, N);
+  h.ring = idql_rows_of(b, N, OD, AF);
+  h.actions = actions, h.logp = logp, h.sig_row = W.sig, h.q1in = h.q2in = W.Q[0].in, h.KpQ = LQ.Kp0;
+  launch_sac_head<P>(h, s);
+  W.Q[1].in = W.Q[0].in;
+  const float* prm[2] = {qp, qp + plq.total};
+  const char* qk[2] = {qk1, qk2};
+  // both forwards side by side; the choice of the twin per row seeds both chains (the other trunk's seed is 0, a tie's are halves)
+  hipStream_t s2 = fork_side(s, 0);
+  mlp_forward<P>(q, prm[1], qk[1], LQ, N, W.Q[1], true, s2);
+  mlp_forward<P>(q, prm[0], qk[0], LQ, N, W.Q[0], true, s);
+  if (s2 != s) join_side(s, s2, 0);
+  CalqlSelect sl;
+  memset(&sl, 0, sizeof(sl));
+  sl.q1 = W.Q[0].out, sl.q2 = W.Q[1].out, sl.ldq = W.Q[0].ldout, sl.wout1 = qk[0] + LQ.Wout, sl.wout2 = qk[1] + LQ.Wout;
+  sl.z1 = W.Q[0].z1[q.n_blocks - 1], sl.z2 = W.Q[1].z1[q.n_blocks - 1], sl.N = N, sl.H = H, sl.act = q.act;
+  sl.dz1 = W.dza[0], sl.dz2 = W.dza[1], sl.sel = sel, sl.qsel = W.qsel;
+  launch_calql_select<P>(sl, s);
+  s2 = fork_side(s, 0);
+  rlpd_chain_from_seed<P>(q, prm[1], qk[1], LQ, N, W.Q[1], W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, 2 * H, s2);
+  rlpd_chain_from_seed<P>(q, prm[0], qk[0], LQ, N, W.Q[0], W.dza[0], W.dzb[0], W.dhcat, 2 * H, s);
+  if (s2 != s) join_side(s, s2, 0);
+  RlpdTail tl;
+  memset(&tl, 0, sizeof(tl));
+  tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.K = 2 * H, tl.E = 1, tl.alpha = alpha;  // (E = 1: the seeds carry the weights)
+  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
+  launch_rlpd_tail<P>(tl, s);
+  SacStats st;
+  memset(&st, 0, sizeof(st));
+  st.qsel = W.qsel, st.logp = logp, st.sig_row = W.sig, st.alpha = alpha, st.N = N, st.AF = AF, st.stats = stats;
+  launch_sac_stats(st, s);
+  mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s);
+  if (W.dout32 != nullptr)  // the two heads' bias gradient again, from the unrounded rows
+    launch_colsum<F32>(W.dout32, (int)N, 2 * AF, 2 * AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
+  return check_launch();
+}
+int dppo_calql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
+                             const void* actor_packed, const float* q_params, const void* q1_packed, const void* q2_packed,
+                             const dppo_sac_cfg* cfg, const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise,
+                             const double* alpha, float* actor_grad, double* stats, float* d_a, float* logp_out, uint8_t* sel_out,
+                             float* actions_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_calql_pair(actor, q, obs_dim, N)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (int e = check_sac_cfg(actor, cfg)) return e;
+  if (cfg->deterministic) return fail(-1, "the actor loss samples: deterministic must be 0");
+  if (!actor_params || !actor_packed || !q_params || !q1_packed || !q2_packed || !alpha || !actor_grad || !stats || !workspace)
+    return fail(-1, "null pointer");
+  if (!batch) return fail(-1, "null batch");
+  if (!batch->obs) return fail(-1, "null pointer in batch");
+  if (batch->cap < 1 || batch->n_envs < 1 || batch->count < 1 || batch->count > batch->cap || batch->head < 0 || batch->head >= batch->cap)
+    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
+  if (!batch->inds && N > batch->count * batch->n_envs)
+    return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N, (long long)(batch->count * batch->n_envs));
+#define CALL(P)                                                                                                                      \
+  calql_actor_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, \
+                      *cfg, *batch, obs_dim, N, noise, alpha, actor_grad, stats, d_a, logp_out, sel_out, actions_out, workspace,      \
+                      workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }

@@ -28,7 +28,26 @@
 //        + 1 target + 2 (loss, statistics) + 2 backwards x [1 data GEMM + L x (2 LayerNorm backward + weight gradient + its slab
 //          reduce + 2 column sum) + (L - 1) data GEMMs + out layer's weight gradient, slab reduce and 2 column sum] + 1 out-layer bias.
 //   Shipped kitchen (L = 3): 1 + 1 + 14 + 14 + 3 + 2 x 25 + 1 = 84.
-// Not built: loss_actor (the min of a LayerNorm twin needs a per-row select in front of rlpd.h's chains), TrainCalQLAgent.
+//
+// The actor's loss through the twin's minimum (reference model/rl/gaussian_calql.py:173-182): with a_n, logp_n SAC's reparameterised
+// sample at obs_n,  loss = mean_n [-min(q1, q2)(obs_n, a_n) + alpha logp_n].  The head writes ONE row image [obs | a | 0] that both
+// trunks read; each runs its forward (z, mean, rstd kept).  calql_select_kernel picks per row (q2 < q1: Q2; q1 == q2: both at one
+// half, torch.minimum's backward; everything else, a NaN included: Q1) and writes both chains' seeds w_i Wout_i (.) act'(z_L), zero
+// for the trunk a row did not select.  From there each trunk runs rlpd.h's data-gradient chain (rlpd_chain_from_seed, shared with
+// dppo_rlpd_actor_fwd_bwd): per hidden layer from the top ln_bwd_kernel with no parameter sums and, except at layer 0, the data GEMM
+// with the act' epilogue.  Trunk i's dx_0 lands in columns [i H, (i + 1) H) of one [N][2H] image; launch_rlpd_pack_w0a (E = 2) packs
+// the action columns of both W0 as [AF][2H]; launch_rlpd_tail with K = 2H, E = 1 forms g = dQ_sel/da (the unselected half is zero,
+// a tie's halves add) and runs SAC's head backward; launch_sac_stats on qsel gives {loss, mean qsel, mean logp, mean sigma}.
+//
+// Launches of dppo_calql_actor_fwd_bwd with L hidden layers per trunk (read off the code, not traced), side-stream events aside:
+//   1 row builder + 1 W0 pack + the actor's forward (3 GEMMs on the shipped two-layer actor) + 1 head epilogue
+//   + 2 x [L x (1 GEMM + 1 row kernel) + 1 GEMM]          the trunks' forwards (Q2 on a side stream)
+//   + 1 select/seed
+//   + 2 x [L LayerNorm backwards + (L - 1) data GEMMs]    the trunks' chains (Q2 on a side stream)
+//   + 1 tail / head backward + 1 statistics (bf16: + 2 for the heads' bias gradient from the unrounded d_out)
+//   + the actor's parameter backward.  Nothing of the critic's is written: no weight gradient, column sum or gradient buffer.
+//   Shipped kitchen (L = 3): 2 + 3 + 1 + 2 x 7 + 1 + 2 x 5 + 2 = 33 before the actor's backward.
+// Not built: a member-batched or fused twin chain, IBRL.
 #pragma once
 #include "rlpd.h"
 
@@ -80,5 +99,24 @@ struct CalqlLoss {
 };
 template <class P>
 void launch_calql_loss(const CalqlLoss& a, hipStream_t s);
+
+// ---- the actor's loss through the twin's minimum -----------------------------------------------------------------------------------
+// sel[n] = 1 where q2 < q1 (weights 0, 1), 2 where q1 == q2 (weights 1/2, 1/2: torch.minimum's backward), 0 otherwise (weights 1, 0;
+// a NaN on either side lands here);  qsel[n] = q2 where sel = 1, q1 elsewhere (no fminf: a NaN in q1 reaches the statistics);
+// dz_i[n][h] = elem(w_i * (wout_i[h] * act'(z_i[n][h]))), exactly zero for w_i = 0.  The whole [N][H] image of both trunks is written
+// on every call.  One wave per row, CALQL_SEL_ROWS rows per 256-thread block, 16-byte accesses along H (a multiple of 64).
+constexpr int CALQL_SEL_ROWS = 4;
+struct CalqlSelect {
+  const float *q1, *q2;  // column 0 of [N][ldq]
+  int ldq;
+  const void *wout1, *wout2, *z1, *z2;  // [H] elem, [N][H] elem: the top hidden layer's LayerNorm output z
+  int64_t N;
+  int H, act;
+  void *dz1, *dz2;  // [N][H] elem
+  uint8_t* sel;     // [N]
+  float* qsel;      // [N]
+};
+template <class P>
+void launch_calql_select(const CalqlSelect& a, hipStream_t s);
 
 }  // namespace dppo

@@ -251,4 +251,46 @@ void launch_calql_loss(const CalqlLoss& a, hipStream_t s) {
 template void launch_calql_loss<F32>(const CalqlLoss&, hipStream_t);
 template void launch_calql_loss<BF16>(const CalqlLoss&, hipStream_t);
 
+// ---- the actor's choice of the twin and both chains' seeds --------------------------------------------------------------------------
+// One wave per row (CALQL_SEL_ROWS rows per block, as ln_rows_kernel): every lane reads the row's two Q values (one cache line each,
+// broadcast), so the choice is wave-uniform; lane l then takes the 16-byte chunks l, l + 64, ... of both trunks' rows.  Elementwise:
+// an output depends on its own inputs alone and on nothing of the launch geometry.
+template <class P>
+__global__ __launch_bounds__(256) void calql_select_kernel(const CalqlSelect a) {
+  typedef typename P::elem_t E;
+  constexpr int EPC = 16 / P::ESIZE;
+  const int lane = threadIdx.x & 63;
+  const int64_t n = (int64_t)blockIdx.x * CALQL_SEL_ROWS + (threadIdx.x >> 6);
+  if (n >= a.N) return;  // (wave-uniform)
+  const float q1 = a.q1[n * a.ldq], q2 = a.q2[n * a.ldq];
+  // (a NaN on either side fails both comparisons: Q1, whose value then reaches the statistics)
+  const int sel = q2 < q1 ? 1 : (q1 == q2 ? 2 : 0);
+  const float w1 = sel == 0 ? 1.f : (sel == 2 ? 0.5f : 0.f), w2 = sel == 1 ? 1.f : (sel == 2 ? 0.5f : 0.f);
+  if (lane == 0) {
+    a.sel[n] = (uint8_t)sel;
+    a.qsel[n] = sel == 1 ? q2 : q1;
+  }
+  const int W = a.H / EPC;
+  for (int c = lane; c < W; c += 64) {
+    CalqlChunk<P> w, x, o;
+    w.v = *(const u32x4*)((const E*)a.wout1 + c * EPC);
+    x.v = *(const u32x4*)((const E*)a.z1 + n * a.H + c * EPC);
+#pragma unroll
+    for (int k = 0; k < EPC; ++k) o.e[k] = P::from_f32(w1 == 0.f ? 0.f : w1 * (P::to_f32(w.e[k]) * act_grad_f(a.act, P::to_f32(x.e[k]))));
+    *(u32x4*)((E*)a.dz1 + n * a.H + c * EPC) = o.v;
+    w.v = *(const u32x4*)((const E*)a.wout2 + c * EPC);
+    x.v = *(const u32x4*)((const E*)a.z2 + n * a.H + c * EPC);
+#pragma unroll
+    for (int k = 0; k < EPC; ++k) o.e[k] = P::from_f32(w2 == 0.f ? 0.f : w2 * (P::to_f32(w.e[k]) * act_grad_f(a.act, P::to_f32(x.e[k]))));
+    *(u32x4*)((E*)a.dz2 + n * a.H + c * EPC) = o.v;
+  }
+}
+template <class P>
+void launch_calql_select(const CalqlSelect& a, hipStream_t s) {
+  if (a.N < 1) return;
+  hipLaunchKernelGGL((calql_select_kernel<P>), dim3((unsigned)((a.N + CALQL_SEL_ROWS - 1) / CALQL_SEL_ROWS)), dim3(256), 0, s, a);
+}
+template void launch_calql_select<F32>(const CalqlSelect&, hipStream_t);
+template void launch_calql_select<BF16>(const CalqlSelect&, hipStream_t);
+
 }  // namespace dppo

@@ -38,7 +38,8 @@
 //   + 1 tail / head backward + 1 statistics (bf16: + 2 for the heads' bias gradient from the unrounded d_out)
 //   + the actor's parameter backward.  Nothing of a critic's is written: no weight gradient, column sum or gradient buffer.
 //   Shipped halfcheetah (E = 10, L = 2): 4 + 3 + 10 x 5 + 10 x 4 + 2 = 99 before the actor's backward.
-// Not built: a member-batched GEMM, weight gradients grouped across members, IBRL.  (Cal-QL's conservative term: calql.h.)
+// Not built: a member-batched GEMM, weight gradients grouped across members, IBRL.  (Cal-QL: calql.h; its actor runs this file's
+// chain from a seed of its own: rlpd_chain_from_seed in api.hip.)
 //
 // Launches of one forward of a trunk: L x (1 GEMM + 1 row kernel) + 1 GEMM.
 #pragma once

@@ -229,6 +229,10 @@ SYMBOLS = {
     "dppo_calql_q_loss_workspace_bytes": (_L, [_ND, _I, _I, _L, _I, _I]),
     "dppo_calql_q_loss_fwd_bwd": (_I, [_ND, _I, _P, _P, _P, _P, _P, _P, C.POINTER(CalqlCfg), C.POINTER(IdqlBatch), _I, _P, _P, _P, _P,
                                        _P, _P, _P, _L, _D, _P, _P, _P, _P, _P, _L, _P]),
+    # ... and the actor loss through the min of that twin (dppo_sac_actor_fwd_bwd's argument list)
+    "dppo_calql_actor_workspace_bytes": (_L, [_ND, _ND, _I, _I, _L]),
+    "dppo_calql_actor_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, _P, C.POINTER(SacCfg), C.POINTER(IdqlBatch), _I, _L, _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _P, _L, _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

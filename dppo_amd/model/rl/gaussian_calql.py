@@ -11,8 +11,11 @@ A fact about the reference, imitated by default: it subtracts ``log_pi`` (N,) fr
 the WHOLE batch's log-probabilities; its loss equals the per-row form with ``-log_pi[n]`` replaced by the scalar ``logsumexp_m(-log_pi
 [m])`` (csrc/calql.h).  ``per_row_logpi=True`` gives the Cal-QL paper's per-row importance weights instead.
 
-``forward``, ``loss_temperature`` and ``update_target_critic`` are SAC's.  ``loss_actor`` (the min of a LayerNorm twin) and
-``TrainCalQLAgent`` are not built yet."""
+``loss_actor`` is one library call too (``dppo_calql_actor_fwd_bwd``): SAC's reparameterised sample, both trunks' forwards, a per-row
+select of the smaller Q (a tie splits in halves, ``torch.minimum``'s backward) that seeds RLPD's action-gradient chains through
+LayerNorm, one tail whose epilogue is SAC's head backward, then the actor's backward.  It runs on the GPU only; on a CPU model it
+raises ``NotImplementedError``.  ``forward``, ``loss_temperature`` and ``update_target_critic`` are SAC's.  The agent is
+``dppo_amd.agent.finetune.train_calql_agent.TrainCalQLAgent``."""
 from __future__ import annotations
 
 import copy
@@ -24,6 +27,7 @@ import torch
 
 from dppo_amd import hip
 from dppo_amd.model.common import off_policy
+from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss, flat_views
 from dppo_amd.model.rl.gaussian_sac import SAC_Gaussian
 from dppo_amd.util.replay import DeviceReplay
 
@@ -107,5 +111,40 @@ class CalQL_Gaussian(SAC_Gaussian):
         return off_policy.critic_loss(self, q, stats)
 
     def loss_actor(self, obs, alpha, inds=None, noise=None):
-        raise NotImplementedError("dppo_amd: Cal-QL's actor loss (the min of a LayerNorm twin: a per-row select in front of RLPD's "
-                                  "action-gradient chains) is the follow-up to the critic loss and is not built")
+        """mean(-min(q1, q2)(s, a) + alpha logp(a)) on a reparameterised sample (reference :173-182), and d loss / d actor parameters
+        in ``last_loss_grad``; nothing of the critic's is written.  ``noise`` (N, Ta, Da) replaces the draws.  ``last_stats``: {loss,
+        mean q_sel, mean logp, mean sigma}; ``last_d_a`` (N, Ta*Da) = d loss / d a through the twin; ``last_logp`` (N,);
+        ``last_actions`` (N, Ta*Da); ``last_sel`` (N,) bytes: 0 Q1 was taken, 1 Q2 (q2 < q1), 2 a tie (both at one half,
+        ``torch.minimum``'s backward).  ``obs`` may be a ``DeviceReplay`` (rows ``inds``)."""
+        q, net = self.critic, self.network
+        if not next(net.parameters()).is_cuda:
+            raise NotImplementedError("dppo_amd: Cal-QL's actor loss runs on the GPU only; a CPU path would be a follow-up and is "
+                                      "not built")
+        batch, N, keep = off_policy.as_batch("Cal-QL", obs, inds)
+        dev = net.flat_params().device
+        AF = self.horizon_steps * net.action_dim
+        cfg = self._cfg(False, noise)
+        if noise is not None:
+            noise = noise.reshape(N, AF).contiguous().float()
+        alpha = self._dev_scalar(alpha, dev)
+        lib, da, dq = hip.load(), net.net_desc(), q.net_desc()
+        OD = q.cond_dim
+        ws = self._ws_actor.get(lib.dppo_calql_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N), dev,
+                                "dppo_calql_actor_workspace_bytes")
+        k1, k2 = q.packed(self.prec)
+        grad = torch.empty_like(net.flat_params())
+        stats = torch.empty(hip.SAC_STAT_COUNT, dtype=torch.float64, device=dev)
+        d_a = torch.empty(N, AF, dtype=torch.float32, device=dev)
+        logp = torch.empty(N, dtype=torch.float32, device=dev)
+        sel = torch.empty(N, dtype=torch.uint8, device=dev)
+        actions = torch.empty(N, AF, dtype=torch.float32, device=dev)
+        hip.check(lib.dppo_calql_actor_fwd_bwd(
+            C.byref(da), C.byref(dq), self.prec, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(),
+            q.flat_params().data_ptr(), k1.data_ptr(), k2.data_ptr(), C.byref(cfg), C.byref(batch), OD, N, hip.ptr(noise),
+            alpha.data_ptr(), grad.data_ptr(), stats.data_ptr(), d_a.data_ptr(), logp.data_ptr(), sel.data_ptr(),
+            actions.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_calql_actor_fwd_bwd")
+        for name, v in (("last_loss_grad", grad), ("last_stats", stats), ("last_d_a", d_a), ("last_logp", logp), ("last_sel", sel),
+                        ("last_actions", actions)):
+            object.__setattr__(self, name, v)
+        params = net.trunk_parameters()
+        return _FusedDenoiseLoss.apply(stats[0], flat_views(grad, params), *params)

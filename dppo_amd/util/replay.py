@@ -64,3 +64,61 @@ class DeviceReplay:
         return hip.IdqlBatch(self.obs.data_ptr(), self.next_obs.data_ptr(), self.actions.data_ptr(), self.reward.data_ptr(),
                              self.terminated.data_ptr(), None if inds is None else inds.data_ptr(), self.cap, self.n_envs,
                              self.head, self.steps)
+
+
+class ReturnsReplay(DeviceReplay):
+    """``DeviceReplay`` with a sixth column: the Monte-Carlo reward-to-go of every stored transition (Cal-QL's online half; reference
+    agent/finetune/train_calql_agent.py:109, 258-276).  A return is known only when its episode ends, so ``append`` remembers the
+    slots of every env's OPEN episode and ``close_episode`` writes that episode's discounted returns into exactly those slots: a
+    return lives in its transition's slot, so wrap-around and eviction cannot separate the two.  Only transitions of closed episodes
+    are drawn (``closed_indices`` / ``draw``); the bookkeeping is host-side numpy, nothing here reads the device.  An episode longer
+    than the ring would evict its own head before its return is known: that is an error."""
+
+    def __init__(self, buffer_size: int, n_envs: int, obs_dim: int, act_dim: int, device="cuda:0"):
+        super().__init__(buffer_size, n_envs, obs_dim, act_dim, device)
+        self.reward_to_go = torch.zeros(self.cap, self.n_envs, dtype=torch.float32, device=device)
+        self.closed = np.zeros((self.cap, self.n_envs), dtype=bool)  # slot holds a transition whose return is written
+        self.open_slots = [[] for _ in range(self.n_envs)]           # per env: the open episode's slots, oldest first
+
+    def append(self, prev_obs, next_obs, action, reward, terminated) -> None:
+        slot = (self.head + self.steps) % self.cap if self.steps < self.cap else self.head
+        for e, op in enumerate(self.open_slots):
+            if op and op[0] == slot:
+                raise ValueError(f"an episode of env {e} is longer than the replay ring ({self.cap} steps): its first transition "
+                                 "would be evicted before its return is known")
+        super().append(prev_obs, next_obs, action, reward, terminated)
+        self.closed[slot] = False
+        for op in self.open_slots:
+            op.append(slot)
+
+    def close_episode(self, returns, env: int = 0) -> None:
+        """The episode of ``env`` that is open ends: ``returns`` (its length,) are the discounted rewards-to-go of its transitions,
+        oldest first, computed on the host from the rollout's rewards."""
+        slots = self.open_slots[env]
+        returns = np.asarray(returns, dtype=np.float32).reshape(-1)
+        if len(returns) != len(slots):
+            raise ValueError(f"close_episode: {len(returns)} returns for the {len(slots)} transitions of env {env}'s open episode")
+        if len(slots):
+            rows = torch.as_tensor(np.asarray(slots, dtype=np.int64))
+            self.reward_to_go[rows.to(self.reward_to_go.device), env] = torch.from_numpy(returns).to(self.reward_to_go.device)
+            self.closed[slots, env] = True
+        self.open_slots[env] = []
+
+    def closed_indices(self) -> np.ndarray:
+        """The logical indices (oldest first) of the stored transitions whose episode is closed."""
+        order = (self.head + np.arange(self.steps)) % self.cap
+        return np.flatnonzero(self.closed[order].reshape(-1))
+
+    def n_closed(self) -> int:
+        return int(self.closed.sum())
+
+    def gather(self, inds: torch.Tensor):
+        """(obs, next_obs, actions, reward, terminated, reward_to_go) rows of the logical indices ``inds``."""
+        rows = self.slot_of(inds.to(self.obs.device))
+        return super().gather(inds) + (self.reward_to_go.reshape(self.cap * self.n_envs)[rows],)
+
+    def draw(self, num_batch: int, batch_size: int) -> torch.Tensor:
+        """As ``DeviceReplay.draw`` over the transitions of closed episodes only."""
+        ok = self.closed_indices()
+        inds = ok[np.random.choice(len(ok), (num_batch, batch_size))]
+        return torch.from_numpy(inds.astype(np.int64)).to(self.obs.device)

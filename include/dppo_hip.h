@@ -945,7 +945,7 @@ int dppo_sac_alpha_loss(const float* logp, int64_t N, const double* log_alpha, d
  * A plain kind-1 descriptor may set use_layernorm = 1 (hidden a multiple of 64, at most 1024): nn.LayerNorm(hidden), eps 1e-5,
  * behind every Linear but the last and in front of the activation.  Flat order per hidden layer: linear_1.weight, linear_1.bias,
  * norm_1.weight, norm_1.bias; the last layer is the Linear alone.  dppo_net_param_count, dppo_packed_bytes, dppo_pack_net(s),
- * dppo_idql_q_forward with double_q = 0 (one member's Q), the entries below and dppo_calql_q_loss_fwd_bwd (a twin of such trunks)
+ * dppo_idql_q_forward with double_q = 0 (one member's Q), the entries below and dppo_calql_q_loss_fwd_bwd / dppo_calql_actor_fwd_bwd (a twin of such trunks)
  * read such a descriptor; every other entry refuses it.
  *
  * loss_critic (reference model/rl/gaussian_rlpd.py:64-103).  E members (2 <= E <= 16) share the descriptor: q_params and
@@ -1014,6 +1014,23 @@ int dppo_calql_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_p
                               const float* log_pi_next, const float* random_actions, int64_t N, double gamma, float* q_grad,
                               double* stats, float* y_out, float* random_out, void* workspace, int64_t workspace_bytes,
                               dppo_stream_t stream);
+/* loss_actor (reference model/rl/gaussian_calql.py:173-182) = mean_n [-min(q1, q2)(obs_n, a_n) + (float)alpha * logp_n] on SAC's
+ * reparameterised sample: dppo_sac_actor_fwd_bwd's argument list on the LayerNorm twin dppo_calql_q_loss_fwd_bwd trains (q_params
+ * [2][P] flat fp32, one kernel image per trunk; deterministic must be 0).  One call: the actor's forward, the head (ONE image of the
+ * critic's rows [obs | a | 0], read by both trunks), both LayerNorm forwards, one launch that picks per row and seeds both trunks'
+ * data-gradient chains, the chains through LayerNorm, one launch for the K = 2*hidden product with the stacked action columns whose
+ * epilogue is SAC's head backward with g = dQ_sel/da, then the actor's backward.  Per row: q2 < q1 selects Q2 (sel = 1); q1 == q2 is
+ * a tie (sel = 2), both trunks at one half, torch.minimum's backward; everything else selects Q1 (sel = 0), a NaN on either side
+ * included, and q1 is then what the statistics read.  actor_grad <- d loss / d actor params (flat, OVERWRITTEN); stats[4] <- {loss,
+ * mean q_sel, mean logp, mean sigma} (device doubles, fixed summation order).  Optional (NULL): d_a (N, AF) = -g / N, logp_out (N,),
+ * sel_out (N,) bytes, actions_out (N, AF).  A row's outputs depend on that row alone and are the same bits in every call.  No weight
+ * gradient, column sum or gradient buffer of the critic is written. */
+int64_t dppo_calql_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N);
+int dppo_calql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
+                             const void* actor_packed, const float* q_params, const void* q1_packed, const void* q2_packed,
+                             const dppo_sac_cfg* cfg, const dppo_idql_batch* batch, int obs_dim, int64_t N, const float* noise,
+                             const double* alpha, float* actor_grad, double* stats, float* d_a, float* logp_out, uint8_t* sel_out,
+                             float* actions_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
 
 #ifdef __cplusplus
 }
