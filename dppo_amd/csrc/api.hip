@@ -16,6 +16,7 @@
 #include "sac.h"
 #include "rlpd.h"
 #include "calql.h"
+#include "ibrl.h"
 #include "unet.h"
 #include "sampler.h"
 
@@ -420,6 +421,8 @@ struct MlpBufs {  // activations of one network for M rows
   void* dz1_all[MAX_BLOCKS];
   float* ln_stats;               // [nb][2][M][2] LayerNorm row statistics (training); a plain trunk uses [nb + 1][M][2] of it
   float* ln_part;                // plain trunk with LayerNorm, backward: [ln_bwd_blocks(M)][2][H] partial parameter sums
+  float* ln_dz32[2];             // plain trunk with LayerNorm, backward, or null (carve_mlp leaves them null): [M][H] fp32 each; the data
+                                 // GEMMs then hand LayerNorm's backward its input unrounded (ibrl.h)
   const void* dh0_final;         // where the last backward left d loss / d h_0
   void* w0T;                     // [cond_dim][H] elem: layer 0's observation columns, transposed (obs_grad)
   float* dobs;                   // [M][round_up(cond_dim, 16)]: obs_grad's GEMM output (the epilogue stores 16-column groups)
@@ -567,10 +570,13 @@ static void cond_encode(const dppo_net_desc& d, const float* prm, const char* pk
 
 template <class P>
 static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
-                        MlpBufs<P>& B, bool keep, hipStream_t s, const LossArgs* fuse_loss = nullptr, bool layered = false) {
+                        MlpBufs<P>& B, bool keep, hipStream_t s, const LossArgs* fuse_loss = nullptr, bool layered = false,
+                        const dppo_dropout* drop = nullptr) {
   // fuse_loss: the policy half of the PPO loss in the forward kernel's epilogue (fuse_loss_ok() held: the merged fused kernel runs)
   // layered: the GEMM path even where the fused kernels cover the shape (the caller's backward reads the layered path's
   // derivative sources: dql_impl)
+  // drop: dropout behind every hidden layer of a plain trunk without LayerNorm (ibrl.h; the entry checked the descriptor); null, or
+  // p = 0 without a given mask, is the path without it, launch for launch
   const ParamLayout pl = param_layout(d);
   const int H = d.hidden, nb = d.n_blocks;
   if (fuse_loss != nullptr && !(fused_ok<P>(d) && B.route.merged)) {
@@ -621,8 +627,19 @@ static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk
       ln.stats = keep ? B.ln_stats : nullptr;
       q.out_act = q.out_pre = nullptr, q.out_f32 = B.h[0], q.ldo32 = H;
     }
+    // dropout (ibrl.h) takes the same route: the unrounded row in B.h[.], then the row kernel in the epilogue's place
+    const bool dropping = drop != nullptr && !d.use_layernorm && (drop->p > 0.f || drop->mask != nullptr);
+    DropRows dr;
+    memset(&dr, 0, sizeof(dr));
+    if (dropping) {
+      dr.M = M, dr.H = H, dr.act = d.act, dr.ldx = H, dr.ldo = H, dr.p = drop->p, dr.scale = 1.f / (1.f - drop->p);
+      dr.k0 = drop->seed_lo, dr.k1 = drop->seed_hi, dr.mask = drop->mask, dr.mask_out = drop->mask_out;
+      dr.x = B.h[0], dr.layer = 0, dr.out_act = q.out_act, dr.out_z = q.out_pre;
+      q.out_act = q.out_pre = nullptr, q.out_f32 = B.h[0], q.ldo32 = H;
+    }
     launch_gemm_nt<P>(q, s);
     if (d.use_layernorm) launch_ln_rows<P>(ln, s);
+    if (dropping) launch_drop_rows<P>(dr, s);
     for (int b = 0; b < nb; ++b) {
       memset(&q, 0, sizeof(q));
       q.M = (int)M, q.N = H, q.Kp = H, q.ldx = H, q.ldw = H, q.ldo = H, q.act = d.act;
@@ -633,8 +650,13 @@ static void mlp_forward(const dppo_net_desc& d, const float* prm, const char* pk
         ln.stats = keep ? B.ln_stats + (size_t)(b + 1) * M * 2 : nullptr;
         q.out_act = q.out_pre = nullptr, q.out_f32 = B.h[b + 1], q.ldo32 = H;
       }
+      if (dropping) {
+        dr.x = B.h[b + 1], dr.layer = b + 1, dr.out_act = q.out_act, dr.out_z = q.out_pre;
+        q.out_act = q.out_pre = nullptr, q.out_f32 = B.h[b + 1], q.ldo32 = H;
+      }
       launch_gemm_nt<P>(q, s);
       if (d.use_layernorm) launch_ln_rows<P>(ln, s);
+      if (dropping) launch_drop_rows<P>(dr, s);
     }
     memset(&q, 0, sizeof(q));
     q.M = (int)M, q.N = d.out_dim, q.Kp = H, q.ldx = H, q.ldw = H;
@@ -1143,6 +1165,11 @@ static void backward_plain(const dppo_net_desc& d, const float* prm, const char*
   memset(&q, 0, sizeof(q));
   q.M = (int)M, q.N = H, q.Kp = L.Kpo, q.ldx = L.Kpo, q.ldw = L.Kpo, q.ldo = H;
   q.X = B.d_out, q.W = pk + L.WoutT, q.dsrc = B.z1[nb - 1], q.dsrc_kind = 2, q.dsrc_ld = H, q.dact = d.act, q.out_pre = B.dh;
+  // wide: upstream (.) act'(z) reaches LayerNorm's backward in fp32 (ibrl.h); its in-place output is the elem row either way
+  const bool wide = d.use_layernorm && B.ln_dz32[0] != nullptr;
+  float* dz32 = B.ln_dz32[0];
+  float* other32 = B.ln_dz32[1];
+  if (wide) q.out_pre = nullptr, q.out_f32 = dz32, q.ldo32 = H;
   launch_gemm_nt<P>(q, s);
   void* dz = B.dh;
   void* other = B.dz1;
@@ -1152,7 +1179,7 @@ static void backward_plain(const dppo_net_desc& d, const float* prm, const char*
   ln.ld = H, ln.ldx = H, ln.M = M, ln.H = H, ln.partial = B.ln_part;
   for (int b = nb - 1; b >= 0; --b) {
     if (d.use_layernorm) {
-      ln.dz = dz, ln.x = B.h[b + 1], ln.stats = B.ln_stats + (size_t)(b + 1) * M * 2, ln.gamma = prm + pl.n1w[b];
+      ln.dz = dz, ln.dz32 = wide ? dz32 : nullptr, ln.x = B.h[b + 1], ln.stats = B.ln_stats + (size_t)(b + 1) * M * 2, ln.gamma = prm + pl.n1w[b];
       ln.dgamma = grad + pl.n1w[b], ln.dbeta = grad + pl.n1b[b];
       launch_ln_bwd<P>(ln, s);
     }
@@ -1162,12 +1189,15 @@ static void backward_plain(const dppo_net_desc& d, const float* prm, const char*
     q.M = (int)M, q.N = H, q.Kp = H, q.ldx = H, q.ldw = H, q.ldo = H;
     q.X = dz, q.W = pk + L.W1T[b], q.dsrc = b == 0 ? B.hpre[0] : B.z1[b - 1], q.dsrc_kind = 2, q.dsrc_ld = H, q.dact = d.act;
     q.out_pre = other;
+    if (wide) q.out_pre = nullptr, q.out_f32 = other32, q.ldo32 = H;
     launch_gemm_nt<P>(q, s);
     void* t = dz;
     dz = other, other = t;
+    float* t32 = dz32;
+    dz32 = other32, other32 = t32;
   }
   if (d.use_layernorm) {
-    ln.dz = dz, ln.x = B.h[0], ln.stats = B.ln_stats, ln.gamma = prm + pl.n0w, ln.dgamma = grad + pl.n0w, ln.dbeta = grad + pl.n0b;
+    ln.dz = dz, ln.dz32 = wide ? dz32 : nullptr, ln.x = B.h[0], ln.stats = B.ln_stats, ln.gamma = prm + pl.n0w, ln.dgamma = grad + pl.n0w, ln.dbeta = grad + pl.n0b;
     launch_ln_bwd<P>(ln, s);
   }
   weight_grad<P>(dz, H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s);
@@ -2047,7 +2077,8 @@ int64_t dppo_gaussian_workspace_bytes(const dppo_net_desc* actor, const dppo_net
 template <class P>
 static int gauss_infer_impl(const dppo_net_desc& d, const float* prm, const char* pk, const dppo_gaussian_cfg& cfg,
                             const float* logvar, const float* obs, const float* noise, const float* actions, int64_t N,
-                            float* out_actions, float* out_mean, float* out_logp, void* ws, int64_t wsb, hipStream_t s) {
+                            float* out_actions, float* out_mean, float* out_logp, void* ws, int64_t wsb, hipStream_t s,
+                            const dppo_dropout* drop = nullptr) {
   Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> A, Cb;
   double *m, *sc, *pa;
@@ -2055,7 +2086,7 @@ static int gauss_infer_impl(const dppo_net_desc& d, const float* prm, const char
   if (!ws || (int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
   const PackLayout L = pack_layout<P>(d, 0);
   launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, d.cond_dim, N, A.in, L.Kp0, s);
-  mlp_forward<P>(d, prm, pk, L, N, A, false, s);
+  mlp_forward<P>(d, prm, pk, L, N, A, false, s, nullptr, false, drop);
   GaussArgs g;
   memset(&g, 0, sizeof(g));
   g.cfg = cfg, g.mean_pre = A.out, g.ldm = A.ldout, g.logvar = logvar, g.N = N, g.AF = d.out_dim;
@@ -2079,6 +2110,34 @@ int dppo_gaussian_sample(const dppo_net_desc* actor, int prec, const float* para
 #define CALL(P)                                                                                                        \
   gauss_infer_impl<P>(*actor, params, (const char*)packed, *cfg, logvar, obs, noise, nullptr, B, actions, mean_out, nullptr, \
                       workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+// ---- dropout in a plain trunk's forward (ibrl.h) ---------------------------------------------------------------------------------
+static int check_drop_actor(const dppo_net_desc* actor) {
+  if (int e = check_net(actor)) return e;
+  if (actor->kind != 1 || !actor->plain || actor->use_layernorm)
+    return fail(-1, "dropout runs in a plain kind-1 trunk without LayerNorm only (kind = 1, plain = 1, use_layernorm = 0)");
+  return 0;
+}
+static int check_dropout(const dppo_dropout* drop) {
+  if (!drop) return fail(-1, "null pointer: the dropout struct");
+  if (!(drop->p >= 0.f && drop->p < 1.f)) return fail(-1, "dropout p=%g outside [0, 1)", (double)drop->p);
+  return 0;
+}
+int dppo_gaussian_sample_drop(const dppo_net_desc* actor, int prec, const float* params, const void* packed,
+                              const dppo_gaussian_cfg* cfg, const float* logvar, const float* obs, const float* noise, int64_t B,
+                              float* actions, float* mean_out, const dppo_dropout* drop, void* workspace, int64_t workspace_bytes,
+                              dppo_stream_t stream) {
+  if (int e = check_drop_actor(actor)) return e;
+  if (int e = check_gauss(actor, cfg, logvar)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (int e = check_dropout(drop)) return e;
+  if (!params || !packed || !obs || !actions) return fail(-1, "null pointer");
+  if (B < 1 || B > 0x7fffffff) return fail(-1, "B out of range");
+#define CALL(P)                                                                                                        \
+  gauss_infer_impl<P>(*actor, params, (const char*)packed, *cfg, logvar, obs, noise, nullptr, B, actions, mean_out, nullptr, \
+                      workspace, workspace_bytes, (hipStream_t)stream, drop)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }
@@ -3203,6 +3262,237 @@ int dppo_rlpd_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const floa
   rlpd_td_impl<P>(*q, E, q_params, q_packed, target_q_params, (const char*)target_q_packed[pair0], (const char*)target_q_packed[pair1], \
                   pair0, pair1, *batch, obs_dim, next_actions, next_logp, alpha, N, gamma, q_grad, stats, workspace, workspace_bytes, \
                   (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+// ---- IBRL (ibrl.hip): acting through two proposals, and the ensemble's TD loss with the better of them as bootstrap ----------------
+static int check_ibrl_pair(int pair0, int pair1, int E) {
+  if (pair0 < 0 || pair0 >= E || pair1 < 0 || pair1 >= E || pair0 == pair1)
+    return fail(-1, "pair (%d, %d): two different members of [0, %d) are needed", pair0, pair1, E);
+  return 0;
+}
+template <class P>
+struct IbrlActWs {
+  MlpBufs<P> A[2], Q[2];  // the BC and the RL actor over B rows, the pair's members over 2B
+  float *a_bc, *a_rl, *q_bc, *q_rl;
+  uint8_t* took;
+};
+template <class P>
+static size_t carve_ibrl_act(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t B, IbrlActWs<P>& W) {
+  W.a_bc = (float*)c.take((size_t)B * a.out_dim * 4);
+  W.a_rl = (float*)c.take((size_t)B * a.out_dim * 4);
+  W.q_bc = (float*)c.take((size_t)B * 4);
+  W.q_rl = (float*)c.take((size_t)B * 4);
+  W.took = (uint8_t*)c.take((size_t)B);
+  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, a, B, false, false, W.A[i]);
+  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, q, 2 * B, false, false, W.Q[i]);
+  return al256(c.off);
+}
+static int check_ibrl_act_nets(const dppo_net_desc* actor, const dppo_net_desc* q, int E) {
+  if (int e = check_drop_actor(actor)) return e;
+  if (int e = check_rlpd_q(q, actor ? actor->cond_dim : 0, E)) return e;
+  if (q->in_dim != actor->cond_dim + actor->out_dim)
+    return fail(-1, "Q descriptor does not pair with the actor: in_dim=%d must be cond_dim=%d + Ta*Da=%d", q->in_dim, actor->cond_dim,
+                actor->out_dim);
+  return 0;
+}
+int64_t dppo_ibrl_act_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int64_t B) {
+  if (check_ibrl_act_nets(actor, q, 2) || check_prec(prec)) return -1;
+  if (B < 1 || B > 0x3fffffff) return fail(-1, "B out of range");
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    IbrlActWs<decltype(p)> W;
+    return carve_ibrl_act<decltype(p)>(c, *actor, *q, B, W);
+  });
+}
+template <class P>
+static int ibrl_act_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float* bcp, const char* bck, const float* rlp,
+                         const char* rlk, dppo_gaussian_cfg cfg_bc, const dppo_gaussian_cfg& cfg_rl, const dppo_dropout* drop_bc,
+                         const dppo_dropout* drop_rl, const float* qp0, const char* qk0, const float* qp1, const char* qk1,
+                         const float* obs, const float* noise_bc, const float* noise_rl, int64_t B, const IbrlSelect& sel_in,
+                         float* a_bc_out, float* a_rl_out, float* q_bc_out, float* q_rl_out, uint8_t* took_out, void* ws, int64_t wsb,
+                         hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  IbrlActWs<P> W;
+  const size_t need = carve_ibrl_act<P>(c, a, q, B, W);
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const int AF = a.out_dim, OD = a.cond_dim;
+  float* abc = a_bc_out ? a_bc_out : W.a_bc;
+  float* arl = a_rl_out ? a_rl_out : W.a_rl;
+  // both actors read one image of the observation rows
+  launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, OD, B, W.A[0].in, LA.Kp0, s);
+  W.A[1].in = W.A[0].in;
+  cfg_bc.deterministic = 1;                       // sigma 1e-4, and the draw all the same
+  const float* prm[2] = {bcp, rlp};
+  const char* pk[2] = {bck, rlk};
+  const dppo_gaussian_cfg* cfg[2] = {&cfg_bc, &cfg_rl};
+  const dppo_dropout* drop[2] = {drop_bc, drop_rl};
+  const float* noise[2] = {noise_bc, noise_rl};
+  float* out[2] = {abc, arl};
+  hipStream_t st = fork_side(s, 0);  // the BC actor beside the online one, then one member beside the other (ibrl.h: measured at B = 1)
+  for (int i = 0; i < 2; ++i) {
+    hipStream_t si = i == 0 ? st : s;
+    mlp_forward<P>(a, prm[i], pk[i], LA, B, W.A[i], false, si, nullptr, false, drop[i]);
+    GaussArgs g;
+    memset(&g, 0, sizeof(g));
+    g.cfg = *cfg[i], g.mean_pre = W.A[i].out, g.ldm = W.A[i].ldout, g.N = B, g.AF = AF;
+    g.noise = noise[i], g.out_actions = out[i];
+    launch_gauss_sample(g, si);
+  }
+  join_side(s, st, 0);
+  IbrlRows r;
+  memset(&r, 0, sizeof(r));
+  r.ring.next_obs = obs, r.ring.obs_mod = B, r.ring.N = B, r.ring.OD = OD, r.ring.AD = AF;
+  r.a_bc = abc, r.a_rl = arl, r.tin = W.Q[0].in, r.Kp = LQ.Kp0;
+  launch_ibrl_rows<P>(r, s);
+  W.Q[1].in = W.Q[0].in;
+  st = fork_side(s, 0);
+  mlp_forward<P>(q, qp1, qk1, LQ, 2 * B, W.Q[1], false, st);
+  mlp_forward<P>(q, qp0, qk0, LQ, 2 * B, W.Q[0], false, s);
+  join_side(s, st, 0);
+  IbrlSelect sel = sel_in;
+  sel.q1 = W.Q[0].out, sel.q2 = W.Q[1].out, sel.ldq = W.Q[0].ldout, sel.N = B, sel.AF = AF, sel.a_bc = abc, sel.a_rl = arl;
+  sel.q_bc = q_bc_out ? q_bc_out : W.q_bc, sel.q_rl = q_rl_out ? q_rl_out : W.q_rl, sel.took_bc = took_out ? took_out : W.took;
+  launch_ibrl_select(sel, s);
+  return check_launch();
+}
+int dppo_ibrl_act(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int E, const float* bc_params, const void* bc_packed,
+                  const float* rl_params, const void* rl_packed, const dppo_gaussian_cfg* cfg_bc, const dppo_gaussian_cfg* cfg_rl,
+                  const dppo_dropout* drop_bc, const dppo_dropout* drop_rl, const float* q_params, const void* const* q_packed,
+                  int pair0, int pair1, const float* obs, const float* noise_bc, const float* noise_rl, int64_t B, int soft,
+                  double beta, const float* u, uint32_t seed_lo, uint32_t seed_hi, float* actions, float* a_bc_out, float* a_rl_out,
+                  float* q_bc_out, float* q_rl_out, uint8_t* took_bc_out, void* workspace, int64_t workspace_bytes,
+                  dppo_stream_t stream) {
+  if (int e = check_ibrl_act_nets(actor, q, E)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (int e = check_gauss(actor, cfg_bc, nullptr)) return e;
+  if (int e = check_gauss(actor, cfg_rl, nullptr)) return e;
+  if (cfg_bc->std_mode != 0 || cfg_rl->std_mode != 0) return fail(-1, "IBRL's actors have a fixed std (std_mode 0)");
+  if (drop_bc)
+    if (int e = check_dropout(drop_bc)) return e;
+  if (drop_rl)
+    if (int e = check_dropout(drop_rl)) return e;
+  if (!bc_params || !bc_packed || !rl_params || !rl_packed || !q_params || !q_packed || !obs || !actions || !workspace)
+    return fail(-1, "null pointer");
+  if (int e = check_ibrl_pair(pair0, pair1, E)) return e;
+  if (!q_packed[pair0] || !q_packed[pair1]) return fail(-1, "null pointer: kernel image of a member of the pair");
+  if (B < 1 || B > 0x3fffffff) return fail(-1, "B out of range");
+  if (!(beta == beta)) return fail(-1, "soft_action_sample_beta is NaN");
+  IbrlSelect sel;
+  memset(&sel, 0, sizeof(sel));
+  sel.soft = soft != 0, sel.beta = (float)beta, sel.u = u, sel.k0 = seed_lo, sel.k1 = seed_hi, sel.action = actions;
+  const int64_t nq = param_layout(*q).total;
+#define CALL(P)                                                                                                                     \
+  ibrl_act_impl<P>(*actor, *q, bc_params, (const char*)bc_packed, rl_params, (const char*)rl_packed, *cfg_bc, *cfg_rl, drop_bc,     \
+                   drop_rl, q_params + pair0 * nq, (const char*)q_packed[pair0], q_params + pair1 * nq,                             \
+                   (const char*)q_packed[pair1], obs, noise_bc, noise_rl, B, sel, a_bc_out, a_rl_out, q_bc_out, q_rl_out,           \
+                   took_bc_out, workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+// The TD loss: rlpd_td_impl's sequence with the targets over 2N rows and ibrl.h's target kernel in front of RLPD's loss.  A sibling
+// and no split of rlpd_td_impl: the members' part is the same calls in the same order on the same streams, and RLPD's is left alone.
+template <class P>
+struct IbrlTdWs {
+  MlpBufs<P> Q[RLPD_MAX_E], T[2];
+  double* partial;
+  float *r, *term, *tq;
+  uint32_t* won;
+  double* share;
+};
+template <class P>
+static size_t carve_ibrl_td(Carver& c, const dppo_net_desc& q, int64_t N, int E, IbrlTdWs<P>& W) {
+  W.partial = (double*)c.take((size_t)E * rlpd_blocks(N) * 4 * sizeof(double));
+  W.r = (float*)c.take((size_t)N * 4);
+  W.term = (float*)c.take((size_t)N * 4);
+  W.tq = (float*)c.take((size_t)N * 4);
+  W.won = (uint32_t*)c.take((size_t)ibrl_target_blocks(N) * 4);
+  W.share = (double*)c.take(sizeof(double));
+  for (int e = 0; e < E; ++e) {
+    carve_mlp<P>(c, q, N, true, true, W.Q[e]);
+    // bf16: the rows that enter LayerNorm's backward stay in fp32 (ibrl.h); in fp32 the elem rows are that already
+    if (P::ESIZE == 2)
+      for (int i = 0; i < 2; ++i) W.Q[e].ln_dz32[i] = (float*)c.take((size_t)N * q.hidden * 4);
+  }
+  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, q, 2 * N, false, false, W.T[i]);
+  return al256(c.off);
+}
+int64_t dppo_ibrl_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
+  if (check_rlpd_q(q, obs_dim, E) || check_prec(prec)) return -1;
+  if (N < 1 || N > 0x3fffffff) return fail(-1, "N out of range");
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    IbrlTdWs<decltype(p)> W;
+    return carve_ibrl_td<decltype(p)>(c, *q, N, E, W);
+  });
+}
+template <class P>
+static int ibrl_td_impl(const dppo_net_desc& q, int E, const float* qp, const void* const* qk, const float* tp, const char* tk1,
+                        const char* tk2, int p0, int p1, const dppo_idql_batch& b, int OD, const float* next_bc, const float* next_rl,
+                        int64_t N, double gamma, float* qgrad, double* stats, float* y_out, double* bc_share, void* ws, int64_t wsb,
+                        hipStream_t s) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  IbrlTdWs<P> W;
+  const size_t need = carve_ibrl_td<P>(c, q, N, E, W);
+  const int64_t q_stride = W.Q[1].out - W.Q[0].out, d_stride = (char*)W.Q[1].d_out - (char*)W.Q[0].d_out;
+  bool even = true;
+  for (int e = 1; e < E; ++e) even = even && W.Q[e].out - W.Q[0].out == e * q_stride && (char*)W.Q[e].d_out - (char*)W.Q[0].d_out == e * d_stride;
+  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (!even) return fail(-1, "members' workspaces are not evenly spaced");
+  const PackLayout L = pack_layout<P>(q, 0);
+  const int64_t nq = param_layout(q).total;
+  IbrlRows r;
+  memset(&r, 0, sizeof(r));
+  r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
+  r.a_bc = next_bc, r.a_rl = next_rl, r.qin = W.Q[0].in, r.tin = W.T[0].in, r.Kp = L.Kp0, r.r_out = W.r, r.term_out = W.term;
+  launch_ibrl_rows<P>(r, s);
+  for (int e = 1; e < E; ++e) W.Q[e].in = W.Q[0].in;
+  W.T[1].in = W.T[0].in;
+  hipStream_t st[4] = {s, fork_side(s, 0), fork_side(s, 1), fork_side(s, 2)};
+  mlp_forward<P>(q, tp + p0 * nq, tk1, L, 2 * N, W.T[0], false, st[1]);
+  mlp_forward<P>(q, tp + p1 * nq, tk2, L, 2 * N, W.T[1], false, st[2]);
+  for (int e = 0; e < E; ++e) mlp_forward<P>(q, qp + e * nq, (const char*)qk[e], L, N, W.Q[e], true, st[(e + 3) & 3]);
+  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
+  IbrlTarget t;
+  memset(&t, 0, sizeof(t));
+  t.t1 = W.T[0].out, t.t2 = W.T[1].out, t.ldt = W.T[0].ldout, t.N = N, t.tq = W.tq, t.reward = W.r, t.terminated = W.term;
+  t.gamma = (float)gamma, t.y_out = y_out, t.partial = W.won, t.share = bc_share ? bc_share : W.share;
+  launch_ibrl_target(t, s);
+  RlpdLoss l;
+  memset(&l, 0, sizeof(l));
+  l.q = W.Q[0].out, l.q_stride = q_stride, l.ldq = W.Q[0].ldout, l.t1 = l.t2 = W.tq, l.ldt = 1;
+  l.reward = W.r, l.terminated = W.term, l.gamma = (float)gamma, l.N = N, l.E = E;
+  l.d_out = W.Q[0].d_out, l.d_stride = d_stride, l.ldd = L.Kpo, l.partial = W.partial, l.stats = stats;
+  launch_rlpd_loss<P>(l, s);
+  for (int i = 1; i < 4; ++i) st[i] = fork_side(s, i - 1);
+  for (int e = 0; e < E; ++e)
+    mlp_backward<P>(q, qp + e * nq, (const char*)qk[e], L, N, W.Q[e], qgrad + e * nq, nullptr, nullptr, 0, st[e & 3]);
+  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
+  launch_rlpd_out_bias(W.partial, N, E, qgrad, nq, param_layout(q).bout, s);
+  return check_launch();
+}
+int dppo_ibrl_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const float* q_params, const void* const* q_packed,
+                             const float* target_q_params, const void* const* target_q_packed, int pair0, int pair1,
+                             const dppo_idql_batch* batch, int obs_dim, const float* next_actions_bc, const float* next_actions_rl,
+                             int64_t N, double gamma, float* q_grad, double* stats, float* y_out, double* bc_share, void* workspace,
+                             int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_rlpd_q(q, obs_dim, E)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (!q_params || !q_packed || !target_q_params || !target_q_packed || !next_actions_bc || !next_actions_rl || !q_grad || !stats ||
+      !workspace)
+    return fail(-1, "null pointer");
+  if (int e = check_ibrl_pair(pair0, pair1, E)) return e;
+  for (int e = 0; e < E; ++e)
+    if (!q_packed[e]) return fail(-1, "null pointer: kernel image of member %d", e);
+  if (!target_q_packed[pair0] || !target_q_packed[pair1]) return fail(-1, "null pointer: kernel image of a target member of the pair");
+  if (N < 1 || N > 0x3fffffff) return fail(-1, "N out of range");
+  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
+#define CALL(P)                                                                                                                      \
+  ibrl_td_impl<P>(*q, E, q_params, q_packed, target_q_params, (const char*)target_q_packed[pair0], (const char*)target_q_packed[pair1], \
+                  pair0, pair1, *batch, obs_dim, next_actions_bc, next_actions_rl, N, gamma, q_grad, stats, y_out, bc_share,         \
+                  workspace, workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }

@@ -38,9 +38,10 @@ build "$HERE/dql.hip" -ffp-contract=off
 build "$HERE/sac.hip" -ffp-contract=off
 build "$HERE/rlpd.hip" -ffp-contract=off
 build "$HERE/calql.hip" -ffp-contract=off
+build "$HERE/ibrl.hip" -ffp-contract=off
 build "$HERE/unet.hip" -ffp-contract=off
 build "$HERE/vision.hip"
 build "$HERE/api.hip"
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIB" "$OBJ"/gemm.o "$OBJ"/fused.o "$OBJ"/sampler.o "$OBJ"/sampler_split.o "$OBJ"/ppo.o "$OBJ"/gaussian.o "$OBJ"/gmm.o "$OBJ"/idql.o "$OBJ"/qsm.o "$OBJ"/dql.o "$OBJ"/sac.o "$OBJ"/rlpd.o "$OBJ"/calql.o "$OBJ"/unet.o "$OBJ"/vision.o "$OBJ"/api.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIB" "$OBJ"/gemm.o "$OBJ"/fused.o "$OBJ"/sampler.o "$OBJ"/sampler_split.o "$OBJ"/ppo.o "$OBJ"/gaussian.o "$OBJ"/gmm.o "$OBJ"/idql.o "$OBJ"/qsm.o "$OBJ"/dql.o "$OBJ"/sac.o "$OBJ"/rlpd.o "$OBJ"/calql.o "$OBJ"/ibrl.o "$OBJ"/unet.o "$OBJ"/vision.o "$OBJ"/api.o
 echo "built $OUT/$LIB"

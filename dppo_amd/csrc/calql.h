@@ -47,7 +47,7 @@
 //   + 1 tail / head backward + 1 statistics (bf16: + 2 for the heads' bias gradient from the unrounded d_out)
 //   + the actor's parameter backward.  Nothing of the critic's is written: no weight gradient, column sum or gradient buffer.
 //   Shipped kitchen (L = 3): 2 + 3 + 1 + 2 x 7 + 1 + 2 x 5 + 2 = 33 before the actor's backward.
-// Not built: a member-batched or fused twin chain, IBRL.
+// Not built: a member-batched or fused twin chain.  (IBRL's model and critic loss: ibrl.h.)
 #pragma once
 #include "rlpd.h"
 

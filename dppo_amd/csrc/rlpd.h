@@ -38,7 +38,7 @@
 //   + 1 tail / head backward + 1 statistics (bf16: + 2 for the heads' bias gradient from the unrounded d_out)
 //   + the actor's parameter backward.  Nothing of a critic's is written: no weight gradient, column sum or gradient buffer.
 //   Shipped halfcheetah (E = 10, L = 2): 4 + 3 + 10 x 5 + 10 x 4 + 2 = 99 before the actor's backward.
-// Not built: a member-batched GEMM, weight gradients grouped across members, IBRL.  (Cal-QL: calql.h; its actor runs this file's
+// Not built: a member-batched GEMM, weight gradients grouped across members.  (IBRL's model and critic loss: ibrl.h; Cal-QL: calql.h; its actor runs this file's
 // chain from a seed of its own: rlpd_chain_from_seed in api.hip.)
 //
 // Launches of one forward of a trunk: L x (1 GEMM + 1 row kernel) + 1 GEMM.
@@ -69,6 +69,7 @@ constexpr int LN_MAX_H = 1024;   // a lane keeps its columns' parameter sums in 
 struct LnBwd {
   void* dz;  // [M][ld] elem.  In: upstream (.) act'(z).  Out (in place; a lane reads an element before it writes it): d loss / d x
   int ld;
+  const float* dz32;  // [M][ld] fp32 or null: the input read from here, unrounded, instead of from dz (ibrl.h); the output still goes to dz
   const float* x;  // [M][ldx] fp32: the pre-LayerNorm rows the forward's GEMM left
   int ldx;
   const float* stats;  // [M][2] {mean, rstd}

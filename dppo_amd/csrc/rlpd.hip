@@ -123,7 +123,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd a) {
       const int c = 4 * lane + 256 * k;
       if (c < a.H) {
         float dz[4];
-        load4<P>((const E*)a.dz + row * a.ld + c, dz);
+        if (a.dz32 != nullptr) {  // (kernel-uniform)
+          const float4 t = *(const float4*)(a.dz32 + row * a.ld + c);
+          dz[0] = t.x, dz[1] = t.y, dz[2] = t.z, dz[3] = t.w;
+        } else {
+          load4<P>((const E*)a.dz + row * a.ld + c, dz);
+        }
         const float4 xv = *(const float4*)(a.x + row * a.ldx + c);
         const float x4[4] = {xv.x, xv.y, xv.z, xv.w};
 #pragma unroll

@@ -116,7 +116,13 @@ class CalqlCfg(C.Structure):  # struct dppo_calql_cfg
                 ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
 
 
+class Dropout(C.Structure):  # struct dppo_dropout
+    _fields_ = [("p", C.c_float), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("pad", C.c_int32), ("mask", C.c_void_p),
+                ("mask_out", C.c_void_p)]
+
+
 IDQL_STAT_COUNT = 3
+RLPD_MAX_E = 16  # csrc/rlpd.h
 CALQL_STAT_COUNT = 6
 DQL_STAT_COUNT = 5
 SAC_STAT_COUNT = 4
@@ -233,6 +239,16 @@ SYMBOLS = {
     "dppo_calql_actor_workspace_bytes": (_L, [_ND, _ND, _I, _I, _L]),
     "dppo_calql_actor_fwd_bwd": (_I, [_ND, _ND, _I, _P, _P, _P, _P, _P, C.POINTER(SacCfg), C.POINTER(IdqlBatch), _I, _L, _P, _P, _P,
                                       _P, _P, _P, _P, _P, _P, _L, _P]),
+    # IBRL: dropout in a plain actor, the Q-guided choice between two proposals, the ensemble's TD loss (csrc/ibrl.hip)
+    "dppo_gaussian_sample_drop": (_I, [_ND, _I, _P, _P, C.POINTER(GaussianCfg), _P, _P, _P, _L, _P, _P, C.POINTER(Dropout), _P, _L,
+                                       _P]),
+    "dppo_ibrl_act_workspace_bytes": (_L, [_ND, _ND, _I, _L]),
+    "dppo_ibrl_act": (_I, [_ND, _ND, _I, _I, _P, _P, _P, _P, C.POINTER(GaussianCfg), C.POINTER(GaussianCfg), C.POINTER(Dropout),
+                           C.POINTER(Dropout), _P, C.POINTER(C.c_void_p), _I, _I, _P, _P, _P, _L, _I, _D, _P, C.c_uint32, C.c_uint32,
+                           _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "dppo_ibrl_q_loss_workspace_bytes": (_L, [_ND, _I, _I, _L, _I]),
+    "dppo_ibrl_q_loss_fwd_bwd": (_I, [_ND, _I, _I, _P, C.POINTER(C.c_void_p), _P, C.POINTER(C.c_void_p), _I, _I, C.POINTER(IdqlBatch), _I,
+                                      _P, _P, _L, _D, _P, _P, _P, _P, _P, _L, _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

@@ -45,8 +45,11 @@ class GaussianModel(torch.nn.Module):
         ``.backward()``, and the flat d loss / d trunk parameters stays in ``last_loss_grad`` (d loss / d logvar in
         ``last_logvar_grad``) for callers that step a flat optimiser."""
         state = cond["state"]
-        hip.require_gpu(state, type(self).__name__ + ".loss")
         net = self.network
+        if getattr(net, "plain_fixed_std", False):
+            raise NotImplementedError("dppo_amd: behaviour cloning of the plain fixed-std actor (IBRL's pre-training, with the "
+                                      "backward through dropout) is not built")
+        hip.require_gpu(state, type(self).__name__ + ".loss")
         if getattr(net, "is_vision", False):
             raise NotImplementedError("dppo_amd: supervised pre-training of the pixel Gaussian policy is not built")
         B, dev = len(true_action), state.device
@@ -75,8 +78,35 @@ class GaussianModel(torch.nn.Module):
             params, views = params + [net.logvar], views + [lv_grad]
         return _FusedDenoiseLoss.apply(out[0], views, *params), {"entropy": out[1].float()}
 
+    def _dropout_of(self, net, B, dev, drop_mask=None, want_mask=False):
+        """(struct or None, tensors to keep alive, the mask buffer written or None): the per-call dropout of ``net``'s trunk
+        (csrc/ibrl.h), live iff ``net.training`` and ``net.dropout > 0`` as in torch.  ``drop_mask`` (L, B, H) uint8, 1 = keep,
+        replaces the draw; ``want_mask`` has the mask used written out."""
+        p = float(getattr(net, "dropout", 0.0))
+        if not (net.training and p > 0):
+            if drop_mask is not None:
+                raise ValueError("drop_mask given, but this actor's dropout is off (eval() or dropout = 0)")
+            return None, (), None
+        d = net.net_desc()
+        shape = (d.n_blocks + 1, B, d.hidden)
+        drop = hip.Dropout(p=p, seed_lo=0, seed_hi=0, pad=0, mask=None, mask_out=None)
+        keep, out = [], None
+        if drop_mask is not None:
+            if tuple(drop_mask.shape) != shape:
+                raise ValueError(f"drop_mask must be {shape} (hidden layers, rows, hidden), got {tuple(drop_mask.shape)}")
+            m = drop_mask.to(device=dev, dtype=torch.uint8).contiguous()
+            drop.mask = m.data_ptr()
+            keep.append(m)
+        else:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
+            drop.seed_lo, drop.seed_hi = seed & 0xFFFFFFFF, seed >> 32
+        if want_mask:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+            drop.mask_out = out.data_ptr()
+        return drop, keep, out
+
     @torch.no_grad()
-    def _sample(self, net, cond, deterministic, noise=None, want_mean=False):
+    def _sample(self, net, cond, deterministic, noise=None, want_mean=False, drop_mask=None, want_mask=False):
         state = cond["state"]
         hip.require_gpu(state, type(self).__name__ + ".forward")
         B, dev = state.shape[0], state.device
@@ -93,15 +123,25 @@ class GaussianModel(torch.nn.Module):
         mean = torch.empty(B, AF, device=dev) if want_mean else None
         wsb = lib.dppo_gaussian_workspace_bytes(C.byref(d), None, self.prec, B)
         ws = self._ws_g.get(wsb, dev)
+        drop, keep, mask_out = self._dropout_of(net, B, dev, drop_mask, want_mask)
+        if drop is not None:  # dropout live in the trunk (IBRL's actors in train())
+            hip.check(lib.dppo_gaussian_sample_drop(
+                C.byref(d), self.prec, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(), C.byref(cfg),
+                net.logvar_ptr(), obs.data_ptr(), hip.ptr(noise), B, actions.data_ptr(), hip.ptr(mean), C.byref(drop), ws.data_ptr(),
+                ws.numel(), hip.stream()), "dppo_gaussian_sample_drop")
+            object.__setattr__(self, "last_drop_mask", mask_out)
+            return actions.view(B, self.horizon_steps, -1), mean
         hip.check(lib.dppo_gaussian_sample(
             C.byref(d), self.prec, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(), C.byref(cfg),
             net.logvar_ptr(), obs.data_ptr(), hip.ptr(noise), B, actions.data_ptr(), hip.ptr(mean), ws.data_ptr(), ws.numel(),
             hip.stream()), "dppo_gaussian_sample")
         return actions.view(B, self.horizon_steps, -1), mean
 
-    def forward(self, cond, deterministic=False, network_override=None, reparameterize=False, get_logprob=False, noise=None):
-        """cond {"state": (B,To,Do)} -> sampled action chunk (B,Ta,Da) (reference :94-121)."""
+    def forward(self, cond, deterministic=False, network_override=None, reparameterize=False, get_logprob=False, noise=None,
+                drop_mask=None):
+        """cond {"state": (B,To,Do)} -> sampled action chunk (B,Ta,Da) (reference :94-121).  ``drop_mask`` (L, B, H) uint8 hands a
+        recorded dropout mask to an actor whose dropout is live (``_dropout_of``)."""
         if get_logprob or reparameterize:
             raise NotImplementedError("dppo_amd: get_logprob / reparameterize (SAC-style use) are out of scope")
         net = network_override if network_override is not None else self.network
-        return self._sample(net, cond, deterministic, noise)[0]
+        return self._sample(net, cond, deterministic, noise, drop_mask=drop_mask)[0]

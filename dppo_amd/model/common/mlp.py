@@ -66,14 +66,20 @@ class MLP(nn.Module):
     reference mlp.py:27-81.  Built for one hidden width (a multiple of 64), at least two hidden layers, no dropout / appended
     inputs; runs on the library's layered GEMM path (``NetDesc.plain = 1``).  ``use_layernorm`` puts ``norm_1 =
     nn.LayerNorm(o_dim)`` (eps 1e-5) behind every Linear but the last, in front of the activation (reference mlp.py:56-58); the
-    library reads such a trunk as a critic only, forward only (csrc/rlpd.h), so the owners that cannot run it refuse it."""
+    library reads such a trunk as a critic only, forward only (csrc/rlpd.h), so the owners that cannot run it refuse it.
+    ``dropout`` in (0, 1), without LayerNorm, puts ``dropout_1 = nn.Dropout(p)`` at the same place (reference mlp.py:59-60): it has no
+    parameters, so the state dict is unchanged; the library applies it in the forward only (csrc/ibrl.h), and the owners that
+    cannot run it (everything but IBRL's actor) refuse it."""
 
     def __init__(self, dim_list: List[int], activation_type: str = "Tanh", out_activation_type: str = "Identity",
                  use_layernorm: bool = False, use_layernorm_final: bool = False, dropout: float = 0, append_dim: int = 0,
                  append_layers=None, use_drop_final: bool = False, verbose: bool = False):
         super().__init__()
-        if use_layernorm_final or dropout or append_dim:
-            raise NotImplementedError("dppo_amd: plain MLP with a final LayerNorm / dropout / appended inputs is not built")
+        if use_layernorm_final or append_dim or use_drop_final or (dropout and use_layernorm):
+            raise NotImplementedError("dppo_amd: plain MLP with a final LayerNorm / dropout behind LayerNorm or the last layer / "
+                                      "appended inputs is not built")
+        if not 0 <= dropout < 1:
+            raise ValueError(f"dropout probability has to be in [0, 1), got {dropout}")
         if out_activation_type != "Identity":
             raise NotImplementedError("dppo_amd: only out_activation_type='Identity' is built")
         if activation_type not in SUPPORTED_ACT:
@@ -87,10 +93,13 @@ class MLP(nn.Module):
             layer.linear_1 = nn.Linear(dim_list[i], dim_list[i + 1])
             if use_layernorm and i < len(dim_list) - 2:
                 layer.norm_1 = nn.LayerNorm(dim_list[i + 1])
+            if dropout > 0 and i < len(dim_list) - 2:
+                layer.dropout_1 = nn.Dropout(dropout)
             self.moduleList.append(layer)
         self.hidden, self.n_blocks = hidden, len(dim_list) - 3  # hidden-to-hidden layers
         self.in_dim, self.out_dim = dim_list[0], dim_list[-1]
         self.act, self.use_layernorm, self.plain = SUPPORTED_ACT[activation_type], int(bool(use_layernorm)), 1
+        self.dropout = float(dropout)
 
 
 class HipNet(nn.Module):

@@ -6,9 +6,11 @@ fused trunk kernels); this class owns parameters only.
 
 Built: ``residual_style=True`` with ``fixed_std`` given -- the d3il / furniture fine-tuning cfgs (7 of the 10 shipped
 PPO_Gaussian cfgs) -- and the SAC actor: the state-dependent ``mlp_logvar`` head on a plain ``MLP`` base (``fixed_std=None``,
-``tanh_output=False``, ``residual_style=False``; reference :304-321, 370-379).  Not built (raises): the state-dependent head
-with ``tanh_output=True`` (walker2d pre-training, the three gym ``scratch`` PPO cfgs: no BC / PPO loss exists for it) and plain
-(non-residual) trunks with a fixed std.
+``tanh_output=False``, ``residual_style=False``; reference :304-321, 370-379), and IBRL's actor: a fixed std on a plain ``MLP``
+trunk, with dropout behind every hidden Linear where the cfg asks for it, under the keyword ``plain_fixed_std=True`` (which
+``IBRL_Gaussian``'s cfg node sets): sampling only, no BC / PPO loss.  Not built (raises): the state-dependent head with
+``tanh_output=True`` (walker2d pre-training, the three gym ``scratch`` PPO cfgs: no BC / PPO loss exists for it) and plain
+(non-residual) trunks with a fixed std outside that keyword.
 """
 from __future__ import annotations
 
@@ -18,15 +20,20 @@ import torch
 from torch import nn
 
 from dppo_amd import hip
-from dppo_amd.model.common.mlp import SUPPORTED_ACT, HipNet, ResidualMLP
+from dppo_amd.model.common.mlp import MLP, SUPPORTED_ACT, HipNet, ResidualMLP
 from dppo_amd.model.common.vit import VisionMixin
 
 
 class Gaussian_MLP(HipNet):
     def __init__(self, action_dim, horizon_steps, cond_dim, mlp_dims=[256, 256, 256], activation_type="Mish",
                  tanh_output=True, residual_style=False, use_layernorm=False, dropout=0.0, fixed_std=None,
-                 learn_fixed_std=False, std_min=0.01, std_max=1, precision="bf16"):
+                 learn_fixed_std=False, std_min=0.01, std_max=1, precision="bf16", plain_fixed_std=False):
         super().__init__()
+        self.plain_fixed_std, self.dropout = False, 0.0
+        if plain_fixed_std:
+            self._init_plain_fixed_std(action_dim, horizon_steps, cond_dim, list(mlp_dims), activation_type, tanh_output,
+                                       residual_style, use_layernorm, dropout, fixed_std, learn_fixed_std, std_min, std_max, precision)
+            return
         if fixed_std is None and (tanh_output or residual_style):
             raise NotImplementedError("dppo_amd: Gaussian_MLP with a state-dependent logvar head (fixed_std=None) is built for "
                                       "tanh_output=False on a plain trunk only (the SAC actor); no BC / PPO loss exists for it")
@@ -49,6 +56,26 @@ class Gaussian_MLP(HipNet):
         self.logvar_max = nn.Parameter(torch.log(torch.tensor(std_max ** 2)), requires_grad=False)
         self.use_fixed_std, self.fixed_std, self.learn_fixed_std = True, fixed_std, learn_fixed_std
         self.tanh_output = tanh_output
+        self.prec = hip.PREC_BY_NAME[precision]
+        self._cache_clamp_bounds()
+
+    def _init_plain_fixed_std(self, action_dim, horizon_steps, cond_dim, mlp_dims, activation_type, tanh_output, residual_style,
+                              use_layernorm, dropout, fixed_std, learn_fixed_std, std_min, std_max, precision):
+        """IBRL's actor (reference :323-329 with ``residual_style=False``): ``mlp_mean`` = plain [cond] + mlp_dims + [Ta*Da],
+        names ``mlp_mean.moduleList.{i}.linear_1.*``, a tanh mean per ``tanh_output``, a fixed std, ``nn.Dropout(dropout)`` behind
+        every hidden Linear.  The library samples from it (``dppo_gaussian_sample_drop``, ``dppo_ibrl_act``); nothing trains it yet."""
+        if fixed_std is None or residual_style:
+            raise NotImplementedError("dppo_amd: plain_fixed_std is the plain (residual_style=False) trunk with fixed_std given")
+        if use_layernorm or learn_fixed_std:
+            raise NotImplementedError("dppo_amd: plain_fixed_std is built without LayerNorm and without a learned std "
+                                      "(no shipped IBRL cfg sets either)")
+        self.action_dim, self.horizon_steps, self.cond_dim = action_dim, horizon_steps, cond_dim
+        self.mlp_mean = MLP([cond_dim] + mlp_dims + [action_dim * horizon_steps], activation_type=activation_type,
+                            out_activation_type="Identity", dropout=dropout)
+        self.logvar_min = nn.Parameter(torch.log(torch.tensor(std_min ** 2)), requires_grad=False)
+        self.logvar_max = nn.Parameter(torch.log(torch.tensor(std_max ** 2)), requires_grad=False)
+        self.use_fixed_std, self.fixed_std, self.learn_fixed_std = True, fixed_std, False
+        self.tanh_output, self.plain_fixed_std, self.dropout = tanh_output, True, float(dropout)
         self.prec = hip.PREC_BY_NAME[precision]
         self._cache_clamp_bounds()
 
@@ -138,6 +165,8 @@ class Gaussian_MLP(HipNet):
         import ctypes as C
         if not self.use_fixed_std:
             raise NotImplementedError("dppo_amd: the state-dependent head is evaluated inside SAC_Gaussian (dppo_sac_sample)")
+        if self.plain_fixed_std and self.training and self.dropout > 0:
+            raise NotImplementedError("dppo_amd: a dropout actor in train() is sampled through GaussianModel (its mask is per call)")
         state = cond["state"]
         hip.require_gpu(state, "Gaussian_MLP.forward")
         B = state.shape[0]

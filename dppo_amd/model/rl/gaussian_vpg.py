@@ -13,6 +13,8 @@ from dppo_amd.model.common.gaussian import GaussianModel
 
 class VPG_Gaussian(GaussianModel):
     def __init__(self, actor, critic, **kwargs):
+        if getattr(actor, "plain_fixed_std", False):
+            raise NotImplementedError("dppo_amd: policy-gradient fine-tuning of the plain fixed-std actor (IBRL's) is not built")
         super().__init__(network=actor, **kwargs)
         self.critic = critic.to(self.device)
         self.actor_ft = actor

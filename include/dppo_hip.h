@@ -1032,6 +1032,58 @@ int dppo_calql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q,
                              const double* alpha, float* actor_grad, double* stats, float* d_a, float* logp_out, uint8_t* sel_out,
                              float* actions_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
 
+/* ---- IBRL: dropout actors, Q-guided choice between two proposals, the ensemble's TD loss (csrc/ibrl.h) ----------------------------
+ * Dropout of one forward of a PLAIN trunk without LayerNorm (reference model/common/mlp.py:59-60: nn.Dropout behind every Linear but
+ * the last, in front of the activation): z' = keep ? z * (1 / (1 - p)) : 0 in fp32, then the activation.  keep of hidden layer l, row
+ * m, feature h is mask[(l M + m) H + h] != 0 where a mask is given (uint8 [L][M][H], L = n_blocks + 1 hidden layers, M the call's
+ * rows); otherwise Philox4x32-10 keyed by (seed_lo, seed_hi) at counter (l M + m) H + h: keep iff (first word >> 8) * 2^-24 >= p.
+ * mask_out (or NULL) receives the mask used, [L][M][H].  0 <= p < 1.  A NULL struct pointer, or p = 0 without a mask, is the forward
+ * without dropout, launch for launch. */
+typedef struct dppo_dropout {
+  float p;
+  uint32_t seed_lo, seed_hi;
+  int32_t pad;
+  const uint8_t* mask;
+  uint8_t* mask_out;
+} dppo_dropout;
+/* dppo_gaussian_sample with dropout in the trunk (the workspace is dppo_gaussian_workspace_bytes').  Refuses anything but a plain
+ * kind-1 trunk without LayerNorm. */
+int dppo_gaussian_sample_drop(const dppo_net_desc* actor, int prec, const float* params, const void* packed,
+                              const dppo_gaussian_cfg* cfg, const float* logvar, const float* obs, const float* noise, int64_t B,
+                              float* actions, float* mean_out, const dppo_dropout* drop, void* workspace, int64_t workspace_bytes,
+                              dppo_stream_t stream);
+/* IBRL_Gaussian.forward (reference model/rl/gaussian_ibrl.py:149-205) in one call.  Both actors share the descriptor (a plain
+ * fixed-std trunk) and read obs (B, cond); cfg_bc is read with sigma = 1e-4 whatever its `deterministic` says (the reference samples
+ * its frozen policy "deterministically" and still draws).  noise_bc / noise_rl (B, Ta*Da) or NULL: Philox keyed by the cfg's seed.
+ * drop_bc / drop_rl or NULL: no dropout in that actor.  q: the LayerNorm descriptor dppo_rlpd_q_loss_fwd_bwd accepts; q_params [E][P]
+ * flat fp32, q_packed[E] kernel images, of which the members pair0 != pair1 are read.  Each scores the 2B rows [obs | a_bc | 0],
+ * [obs | a_rl | 0] in one forward; q_bc = min over the pair (torch.min: a NaN wins), q_rl likewise.  Per row:
+ *   soft == 0:  BC iff q_bc > q_rl (strict: a tie or a NaN takes RL)
+ *   soft != 0:  w = exp((float)beta * q), p_bc = 1 / (1 + exp(w_rl - w_bc)) in fp32, BC iff u < p_bc; u (B,) or NULL: Philox keyed by
+ *               (seed_lo, seed_hi), counter = row, (first word >> 8) * 2^-24.  Where w_rl - w_bc is NaN the rule of soft == 0 decides.
+ * actions (B, Ta*Da) <- the chosen proposal's bits.  Optional (NULL): a_bc_out, a_rl_out (B, Ta*Da), q_bc_out, q_rl_out (B,),
+ * took_bc_out (B,) bytes. */
+int64_t dppo_ibrl_act_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int64_t B);
+int dppo_ibrl_act(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int E, const float* bc_params, const void* bc_packed,
+                  const float* rl_params, const void* rl_packed, const dppo_gaussian_cfg* cfg_bc, const dppo_gaussian_cfg* cfg_rl,
+                  const dppo_dropout* drop_bc, const dppo_dropout* drop_rl, const float* q_params, const void* const* q_packed,
+                  int pair0, int pair1, const float* obs, const float* noise_bc, const float* noise_rl, int64_t B, int soft,
+                  double beta, const float* u, uint32_t seed_lo, uint32_t seed_hi, float* actions, float* a_bc_out, float* a_rl_out,
+                  float* q_bc_out, float* q_rl_out, uint8_t* took_bc_out, void* workspace, int64_t workspace_bytes,
+                  dppo_stream_t stream);
+/* IBRL_Gaussian.loss_critic (reference :69-113): dppo_rlpd_q_loss_fwd_bwd's argument list with TWO next-action samples, the frozen
+ * imitation policy's and the target actor's, both (N, Ta*Da), and no entropy term.  With t_i, t_j the pair's target members:
+ *   mb = min(t_i, t_j)(next_obs, next_actions_bc),  mr = min(t_i, t_j)(next_obs, next_actions_rl),  tq = mb > mr ? mb : mr
+ *   y = reward + ((float)gamma * (1 - terminated)) * tq,   loss = mean over E N of (q_e(obs, actions) - y)^2
+ * q_grad <- d loss / d params of all E members, [E][P] (OVERWRITTEN); stats[3] <- {loss, mean q, mean y}.  Optional (NULL): y_out
+ * (N,), bc_share (one device double: the share of rows with mb > mr). */
+int64_t dppo_ibrl_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E);
+int dppo_ibrl_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const float* q_params, const void* const* q_packed,
+                             const float* target_q_params, const void* const* target_q_packed, int pair0, int pair1,
+                             const dppo_idql_batch* batch, int obs_dim, const float* next_actions_bc, const float* next_actions_rl,
+                             int64_t N, double gamma, float* q_grad, double* stats, float* y_out, double* bc_share, void* workspace,
+                             int64_t workspace_bytes, dppo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
