@@ -26,13 +26,10 @@ Deviations from the reference:
 """
 from __future__ import annotations
 
-import time
-
 import numpy as np
 import torch
 
 from dppo_amd.agent.finetune.train_off_policy_agent import OffPolicyAgent
-from dppo_amd.agent.finetune.train_sac_agent import TrainSACAgent
 from dppo_amd.cfg.loader import instantiate
 from dppo_amd.util.optim import FlatAdamW
 from dppo_amd.util.replay import ReturnsReplay
@@ -50,8 +47,8 @@ class TrainCalQLAgent(OffPolicyAgent):
     nets = ("network", "critic", "target_critic")
     log_line = "loss actor %8.4f | loss critic %8.4f | reward %8.4f | alpha %8.4f | t %8.4f"
     log_keys = ("loss_actor", "loss_critic", "train_episode_reward", "alpha", "time")
-    _explore_action = TrainSACAgent._explore_action
     replay_cls = ReturnsReplay  # a sixth column: the reward-to-go, written when an episode closes
+    strictly_past_exploration = ()
 
     def __init__(self, cfg, venv=None):
         super().__init__(cfg, venv, "Cal-QL")
@@ -129,70 +126,31 @@ class TrainCalQLAgent(OffPolicyAgent):
             loss_t = lt.detach()
         return loss_c, loss_a, loss_t
 
-    def run(self):
-        model, dev = self.model, self.device
-        E = self.n_envs
-        t_start = time.time()
-        run_results = []
-        cnt_train_step = 0
-        done_venv = np.zeros(E, dtype=bool)
-        prev_obs = None
+    # ------------------------------------------------------------------------------------------------- the loop's Cal-QL parts
+    def _begin_rollout(self, eval_mode):
+        """An evaluation and an online rollout end by their episode count; offline training does not step the env (:160-165)."""
+        self._first_episode_steps = None  # of the first training episode that finishes in this iteration
+        return int(1e5) if eval_mode or self.train_online else 0
+
+    def _rollout_done(self, eval_mode, cnt_episode):
+        return cnt_episode >= (self.n_eval_episode if eval_mode else self.n_episode_per_epoch)
+
+    def _after_train_step(self, reward, done_venv):
+        """The open episode's UNSCALED rewards (deviation 4); when it closes, its returns go into its own transitions' slots."""
+        self._open_rewards.append(float(np.asarray(reward).reshape(-1)[0]))
+        if done_venv[0]:
+            self.replay.close_episode(discounted_returns(self._open_rewards, self.gamma))
+            if self._first_episode_steps is None:
+                self._first_episode_steps = len(self._open_rewards)
+            self._open_rewards = []
+
+    def _update(self):
+        """(:301-445) online as many updates as the first episode finished in the iteration had steps, offline ``num_update``."""
         losses = None
-        open_rewards = []  # the open training episode's UNSCALED rewards (deviation 4): its returns are formed when it closes
-        while self.itr < self.n_train_itr:
-            eval_mode = self.itr % self.val_freq == 0 and self.itr >= self.n_explore_steps and not self.force_train
-            # an evaluation and an online rollout end by their episode count; offline training does not step the env (:160-165)
-            n_steps = int(1e5) if eval_mode or self.train_online else 0
-            model.eval() if eval_mode else model.train()
-            firsts, rewards = [np.zeros(E)], []
-            if self.reset_at_iteration or eval_mode or self.itr == 0 or prev_obs is None:
-                prev_obs = self.reset_env_all()
-                firsts[0] = np.ones(E)
-            else:
-                firsts[0] = done_venv.astype(np.float64)
-            cnt_episode = 0
-            first_episode_steps = None  # of the first training episode that finished in this iteration
-            # ---------------- rollout (:180-241)
-            for step in range(n_steps):
-                state = torch.from_numpy(prev_obs["state"]).float().to(dev)
-                if self.itr < self.n_explore_steps:
-                    action = self._explore_action()
-                else:
-                    action = model(cond={"state": state}, deterministic=eval_mode).cpu().numpy()[:, :self.act_steps]
-                prev_obs, reward, done_venv = self.env_step(state, action, action, eval_mode)
-                rewards.append(np.asarray(reward, dtype=np.float64))
-                firsts.append(done_venv.astype(np.float64))
-                if not eval_mode:
-                    cnt_train_step += E * self.act_steps
-                    open_rewards.append(float(np.asarray(reward).reshape(-1)[0]))
-                    if done_venv[0]:  # the returns of the episode that just closed go into its own transitions' slots
-                        self.replay.close_episode(discounted_returns(open_rewards, self.gamma))
-                        if first_episode_steps is None:
-                            first_episode_steps = len(open_rewards)
-                        open_rewards = []
-                cnt_episode += int(np.sum(done_venv))
-                if eval_mode and cnt_episode >= self.n_eval_episode:
-                    break
-                if not eval_mode and cnt_episode >= self.n_episode_per_epoch:
-                    break
-            stats = self._episode_stats(np.stack(firsts), np.stack(rewards) if rewards else np.zeros((0, E)))
-            # ---------------- update (:301-445)
-            if not eval_mode and self.itr >= self.n_explore_steps:
-                num_update = (first_episode_steps or 0) if self.train_online else self.num_update
-                for _ in range(num_update):
-                    losses = self.update_iteration()
-            # ---------------- schedules, checkpoint, logging (:447-503)
-            for name in self.lr_schedulers:
-                getattr(self, name).step()
-            if self.itr % self.save_model_freq == 0 or self.itr == self.n_train_itr - 1:
-                self.save_model()
-            rec = {"itr": self.itr, "step": cnt_train_step}
-            if self.itr % self.log_freq == 0 and self.itr >= self.n_explore_steps:
-                fields = {}
-                if not eval_mode and losses is not None:  # the only device reads of the loop, on logging iterations
-                    fields.update(loss_actor=float(losses[1]), loss_critic=float(losses[0]), alpha=float(self.log_alpha.detach().exp()))
-                self.log_record(run_results, rec, t_start, eval_mode, stats, fields)
-            else:
-                run_results.append(rec)
-            self.itr += 1
-        return run_results
+        for _ in range((self._first_episode_steps or 0) if self.train_online else self.num_update):
+            losses = self.update_iteration()
+        return losses
+
+    def run(self):
+        self._open_rewards = []  # of the open training episode, which may span iterations: its returns are formed when it closes
+        return self.run_by_episode_count()

@@ -1,11 +1,13 @@
-"""What the off-policy fine-tuning agents share (IDQL, QSM, DQL, SAC): the reference's ``TrainAgent`` set-up, the device-resident
-replay ring, one env step with its ``final_obs`` bootstrap and ring append, the episode statistics, the checkpoint, the logging
-tail, and the iteration of the replay-ratio agents (IDQL, QSM, DQL).  SAC's iteration is structured differently and stays in
-train_sac_agent.py; it uses the env step and the logging tail from here.
+"""What the off-policy fine-tuning agents share (IDQL, QSM, DQL, SAC, RLPD, Cal-QL): the reference's ``TrainAgent`` set-up, the
+device-resident replay ring, one env step with its ``final_obs`` bootstrap and ring append, the episode statistics, the checkpoint,
+the logging tail, the iteration of the replay-ratio agents (IDQL, QSM, DQL) as ``run``, and that of the agents which explore at
+random first and evaluate by an episode count (SAC, RLPD, Cal-QL) as ``run_by_episode_count``.
 
 A replay-ratio agent supplies its hyper-parameters and optimisers, ``nets`` and ``update_minibatch``; the defaults of
 ``lr_schedulers``, ``log_line`` / ``log_keys``, ``_sample`` (how an action is drawn) and ``_metrics`` (the logged fields from the
-last minibatch's losses) are those of an agent with one actor and one critic optimiser (QSM, DQL).
+last minibatch's losses) are those of an agent with one actor and one critic optimiser (QSM, DQL).  An episode-count agent
+supplies ``update_iteration`` (or its own ``_update``), ``log_alpha``, ``n_explore_steps`` and ``n_eval_episode``; what else differs
+between the three is the handful of small methods in front of ``run_by_episode_count``.
 """
 from __future__ import annotations
 
@@ -219,5 +221,96 @@ class OffPolicyAgent:
                 self.save_model()
             if self.itr % self.log_freq == 0:
                 self.log_record(run_results, {"itr": self.itr, "step": cnt_train_step}, t_start, eval_mode, stats, metrics)
+            self.itr += 1
+        return run_results
+
+    # ------------------------------------------------------------------------------------------------- SAC, RLPD, Cal-QL
+    # Which of "eval", "update" and "log" wait for ``itr > n_explore_steps``; the others start at ``itr >= n_explore_steps``.  (The
+    # reference's agents differ: SAC has ``>`` in all three tests, RLPD in the log line's only, Cal-QL in none.)
+    strictly_past_exploration = ("log",)
+
+    def _explore_action(self):
+        """Uniformly random actions (reference SAC :121-122): the env's own ``action_space.sample()`` where it has one."""
+        space = getattr(self.venv, "action_space", None)
+        if space is not None:
+            return np.asarray(space.sample(), dtype=np.float32).reshape(self.n_envs, self.act_steps, self.action_dim)
+        return np.random.uniform(-1.0, 1.0, size=(self.n_envs, self.act_steps, self.action_dim)).astype(np.float32)
+
+    def _begin_rollout(self, eval_mode):
+        """Called once in front of an iteration's rollout; -> the most env steps it may take (an evaluation ends by its episode
+        count)."""
+        return int(1e5) if eval_mode else self.n_steps
+
+    def _rollout_done(self, eval_mode, cnt_episode):
+        """Whether the rollout ends behind a step that brought the finished episodes to ``cnt_episode``."""
+        return eval_mode and cnt_episode >= self.n_eval_episode
+
+    def _after_train_step(self, reward, done_venv):
+        """Behind every training step's ring append."""
+
+    def _update(self):
+        """A training iteration's update past the exploration phase; -> (critic loss, actor loss or None, ...) as device scalars,
+        or None where no update was due."""
+        return self.update_iteration()
+
+    def run_by_episode_count(self):
+        """The iteration of the agents whose evaluation ends by an episode count and whose first ``n_explore_steps`` iterations
+        act at random (the reference's SAC, RLPD and Cal-QL agents): rollout, ``_update()``, schedules, checkpoint, record."""
+        model, dev = self.model, self.device
+        E = self.n_envs
+        X, strict = self.n_explore_steps, self.strictly_past_exploration
+        past = lambda what: self.itr > X if what in strict else self.itr >= X
+        t_start = time.time()
+        run_results = []
+        cnt_train_step = 0
+        done_venv = np.zeros(E, dtype=bool)
+        prev_obs = None
+        losses = None
+        while self.itr < self.n_train_itr:
+            eval_mode = self.itr % self.val_freq == 0 and past("eval") and not self.force_train
+            model.eval() if eval_mode else model.train()
+            firsts, rewards = [np.zeros(E)], []
+            if self.reset_at_iteration or eval_mode or prev_obs is None:
+                prev_obs = self.reset_env_all()
+                firsts[0] = np.ones(E)
+            else:
+                firsts[0] = done_venv.astype(np.float64)
+            cnt_episode = 0
+            # ---------------- rollout
+            for step in range(self._begin_rollout(eval_mode)):
+                state = torch.from_numpy(prev_obs["state"]).float().to(dev)
+                if self.itr < self.n_explore_steps:
+                    action = self._explore_action()
+                else:
+                    action = model(cond={"state": state}, deterministic=eval_mode).cpu().numpy()[:, :self.act_steps]
+                prev_obs, reward, done_venv = self.env_step(state, action, action, eval_mode)
+                rewards.append(np.asarray(reward, dtype=np.float64))
+                firsts.append(done_venv.astype(np.float64))
+                if not eval_mode:
+                    cnt_train_step += E * self.act_steps
+                    self._after_train_step(reward, done_venv)
+                cnt_episode += int(np.sum(done_venv))
+                if self._rollout_done(eval_mode, cnt_episode):
+                    break
+            stats = self._episode_stats(np.stack(firsts), np.stack(rewards) if rewards else np.zeros((0, E)))
+            # ---------------- update
+            if not eval_mode and past("update"):
+                new = self._update()
+                losses = losses if new is None else new
+            # ---------------- schedules, checkpoint, logging
+            for name in self.lr_schedulers:
+                getattr(self, name).step()
+            if self.itr % self.save_model_freq == 0 or self.itr == self.n_train_itr - 1:
+                self.save_model()
+            rec = {"itr": self.itr, "step": cnt_train_step}
+            if self.itr % self.log_freq == 0 and past("log"):
+                fields = {}
+                if not eval_mode and losses is not None:  # the only device reads of the loop, on logging iterations
+                    fields.update(loss_critic=float(losses[0]), alpha=float(self.log_alpha.detach().exp()))
+                    if losses[1] is not None:  # (SAC: no actor update yet)
+                        fields["loss_actor"] = float(losses[1])
+                self.log_record(run_results, rec, t_start, eval_mode, stats, fields)
+            else:
+                run_results.append(rec)
             self.itr += 1
         return run_results

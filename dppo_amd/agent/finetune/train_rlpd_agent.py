@@ -16,13 +16,10 @@ copies and leaves ``critic_networks`` at their initial values: model/rl/gaussian
 """
 from __future__ import annotations
 
-import time
-
 import numpy as np
 import torch
 
 from dppo_amd.agent.finetune.train_off_policy_agent import OffPolicyAgent
-from dppo_amd.agent.finetune.train_sac_agent import TrainSACAgent
 from dppo_amd.cfg.loader import instantiate
 from dppo_amd.util.optim import FlatAdamW
 
@@ -31,7 +28,6 @@ class TrainRLPDAgent(OffPolicyAgent):
     nets = ("network", "_ens", "_tens")  # the actor and both ensembles: load() refreshes every kernel image
     log_line = "loss actor %8.4f | loss critic %8.4f | reward %8.4f | alpha %8.4f | t %8.4f"
     log_keys = ("loss_actor", "loss_critic", "train_episode_reward", "alpha", "time")
-    _explore_action = TrainSACAgent._explore_action
 
     def __init__(self, cfg, venv=None):
         super().__init__(cfg, venv, "RLPD")
@@ -94,57 +90,4 @@ class TrainRLPDAgent(OffPolicyAgent):
         self.log_alpha_optimizer.step()
         return loss_c, loss_a, lt.detach()
 
-    def run(self):
-        model, dev = self.model, self.device
-        E = self.n_envs
-        t_start = time.time()
-        run_results = []
-        cnt_train_step = 0
-        done_venv = np.zeros(E, dtype=bool)
-        prev_obs = None
-        losses = None
-        while self.itr < self.n_train_itr:
-            eval_mode = self.itr % self.val_freq == 0 and self.itr >= self.n_explore_steps and not self.force_train
-            n_steps = self.n_steps if not eval_mode else int(1e5)  # an evaluation ends by its episode count
-            model.eval() if eval_mode else model.train()
-            firsts, rewards = [np.zeros(E)], []
-            if self.reset_at_iteration or eval_mode or self.itr == 0 or prev_obs is None:
-                prev_obs = self.reset_env_all()
-                firsts[0] = np.ones(E)
-            else:
-                firsts[0] = done_venv.astype(np.float64)
-            cnt_episode = 0
-            # ---------------- rollout (:154-207)
-            for step in range(n_steps):
-                state = torch.from_numpy(prev_obs["state"]).float().to(dev)
-                if self.itr < self.n_explore_steps:
-                    action = self._explore_action()
-                else:
-                    action = model(cond={"state": state}, deterministic=eval_mode).cpu().numpy()[:, :self.act_steps]
-                prev_obs, reward, done_venv = self.env_step(state, action, action, eval_mode)
-                rewards.append(np.asarray(reward, dtype=np.float64))
-                firsts.append(done_venv.astype(np.float64))
-                if not eval_mode:
-                    cnt_train_step += E * self.act_steps
-                cnt_episode += int(np.sum(done_venv))
-                if eval_mode and cnt_episode >= self.n_eval_episode:
-                    break
-            stats = self._episode_stats(np.stack(firsts), np.stack(rewards))
-            # ---------------- update (:246-347)
-            if not eval_mode and self.itr >= self.n_explore_steps:
-                losses = self.update_iteration()
-            # ---------------- schedules, checkpoint, logging (:349-404)
-            for name in self.lr_schedulers:
-                getattr(self, name).step()
-            if self.itr % self.save_model_freq == 0 or self.itr == self.n_train_itr - 1:
-                self.save_model()
-            rec = {"itr": self.itr, "step": cnt_train_step}
-            if self.itr % self.log_freq == 0 and self.itr > self.n_explore_steps:
-                fields = {}
-                if not eval_mode and losses is not None:  # the only device reads of the loop, on logging iterations
-                    fields.update(loss_actor=float(losses[1]), loss_critic=float(losses[0]), alpha=float(self.log_alpha.detach().exp()))
-                self.log_record(run_results, rec, t_start, eval_mode, stats, fields)
-            else:
-                run_results.append(rec)
-            self.itr += 1
-        return run_results
+    run = OffPolicyAgent.run_by_episode_count  # (:154-404) with its defaults

@@ -12,8 +12,6 @@ device float64 tensor stepped by ``torch.optim.Adam``.  State observations only,
 """
 from __future__ import annotations
 
-import time
-
 import numpy as np
 import torch
 
@@ -25,6 +23,8 @@ class TrainSACAgent(OffPolicyAgent):
     nets = ("network", "critic", "target_critic")
     log_line = "loss actor %8.4f | loss critic %8.4f | reward %8.4f | alpha %8.4f | t %8.4f"
     log_keys = ("loss_actor", "loss_critic", "train_episode_reward", "alpha", "time")
+    lr_schedulers = ()  # (:21-68 builds none)
+    strictly_past_exploration = ("eval", "update", "log")
 
     def __init__(self, cfg, venv=None):
         super().__init__(cfg, venv, "SAC")
@@ -41,13 +41,6 @@ class TrainSACAgent(OffPolicyAgent):
                                       requires_grad=True)
         self.target_entropy = cfg.train.target_entropy
         self.log_alpha_optimizer = torch.optim.Adam([self.log_alpha], lr=cfg.train.critic_lr)
-
-    def _explore_action(self):
-        """Uniformly random actions (:121-122): the env's own ``action_space.sample()`` where it has one."""
-        space = getattr(self.venv, "action_space", None)
-        if space is not None:
-            return np.asarray(space.sample(), dtype=np.float32).reshape(self.n_envs, self.act_steps, self.action_dim)
-        return np.random.uniform(-1.0, 1.0, size=(self.n_envs, self.act_steps, self.action_dim)).astype(np.float32)
 
     # -------------------------------------------------------------------------------------------------
     def update_minibatch(self, inds, update_actor=True, next_actions=None, next_logp=None, sample_noise=None, actor_noise=None,
@@ -78,59 +71,12 @@ class TrainSACAgent(OffPolicyAgent):
                 loss_t = lt.detach()
         return loss_c, loss_a, loss_t
 
-    def run(self):
-        model, dev = self.model, self.device
-        E = self.n_envs
-        t_start = time.time()
-        run_results = []
-        cnt_train_step = 0
-        done_venv = np.zeros(E, dtype=bool)
-        prev_obs = None
-        losses = None
-        while self.itr < self.n_train_itr:
-            eval_mode = self.itr % self.val_freq == 0 and self.itr > self.n_explore_steps and not self.force_train
-            n_steps = self.n_steps if not eval_mode else int(1e5)  # an evaluation ends by its episode count
-            model.eval() if eval_mode else model.train()
-            firsts, rewards = [np.zeros(E)], []
-            if self.reset_at_iteration or eval_mode or prev_obs is None:
-                prev_obs = self.reset_env_all()
-                firsts[0] = np.ones(E)
-            else:
-                firsts[0] = done_venv.astype(np.float64)
-            cnt_episode = 0
-            # ---------------- rollout (:117-171)
-            for step in range(n_steps):
-                state = torch.from_numpy(prev_obs["state"]).float().to(dev)
-                if self.itr < self.n_explore_steps:
-                    action = self._explore_action()
-                else:
-                    action = model(cond={"state": state}, deterministic=eval_mode).cpu().numpy()[:, :self.act_steps]
-                prev_obs, reward, done_venv = self.env_step(state, action, action, eval_mode)
-                rewards.append(np.asarray(reward, dtype=np.float64))
-                firsts.append(done_venv.astype(np.float64))
-                if not eval_mode:
-                    cnt_train_step += E * self.act_steps
-                cnt_episode += int(np.sum(done_venv))
-                if eval_mode and cnt_episode >= self.n_eval_episode:
-                    break
-            stats = self._episode_stats(np.stack(firsts), np.stack(rewards))
-            # ---------------- update (:209-280)
-            if not eval_mode and self.itr > self.n_explore_steps and self.itr % self.critic_update_freq == 0:
-                inds = np.random.choice(len(self.replay), self.batch_size, replace=False)
-                inds = torch.from_numpy(inds.astype(np.int64)).to(dev)
-                losses = self.update_minibatch(inds, update_actor=self.itr % self.actor_update_freq == 0)
-            # ---------------- checkpoint, logging (:282-335)
-            if self.itr % self.save_model_freq == 0 or self.itr == self.n_train_itr - 1:
-                self.save_model()
-            rec = {"itr": self.itr, "step": cnt_train_step}
-            if self.itr % self.log_freq == 0 and self.itr > self.n_explore_steps:
-                fields = {}
-                if not eval_mode and losses is not None:  # the only device reads of the loop, on logging iterations
-                    fields.update(loss_critic=float(losses[0]), alpha=float(self.log_alpha.detach().exp()))
-                    if losses[1] is not None:
-                        fields["loss_actor"] = float(losses[1])
-                self.log_record(run_results, rec, t_start, eval_mode, stats, fields)
-            else:
-                run_results.append(rec)
-            self.itr += 1
-        return run_results
+    def _update(self):
+        """(:209-280) one critic update every ``critic_update_freq`` iterations, the actor's with it every ``actor_update_freq``."""
+        if self.itr % self.critic_update_freq:
+            return None
+        inds = np.random.choice(len(self.replay), self.batch_size, replace=False)
+        inds = torch.from_numpy(inds.astype(np.int64)).to(self.device)
+        return self.update_minibatch(inds, update_actor=self.itr % self.actor_update_freq == 0)
+
+    run = OffPolicyAgent.run_by_episode_count

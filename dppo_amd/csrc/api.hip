@@ -2729,9 +2729,13 @@ static int check_idql_pair(const dppo_net_desc* q, const dppo_net_desc* v) {
     return fail(-1, "Q / V descriptors do not pair: Q in_dim=%d must be V cond_dim=%d + the action width", q->in_dim, v->cond_dim);
   return 0;
 }
-static int check_idql_batch(const dppo_idql_batch* b, int64_t N, bool need_next) {
+// what of the ring an entry reads, and so what must be non-null: the observations (an actor loss), the stored actions too, or the
+// whole transition (a TD loss)
+enum RingNeed { RING_OBS, RING_ACTIONS, RING_TRANSITION };
+static int check_idql_batch(const dppo_idql_batch* b, int64_t N, RingNeed need) {
   if (!b) return fail(-1, "null batch");
-  if (!b->obs || !b->actions || (need_next && (!b->next_obs || !b->reward || !b->terminated))) return fail(-1, "null pointer in batch");
+  if (!b->obs || (need >= RING_ACTIONS && !b->actions) || (need == RING_TRANSITION && (!b->next_obs || !b->reward || !b->terminated)))
+    return fail(-1, "null pointer in batch");
   if (b->cap < 1 || b->n_envs < 1 || b->count < 1 || b->count > b->cap || b->head < 0 || b->head >= b->cap)
     return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
   if (!b->inds && N > b->count * b->n_envs) return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N,
@@ -2824,7 +2828,7 @@ int dppo_idql_v_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int
       !workspace)
     return fail(-1, "null pointer");
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  if (int e = check_idql_batch(batch, N, false)) return e;
+  if (int e = check_idql_batch(batch, N, RING_ACTIONS)) return e;
   if (!(expectile >= 0.0 && expectile <= 1.0)) return fail(-1, "expectile tau=%g outside [0, 1]", expectile);
 #define CALL(P)                                                                                                                \
   idql_v_impl<P>(*q, *v, target_q_params, (const char*)target_q1_packed, (const char*)target_q2_packed, v_params,              \
@@ -2878,7 +2882,7 @@ int dppo_idql_q_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int
   if (!q_params || !q1_packed || (double_q && !q2_packed) || !v_params || !v_packed || !q_grad || !stats || !workspace)
     return fail(-1, "null pointer");
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (int e = check_idql_batch(batch, N, RING_TRANSITION)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                  \
   idql_q_impl<P>(*q, *v, q_params, (const char*)q1_packed, (const char*)q2_packed, v_params, (const char*)v_packed, *batch, N, gamma, \
@@ -3063,7 +3067,7 @@ int dppo_qsm_actor_target(const dppo_net_desc* q, int prec, const float* q_param
       !obs_out || !workspace)
     return fail(-1, "null pointer");
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  if (int e = check_idql_batch(batch, N, false)) return e;
+  if (int e = check_idql_batch(batch, N, RING_ACTIONS)) return e;
   if (K < 1 || K > 1024) return fail(-1, "K=%d denoising steps outside [1, 1024]", K);
   if (!(coeff >= 0.0 && coeff <= 3.0e38)) return fail(-1, "q_grad_coeff=%g must be finite and >= 0", coeff);
 #define CALL(P)                                                                                                              \
@@ -3154,7 +3158,7 @@ int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
       !q_grad || !stats || !workspace)
     return fail(-1, "null pointer");
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (int e = check_idql_batch(batch, N, RING_TRANSITION)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                \
   twin_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
@@ -3165,45 +3169,88 @@ int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
 }
 
 // ---- RLPD (rlpd.hip): the TD loss of an ensemble of LayerNorm Q trunks -----------------------------------------------------------
-static int check_rlpd_q(const dppo_net_desc* q, int obs_dim, int E) {
+// A plain LayerNorm Q trunk that pairs with obs_dim (RLPD's and IBRL's members, Cal-QL's twin); not_ln: the caller's own message
+static int check_ln_q(const dppo_net_desc* q, int obs_dim, const char* not_ln) {
   if (int e = check_idql_q(q, true)) return e;
-  if (!q->plain || !q->use_layernorm) return fail(-1, "the ensemble's members are plain trunks with LayerNorm (plain = 1, use_layernorm = 1)");
+  if (!q->plain || !q->use_layernorm) return fail(-1, "%s", not_ln);
   if (obs_dim < 1 || obs_dim >= q->in_dim)
     return fail(-1, "Q descriptor does not pair with obs_dim=%d: in_dim=%d must be obs_dim + the action width", obs_dim, q->in_dim);
+  return 0;
+}
+static int check_rlpd_q(const dppo_net_desc* q, int obs_dim, int E) {
+  if (int e = check_ln_q(q, obs_dim, "the ensemble's members are plain trunks with LayerNorm (plain = 1, use_layernorm = 1)")) return e;
   if (E < 2 || E > RLPD_MAX_E) return fail(-1, "E=%d members out of [2, %d]", E, RLPD_MAX_E);
   return 0;
 }
+static int check_member_pair(int pair0, int pair1, int E) {
+  if (pair0 < 0 || pair0 >= E || pair1 < 0 || pair1 >= E || pair0 == pair1)
+    return fail(-1, "pair (%d, %d): two different members of [0, %d) are needed", pair0, pair1, E);
+  return 0;
+}
+static int check_member_images(const void* const* packed, int E) {
+  for (int e = 0; e < E; ++e)
+    if (!packed[e]) return fail(-1, "null pointer: kernel image of member %d", e);
+  return 0;
+}
+// What the ensemble's TD target bootstraps from.  RLPD: the smaller target Q at one next action per row, with the entropy term
+// where next_logp and alpha are set.  IBRL (next_bc set): the better of the two proposals' smaller target Q (ibrl.h's target kernel).
+struct EnsembleBootstrap {
+  const float *next_actions, *next_logp;  // RLPD
+  const double* alpha;
+  const float *next_bc, *next_rl;  // IBRL
+  float* y_out;
+  double* bc_share;
+};
 template <class P>
-struct RlpdTdWs {
+struct EnsembleTdWs {
   MlpBufs<P> Q[RLPD_MAX_E], T[2];
   double* partial;
   float *r, *term;
+  float* tq;  // IBRL only, as the next two
+  uint32_t* won;
+  double* share;
 };
 template <class P>
-static size_t carve_rlpd_td(Carver& c, const dppo_net_desc& q, int64_t N, int E, RlpdTdWs<P>& W) {
+static size_t carve_ensemble_td(Carver& c, const dppo_net_desc& q, int64_t N, int E, bool ibrl, EnsembleTdWs<P>& W) {
   W.partial = (double*)c.take((size_t)E * rlpd_blocks(N) * 4 * sizeof(double));
   W.r = (float*)c.take((size_t)N * 4);
   W.term = (float*)c.take((size_t)N * 4);
-  for (int e = 0; e < E; ++e) carve_mlp<P>(c, q, N, true, true, W.Q[e]);
-  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, q, N, false, false, W.T[i]);
+  W.tq = ibrl ? (float*)c.take((size_t)N * 4) : nullptr;
+  W.won = ibrl ? (uint32_t*)c.take((size_t)ibrl_target_blocks(N) * 4) : nullptr;
+  W.share = ibrl ? (double*)c.take(sizeof(double)) : nullptr;
+  for (int e = 0; e < E; ++e) {
+    carve_mlp<P>(c, q, N, true, true, W.Q[e]);
+    // IBRL in bf16: the rows that enter LayerNorm's backward stay in fp32 (ibrl.h); in fp32 the elem rows are that already
+    if (ibrl && P::ESIZE == 2)
+      for (int i = 0; i < 2; ++i) W.Q[e].ln_dz32[i] = (float*)c.take((size_t)N * q.hidden * 4);
+  }
+  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, q, ibrl ? 2 * N : N, false, false, W.T[i]);  // IBRL: both proposals' rows
   return al256(c.off);
 }
-int64_t dppo_rlpd_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
+static int64_t ensemble_td_ws_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E, bool ibrl) {
   if (check_rlpd_q(q, obs_dim, E) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (N < 1 || N > (ibrl ? 0x3fffffff : 0x7fffffff)) return fail(-1, "N out of range");
   return ws_bytes(prec, [&](Carver& c, auto p) {
-    RlpdTdWs<decltype(p)> W;
-    return carve_rlpd_td<decltype(p)>(c, *q, N, E, W);
+    EnsembleTdWs<decltype(p)> W;
+    return carve_ensemble_td<decltype(p)>(c, *q, N, E, ibrl, W);
   });
 }
+int64_t dppo_rlpd_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
+  return ensemble_td_ws_bytes(q, prec, obs_dim, N, E, false);
+}
+int64_t dppo_ibrl_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
+  return ensemble_td_ws_bytes(q, prec, obs_dim, N, E, true);
+}
+// The TD loss of the E members against the pair (p0, p1) of target members.  RLPD and IBRL differ in four places: the rows, the
+// targets' row count, IBRL's target step in front of the loss, and (in the carve) IBRL's fp32 LayerNorm rows in bf16.
 template <class P>
-static int rlpd_td_impl(const dppo_net_desc& q, int E, const float* qp, const void* const* qk, const float* tp, const char* tk1,
-                        const char* tk2, int p0, int p1, const dppo_idql_batch& b, int OD, const float* next_actions,
-                        const float* next_logp, const double* alpha, int64_t N, double gamma, float* qgrad, double* stats, void* ws,
-                        int64_t wsb, hipStream_t s) {
+static int ensemble_td_impl(const dppo_net_desc& q, int E, const float* qp, const void* const* qk, const float* tp,
+                            const void* const* tk, int p0, int p1, const dppo_idql_batch& b, int OD, const EnsembleBootstrap& bs,
+                            int64_t N, double gamma, float* qgrad, double* stats, void* ws, int64_t wsb, hipStream_t s) {
+  const bool ibrl = bs.next_bc != nullptr;
   Carver c{(char*)ws, 0, (size_t)wsb};
-  RlpdTdWs<P> W;
-  const size_t need = carve_rlpd_td<P>(c, q, N, E, W);
+  EnsembleTdWs<P> W;
+  const size_t need = carve_ensemble_td<P>(c, q, N, E, ibrl, W);
   // every member's buffers sit at one stride: the loss kernel reaches member e's from member 0's
   const int64_t q_stride = W.Q[1].out - W.Q[0].out, d_stride = (char*)W.Q[1].d_out - (char*)W.Q[0].d_out;
   bool even = true;
@@ -3212,26 +3259,44 @@ static int rlpd_td_impl(const dppo_net_desc& q, int E, const float* qp, const vo
   if (!even) return fail(-1, "members' workspaces are not evenly spaced");
   const PackLayout L = pack_layout<P>(q, 0);
   const int64_t nq = param_layout(q).total;
-  // every member reads the same rows [obs | a | 0], both targets the same [next_obs | next_a | 0]: one image each
-  QsmTdRows r;
-  memset(&r, 0, sizeof(r));
-  r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
-  r.next_actions = next_actions, r.q1in = r.q2in = W.Q[0].in, r.t1in = r.t2in = W.T[0].in, r.KpQ = L.Kp0;
-  r.r_out = W.r, r.term_out = W.term;
-  launch_qsm_td_rows<P>(r, s);
+  // every member reads the same rows [obs | a | 0], both targets the same [next_obs | next_a | 0] (IBRL: for a_bc, then for a_rl):
+  // one image each
+  if (ibrl) {
+    IbrlRows r;
+    memset(&r, 0, sizeof(r));
+    r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
+    r.a_bc = bs.next_bc, r.a_rl = bs.next_rl, r.qin = W.Q[0].in, r.tin = W.T[0].in, r.Kp = L.Kp0, r.r_out = W.r, r.term_out = W.term;
+    launch_ibrl_rows<P>(r, s);
+  } else {
+    QsmTdRows r;
+    memset(&r, 0, sizeof(r));
+    r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
+    r.next_actions = bs.next_actions, r.q1in = r.q2in = W.Q[0].in, r.t1in = r.t2in = W.T[0].in, r.KpQ = L.Kp0;
+    r.r_out = W.r, r.term_out = W.term;
+    launch_qsm_td_rows<P>(r, s);
+  }
   for (int e = 1; e < E; ++e) W.Q[e].in = W.Q[0].in;
   W.T[1].in = W.T[0].in;
   // the trunks take turns on the caller's stream and the three side streams
+  const int64_t NT = ibrl ? 2 * N : N;
   hipStream_t st[4] = {s, fork_side(s, 0), fork_side(s, 1), fork_side(s, 2)};
-  mlp_forward<P>(q, tp + p0 * nq, tk1, L, N, W.T[0], false, st[1]);
-  mlp_forward<P>(q, tp + p1 * nq, tk2, L, N, W.T[1], false, st[2]);
+  mlp_forward<P>(q, tp + p0 * nq, (const char*)tk[p0], L, NT, W.T[0], false, st[1]);
+  mlp_forward<P>(q, tp + p1 * nq, (const char*)tk[p1], L, NT, W.T[1], false, st[2]);
   for (int e = 0; e < E; ++e) mlp_forward<P>(q, qp + e * nq, (const char*)qk[e], L, N, W.Q[e], true, st[(e + 3) & 3]);
   for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
   RlpdLoss l;
   memset(&l, 0, sizeof(l));
   l.q = W.Q[0].out, l.q_stride = q_stride, l.ldq = W.Q[0].ldout, l.t1 = W.T[0].out, l.t2 = W.T[1].out, l.ldt = W.T[0].ldout;
-  l.reward = W.r, l.terminated = W.term, l.next_logp = next_logp, l.alpha = alpha, l.gamma = (float)gamma, l.N = N, l.E = E;
+  l.reward = W.r, l.terminated = W.term, l.next_logp = bs.next_logp, l.alpha = bs.alpha, l.gamma = (float)gamma, l.N = N, l.E = E;
   l.d_out = W.Q[0].d_out, l.d_stride = d_stride, l.ldd = L.Kpo, l.partial = W.partial, l.stats = stats;
+  if (ibrl) {  // the better proposal's smaller target Q per row, which the loss then reads as both of its targets
+    IbrlTarget t;
+    memset(&t, 0, sizeof(t));
+    t.t1 = W.T[0].out, t.t2 = W.T[1].out, t.ldt = W.T[0].ldout, t.N = N, t.tq = W.tq, t.reward = W.r, t.terminated = W.term;
+    t.gamma = (float)gamma, t.y_out = bs.y_out, t.partial = W.won, t.share = bs.bc_share ? bs.bc_share : W.share;
+    launch_ibrl_target(t, s);
+    l.t1 = l.t2 = W.tq, l.ldt = 1;
+  }
   launch_rlpd_loss<P>(l, s);
   for (int i = 1; i < 4; ++i) st[i] = fork_side(s, i - 1);
   for (int e = 0; e < E; ++e)
@@ -3239,6 +3304,17 @@ static int rlpd_td_impl(const dppo_net_desc& q, int E, const float* qp, const vo
   for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
   launch_rlpd_out_bias(W.partial, N, E, qgrad, nq, param_layout(q).bout, s);
   return check_launch();
+}
+// The checks both entries share behind their own null-pointer test
+static int check_ensemble_td(const void* const* q_packed, const void* const* target_q_packed, int pair0, int pair1, int E,
+                             const dppo_idql_batch* batch, int64_t N, int64_t n_max, double gamma) {
+  if (int e = check_member_pair(pair0, pair1, E)) return e;
+  if (int e = check_member_images(q_packed, E)) return e;
+  if (!target_q_packed[pair0] || !target_q_packed[pair1]) return fail(-1, "null pointer: kernel image of a target member of the pair");
+  if (N < 1 || N > n_max) return fail(-1, "N out of range");
+  if (int e = check_idql_batch(batch, N, RING_TRANSITION)) return e;
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
+  return 0;
 }
 int dppo_rlpd_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const float* q_params, const void* const* q_packed,
                              const float* target_q_params, const void* const* target_q_packed, int pair0, int pair1,
@@ -3250,28 +3326,18 @@ int dppo_rlpd_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const floa
   if (!q_params || !q_packed || !target_q_params || !target_q_packed || !next_actions || !q_grad || !stats || !workspace)
     return fail(-1, "null pointer");
   if ((next_logp == nullptr) != (alpha == nullptr)) return fail(-1, "null pointer: next_logp and alpha go together (both null: no entropy backup)");
-  if (pair0 < 0 || pair0 >= E || pair1 < 0 || pair1 >= E || pair0 == pair1)
-    return fail(-1, "pair (%d, %d): two different members of [0, %d) are needed", pair0, pair1, E);
-  for (int e = 0; e < E; ++e)
-    if (!q_packed[e]) return fail(-1, "null pointer: kernel image of member %d", e);
-  if (!target_q_packed[pair0] || !target_q_packed[pair1]) return fail(-1, "null pointer: kernel image of a target member of the pair");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  if (int e = check_idql_batch(batch, N, true)) return e;
-  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
-#define CALL(P)                                                                                                                      \
-  rlpd_td_impl<P>(*q, E, q_params, q_packed, target_q_params, (const char*)target_q_packed[pair0], (const char*)target_q_packed[pair1], \
-                  pair0, pair1, *batch, obs_dim, next_actions, next_logp, alpha, N, gamma, q_grad, stats, workspace, workspace_bytes, \
-                  (hipStream_t)stream)
+  if (int e = check_ensemble_td(q_packed, target_q_packed, pair0, pair1, E, batch, N, 0x7fffffff, gamma)) return e;
+  EnsembleBootstrap bs;
+  memset(&bs, 0, sizeof(bs));
+  bs.next_actions = next_actions, bs.next_logp = next_logp, bs.alpha = alpha;
+#define CALL(P)                                                                                                                   \
+  ensemble_td_impl<P>(*q, E, q_params, q_packed, target_q_params, target_q_packed, pair0, pair1, *batch, obs_dim, bs, N, gamma, q_grad, \
+                      stats, workspace, workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }
 
 // ---- IBRL (ibrl.hip): acting through two proposals, and the ensemble's TD loss with the better of them as bootstrap ----------------
-static int check_ibrl_pair(int pair0, int pair1, int E) {
-  if (pair0 < 0 || pair0 >= E || pair1 < 0 || pair1 >= E || pair0 == pair1)
-    return fail(-1, "pair (%d, %d): two different members of [0, %d) are needed", pair0, pair1, E);
-  return 0;
-}
 template <class P>
 struct IbrlActWs {
   MlpBufs<P> A[2], Q[2];  // the BC and the RL actor over B rows, the pair's members over 2B
@@ -3375,7 +3441,7 @@ int dppo_ibrl_act(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, 
     if (int e = check_dropout(drop_rl)) return e;
   if (!bc_params || !bc_packed || !rl_params || !rl_packed || !q_params || !q_packed || !obs || !actions || !workspace)
     return fail(-1, "null pointer");
-  if (int e = check_ibrl_pair(pair0, pair1, E)) return e;
+  if (int e = check_member_pair(pair0, pair1, E)) return e;
   if (!q_packed[pair0] || !q_packed[pair1]) return fail(-1, "null pointer: kernel image of a member of the pair");
   if (B < 1 || B > 0x3fffffff) return fail(-1, "B out of range");
   if (!(beta == beta)) return fail(-1, "soft_action_sample_beta is NaN");
@@ -3392,86 +3458,7 @@ int dppo_ibrl_act(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, 
 #undef CALL
 }
 
-// The TD loss: rlpd_td_impl's sequence with the targets over 2N rows and ibrl.h's target kernel in front of RLPD's loss.  A sibling
-// and no split of rlpd_td_impl: the members' part is the same calls in the same order on the same streams, and RLPD's is left alone.
-template <class P>
-struct IbrlTdWs {
-  MlpBufs<P> Q[RLPD_MAX_E], T[2];
-  double* partial;
-  float *r, *term, *tq;
-  uint32_t* won;
-  double* share;
-};
-template <class P>
-static size_t carve_ibrl_td(Carver& c, const dppo_net_desc& q, int64_t N, int E, IbrlTdWs<P>& W) {
-  W.partial = (double*)c.take((size_t)E * rlpd_blocks(N) * 4 * sizeof(double));
-  W.r = (float*)c.take((size_t)N * 4);
-  W.term = (float*)c.take((size_t)N * 4);
-  W.tq = (float*)c.take((size_t)N * 4);
-  W.won = (uint32_t*)c.take((size_t)ibrl_target_blocks(N) * 4);
-  W.share = (double*)c.take(sizeof(double));
-  for (int e = 0; e < E; ++e) {
-    carve_mlp<P>(c, q, N, true, true, W.Q[e]);
-    // bf16: the rows that enter LayerNorm's backward stay in fp32 (ibrl.h); in fp32 the elem rows are that already
-    if (P::ESIZE == 2)
-      for (int i = 0; i < 2; ++i) W.Q[e].ln_dz32[i] = (float*)c.take((size_t)N * q.hidden * 4);
-  }
-  for (int i = 0; i < 2; ++i) carve_mlp<P>(c, q, 2 * N, false, false, W.T[i]);
-  return al256(c.off);
-}
-int64_t dppo_ibrl_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
-  if (check_rlpd_q(q, obs_dim, E) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x3fffffff) return fail(-1, "N out of range");
-  return ws_bytes(prec, [&](Carver& c, auto p) {
-    IbrlTdWs<decltype(p)> W;
-    return carve_ibrl_td<decltype(p)>(c, *q, N, E, W);
-  });
-}
-template <class P>
-static int ibrl_td_impl(const dppo_net_desc& q, int E, const float* qp, const void* const* qk, const float* tp, const char* tk1,
-                        const char* tk2, int p0, int p1, const dppo_idql_batch& b, int OD, const float* next_bc, const float* next_rl,
-                        int64_t N, double gamma, float* qgrad, double* stats, float* y_out, double* bc_share, void* ws, int64_t wsb,
-                        hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
-  IbrlTdWs<P> W;
-  const size_t need = carve_ibrl_td<P>(c, q, N, E, W);
-  const int64_t q_stride = W.Q[1].out - W.Q[0].out, d_stride = (char*)W.Q[1].d_out - (char*)W.Q[0].d_out;
-  bool even = true;
-  for (int e = 1; e < E; ++e) even = even && W.Q[e].out - W.Q[0].out == e * q_stride && (char*)W.Q[e].d_out - (char*)W.Q[0].d_out == e * d_stride;
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
-  if (!even) return fail(-1, "members' workspaces are not evenly spaced");
-  const PackLayout L = pack_layout<P>(q, 0);
-  const int64_t nq = param_layout(q).total;
-  IbrlRows r;
-  memset(&r, 0, sizeof(r));
-  r.ring = idql_rows_of(b, N, OD, q.in_dim - OD);
-  r.a_bc = next_bc, r.a_rl = next_rl, r.qin = W.Q[0].in, r.tin = W.T[0].in, r.Kp = L.Kp0, r.r_out = W.r, r.term_out = W.term;
-  launch_ibrl_rows<P>(r, s);
-  for (int e = 1; e < E; ++e) W.Q[e].in = W.Q[0].in;
-  W.T[1].in = W.T[0].in;
-  hipStream_t st[4] = {s, fork_side(s, 0), fork_side(s, 1), fork_side(s, 2)};
-  mlp_forward<P>(q, tp + p0 * nq, tk1, L, 2 * N, W.T[0], false, st[1]);
-  mlp_forward<P>(q, tp + p1 * nq, tk2, L, 2 * N, W.T[1], false, st[2]);
-  for (int e = 0; e < E; ++e) mlp_forward<P>(q, qp + e * nq, (const char*)qk[e], L, N, W.Q[e], true, st[(e + 3) & 3]);
-  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
-  IbrlTarget t;
-  memset(&t, 0, sizeof(t));
-  t.t1 = W.T[0].out, t.t2 = W.T[1].out, t.ldt = W.T[0].ldout, t.N = N, t.tq = W.tq, t.reward = W.r, t.terminated = W.term;
-  t.gamma = (float)gamma, t.y_out = y_out, t.partial = W.won, t.share = bc_share ? bc_share : W.share;
-  launch_ibrl_target(t, s);
-  RlpdLoss l;
-  memset(&l, 0, sizeof(l));
-  l.q = W.Q[0].out, l.q_stride = q_stride, l.ldq = W.Q[0].ldout, l.t1 = l.t2 = W.tq, l.ldt = 1;
-  l.reward = W.r, l.terminated = W.term, l.gamma = (float)gamma, l.N = N, l.E = E;
-  l.d_out = W.Q[0].d_out, l.d_stride = d_stride, l.ldd = L.Kpo, l.partial = W.partial, l.stats = stats;
-  launch_rlpd_loss<P>(l, s);
-  for (int i = 1; i < 4; ++i) st[i] = fork_side(s, i - 1);
-  for (int e = 0; e < E; ++e)
-    mlp_backward<P>(q, qp + e * nq, (const char*)qk[e], L, N, W.Q[e], qgrad + e * nq, nullptr, nullptr, 0, st[e & 3]);
-  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
-  launch_rlpd_out_bias(W.partial, N, E, qgrad, nq, param_layout(q).bout, s);
-  return check_launch();
-}
+// The TD loss with the better of the two proposals as bootstrap: ensemble_td_impl (further up, beside RLPD's)
 int dppo_ibrl_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const float* q_params, const void* const* q_packed,
                              const float* target_q_params, const void* const* target_q_packed, int pair0, int pair1,
                              const dppo_idql_batch* batch, int obs_dim, const float* next_actions_bc, const float* next_actions_rl,
@@ -3482,17 +3469,13 @@ int dppo_ibrl_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const floa
   if (!q_params || !q_packed || !target_q_params || !target_q_packed || !next_actions_bc || !next_actions_rl || !q_grad || !stats ||
       !workspace)
     return fail(-1, "null pointer");
-  if (int e = check_ibrl_pair(pair0, pair1, E)) return e;
-  for (int e = 0; e < E; ++e)
-    if (!q_packed[e]) return fail(-1, "null pointer: kernel image of member %d", e);
-  if (!target_q_packed[pair0] || !target_q_packed[pair1]) return fail(-1, "null pointer: kernel image of a target member of the pair");
-  if (N < 1 || N > 0x3fffffff) return fail(-1, "N out of range");
-  if (int e = check_idql_batch(batch, N, true)) return e;
-  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
-#define CALL(P)                                                                                                                      \
-  ibrl_td_impl<P>(*q, E, q_params, q_packed, target_q_params, (const char*)target_q_packed[pair0], (const char*)target_q_packed[pair1], \
-                  pair0, pair1, *batch, obs_dim, next_actions_bc, next_actions_rl, N, gamma, q_grad, stats, y_out, bc_share,         \
-                  workspace, workspace_bytes, (hipStream_t)stream)
+  if (int e = check_ensemble_td(q_packed, target_q_packed, pair0, pair1, E, batch, N, 0x3fffffff, gamma)) return e;
+  EnsembleBootstrap bs;
+  memset(&bs, 0, sizeof(bs));
+  bs.next_bc = next_actions_bc, bs.next_rl = next_actions_rl, bs.y_out = y_out, bs.bc_share = bc_share;
+#define CALL(P)                                                                                                                   \
+  ensemble_td_impl<P>(*q, E, q_params, q_packed, target_q_params, target_q_packed, pair0, pair1, *batch, obs_dim, bs, N, gamma, q_grad, \
+                      stats, workspace, workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }
@@ -3501,48 +3484,99 @@ int dppo_ibrl_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const floa
 static int check_sac_actor(const dppo_net_desc* a);
 static int check_sac_cfg(const dppo_net_desc* a, const dppo_sac_cfg* cfg);
 static SacHead sac_head_of(const dppo_sac_cfg& cfg, const float* out, int ldo, int AF, const float* noise, int64_t N);
-static int check_rlpd_pair(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim, int E) {
-  if (int e = check_sac_actor(a)) return e;
-  if (int e = check_rlpd_q(q, obs_dim, E)) return e;
+// SAC's actor ([mean | raw logvar], out_dim = 2 Ta*Da) against a Q trunk over [obs | a]; both descriptors already checked
+static int check_sac_actor_q(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim) {
   if (a->cond_dim != obs_dim || q->in_dim - obs_dim != a->out_dim / 2)
     return fail(-1, "actor / Q descriptors do not pair: actor cond_dim=%d, Ta*Da=%d against obs_dim=%d, Q in_dim=%d", a->cond_dim,
                 a->out_dim / 2, obs_dim, q->in_dim);
   return 0;
 }
+static int check_rlpd_pair(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim, int E) {
+  if (int e = check_sac_actor(a)) return e;
+  if (int e = check_rlpd_q(q, obs_dim, E)) return e;
+  return check_sac_actor_q(a, q, obs_dim);
+}
+// An actor loss through M LayerNorm trunks (RLPD: the E members; Cal-QL: the twin, with its choice per row)
 template <class P>
-struct RlpdActorWs {
+struct LnActorWs {
   MlpBufs<P> A, Q[RLPD_MAX_E];
-  void *dza[RLPD_MAX_E], *dzb[RLPD_MAX_E];  // member e's two alternating [N][H] chain buffers
-  void* dhcat;                              // [N][E H] elem: member e's dx_0 in columns [e H, (e + 1) H)
-  void* w0a;                                // [AF][E H] elem
+  void *dza[RLPD_MAX_E], *dzb[RLPD_MAX_E];  // trunk i's two alternating [N][H] chain buffers; dza[i] takes the seed
+  void* dhcat;                              // [N][M H] elem: trunk i's dx_0 in columns [i H, (i + 1) H)
+  void* w0a;                                // [AF][M H] elem
   float *actions, *logp, *sig;
+  float* qsel;    // Cal-QL only, as sel
   float* dout32;  // bf16 only (SacTail::d_out32)
+  uint8_t* sel;
 };
 template <class P>
-static size_t carve_rlpd_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, int E, RlpdActorWs<P>& W) {
+static size_t carve_ln_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, int M, bool calql, LnActorWs<P>& W) {
   const size_t ES = P::ESIZE;
   const int AF = a.out_dim / 2;
   carve_mlp<P>(c, a, N, true, true, W.A);
-  for (int e = 0; e < E; ++e) {
-    carve_mlp<P>(c, q, N, true, false, W.Q[e]);
-    W.dza[e] = c.take((size_t)N * q.hidden * ES);
-    W.dzb[e] = c.take((size_t)N * q.hidden * ES);
+  for (int i = 0; i < M; ++i) {
+    carve_mlp<P>(c, q, N, true, false, W.Q[i]);
+    W.dza[i] = c.take((size_t)N * q.hidden * ES);
+    W.dzb[i] = c.take((size_t)N * q.hidden * ES);
   }
-  W.dhcat = c.take((size_t)N * E * q.hidden * ES);
-  W.w0a = c.take((size_t)AF * E * q.hidden * ES);
+  W.dhcat = c.take((size_t)N * M * q.hidden * ES);
+  W.w0a = c.take((size_t)AF * M * q.hidden * ES);
   W.actions = (float*)c.take((size_t)N * AF * 4);
   W.logp = (float*)c.take((size_t)N * 4);
   W.sig = (float*)c.take((size_t)N * 4);
+  W.qsel = calql ? (float*)c.take((size_t)N * 4) : nullptr;
   W.dout32 = ES == 4 ? nullptr : (float*)c.take((size_t)N * 2 * AF * 4);
+  W.sel = calql ? (uint8_t*)c.take((size_t)N) : nullptr;
   return al256(c.off);
 }
 int64_t dppo_rlpd_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
   if (check_rlpd_pair(actor, q, obs_dim, E) || check_prec(prec)) return -1;
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
   return ws_bytes(prec, [&](Carver& c, auto p) {
-    RlpdActorWs<decltype(p)> W;
-    return carve_rlpd_actor<decltype(p)>(c, *actor, *q, N, E, W);
+    LnActorWs<decltype(p)> W;
+    return carve_ln_actor<decltype(p)>(c, *actor, *q, N, E, false, W);
   });
+}
+// The front of such a loss, on s: the actor's rows [obs | 0], the W0 action columns of the M trunks as [AF][M H], the actor's forward
+// with the activations kept, and the head: sample, log-probability and ONE image of the critic's rows [obs | a | 0] that every trunk
+// reads.  -> the head, which the tail runs backwards.
+template <class P>
+static SacHead ln_actor_front(const dppo_net_desc& a, const dppo_net_desc& q, int M, const float* ap, const char* ak, const float* qp,
+                              const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N, const float* noise,
+                              LnActorWs<P>& W, float* actions, float* logp, hipStream_t s) {
+  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const ParamLayout plq = param_layout(q);
+  const int AF = a.out_dim / 2;
+  IdqlRows r = idql_rows_of(b, N, OD, AF);
+  r.vin = W.A.in, r.KpV = LA.Kp0;
+  launch_idql_rows<P>(r, s);
+  launch_rlpd_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, q.hidden, M, W.w0a, s);
+  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
+  SacHead h = sac_head_of(cfg, W.A.out, W.A.ldout, AF, noise, N);
+  h.ring = idql_rows_of(b, N, OD, AF);
+  h.actions = actions, h.logp = logp, h.sig_row = W.sig, h.q1in = h.q2in = W.Q[0].in, h.KpQ = LQ.Kp0;
+  launch_sac_head<P>(h, s);
+  for (int i = 1; i < M; ++i) W.Q[i].in = W.Q[0].in;
+  return h;
+}
+// The back, on s: one tail over the M trunks' dx_0 (E of them averaged; 1: the seeds carry the weights) whose epilogue is the head's
+// backward, the caller's statistics, the actor's backward.
+static void launch_actor_stats(const RlpdActorStats& a, hipStream_t s) { launch_rlpd_actor_stats(a, s); }
+static void launch_actor_stats(const SacStats& a, hipStream_t s) { launch_sac_stats(a, s); }
+template <class P, class Stats>
+static void ln_actor_back(const dppo_net_desc& a, const dppo_net_desc& q, int M, int E, const float* ap, const char* ak,
+                          const SacHead& h, const double* alpha, const Stats& stats, int64_t N, LnActorWs<P>& W, float* grad, float* d_a,
+                          hipStream_t s) {
+  const PackLayout LA = pack_layout<P>(a, 0);
+  const int AF = a.out_dim / 2;
+  RlpdTail tl;
+  memset(&tl, 0, sizeof(tl));
+  tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.K = M * q.hidden, tl.E = E, tl.alpha = alpha;
+  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
+  launch_rlpd_tail<P>(tl, s);
+  launch_actor_stats(stats, s);
+  mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s);
+  if (W.dout32 != nullptr)  // the two heads' bias gradient again, from the unrounded rows
+    launch_colsum<F32>(W.dout32, (int)N, 2 * AF, 2 * AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
 }
 // d q / d (layer 0's Linear output) of one LayerNorm trunk, into its columns of dhcat (row stride ldh), from a seed d q / d z_L that
 // is already in dza: per hidden layer from the top the LayerNorm backward without parameter sums and, except at layer 0, the data
@@ -3585,29 +3619,17 @@ static int rlpd_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, int E
                            const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
                            float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
   Carver c{(char*)ws, 0, (size_t)wsb};
-  RlpdActorWs<P> W;
-  const size_t need = carve_rlpd_actor<P>(c, a, q, N, E, W);
+  LnActorWs<P> W;
+  const size_t need = carve_ln_actor<P>(c, a, q, N, E, false, W);
   if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
   const int64_t q_stride = W.Q[1].out - W.Q[0].out;
   for (int e = 1; e < E; ++e)
     if (W.Q[e].out - W.Q[0].out != e * q_stride) return fail(-1, "members' workspaces are not evenly spaced");
-  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const PackLayout LQ = pack_layout<P>(q, 0);
   const ParamLayout plq = param_layout(q);
   const int AF = a.out_dim / 2, H = q.hidden;
-  float* actions = actions_out != nullptr ? actions_out : W.actions;
   float* logp = logp_out != nullptr ? logp_out : W.logp;
-  // the actor's rows [obs | 0], its forward with the activations kept, the head: sample, log-probability and ONE image of the
-  // critic's rows [obs | a | 0] that every member reads
-  IdqlRows r = idql_rows_of(b, N, OD, AF);
-  r.vin = W.A.in, r.KpV = LA.Kp0;
-  launch_idql_rows<P>(r, s);
-  launch_rlpd_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, H, E, W.w0a, s);
-  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
-  SacHead h = sac_head_of(cfg, W.A.out, W.A.ldout, AF, noise, N);
-  h.ring = idql_rows_of(b, N, OD, AF);
-  h.actions = actions, h.logp = logp, h.sig_row = W.sig, h.q1in = h.q2in = W.Q[0].in, h.KpQ = LQ.Kp0;
-  launch_sac_head<P>(h, s);
-  for (int e = 1; e < E; ++e) W.Q[e].in = W.Q[0].in;
+  const SacHead h = ln_actor_front<P>(a, q, E, ap, ak, qp, cfg, b, OD, N, noise, W, actions_out != nullptr ? actions_out : W.actions, logp, s);
   // the members take turns on the caller's stream and the three side streams: each runs its forward and its chain back to back
   hipStream_t st[4] = {s, fork_side(s, 0), fork_side(s, 1), fork_side(s, 2)};
   for (int e = 0; e < E; ++e) {
@@ -3617,19 +3639,11 @@ static int rlpd_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, int E
                          E * H, st[e & 3]);
   }
   for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
-  RlpdTail tl;
-  memset(&tl, 0, sizeof(tl));
-  tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.K = E * H, tl.E = E, tl.alpha = alpha;
-  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
-  launch_rlpd_tail<P>(tl, s);
   RlpdActorStats sa;
   memset(&sa, 0, sizeof(sa));
   sa.q = W.Q[0].out, sa.q_stride = q_stride, sa.ldq = W.Q[0].ldout, sa.E = E, sa.logp = logp, sa.sig_row = W.sig, sa.alpha = alpha;
   sa.N = N, sa.AF = AF, sa.stats = stats;
-  launch_rlpd_actor_stats(sa, s);
-  mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s);
-  if (W.dout32 != nullptr)  // the two heads' bias gradient again, from the unrounded rows
-    launch_colsum<F32>(W.dout32, (int)N, 2 * AF, 2 * AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
+  ln_actor_back<P>(a, q, E, E, ap, ak, h, alpha, sa, N, W, grad, d_a, s);
   return check_launch();
 }
 int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int E, const float* actor_params,
@@ -3643,15 +3657,9 @@ int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, 
   if (cfg->deterministic) return fail(-1, "the actor loss samples: deterministic must be 0");
   if (!actor_params || !actor_packed || !q_params || !q_packed || !alpha || !actor_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  for (int e = 0; e < E; ++e)
-    if (!q_packed[e]) return fail(-1, "null pointer: kernel image of member %d", e);
+  if (int e = check_member_images(q_packed, E)) return e;
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  if (!batch) return fail(-1, "null batch");
-  if (!batch->obs) return fail(-1, "null pointer in batch");
-  if (batch->cap < 1 || batch->n_envs < 1 || batch->count < 1 || batch->count > batch->cap || batch->head < 0 || batch->head >= batch->cap)
-    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
-  if (!batch->inds && N > batch->count * batch->n_envs)
-    return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N, (long long)(batch->count * batch->n_envs));
+  if (int e = check_idql_batch(batch, N, RING_OBS)) return e;
 #define CALL(P)                                                                                                                    \
   rlpd_actor_impl<P>(*actor, *q, E, actor_params, (const char*)actor_packed, q_params, q_packed, *cfg, *batch, obs_dim, N, noise,   \
                      alpha, actor_grad, stats, d_a, logp_out, actions_out, workspace, workspace_bytes, (hipStream_t)stream)
@@ -3661,11 +3669,8 @@ int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, 
 
 // ---- Cal-QL (calql.hip): the conservative critic loss on a twin of LayerNorm Q trunks --------------------------------------------
 static int check_calql_q(const dppo_net_desc* q, int obs_dim, int64_t N, int R, int S) {
-  if (int e = check_idql_q(q, true)) return e;
-  if (!q->plain || !q->use_layernorm)
-    return fail(-1, "Cal-QL's twin is two plain trunks with LayerNorm (plain = 1, use_layernorm = 1); a twin without LayerNorm trains through dppo_sac_q_loss_fwd_bwd");
-  if (obs_dim < 1 || obs_dim >= q->in_dim)
-    return fail(-1, "Q descriptor does not pair with obs_dim=%d: in_dim=%d must be obs_dim + the action width", obs_dim, q->in_dim);
+  if (int e = check_ln_q(q, obs_dim, "Cal-QL's twin is two plain trunks with LayerNorm (plain = 1, use_layernorm = 1); a twin without LayerNorm trains through dppo_sac_q_loss_fwd_bwd"))
+    return e;
   if (R < 1 || R > CALQL_MAX_SAMPLES) return fail(-1, "n_random=%d random actions per row out of [1, %d]", R, CALQL_MAX_SAMPLES);
   if (S < 1 || S > CALQL_MAX_SAMPLES) return fail(-1, "n_next=%d policy samples per next observation out of [1, %d]", S, CALQL_MAX_SAMPLES);
   if (N < 1 || N * (R + 3) > 0x7fffffff || N * S > 0x7fffffff) return fail(-1, "N out of range");
@@ -3762,7 +3767,7 @@ int dppo_calql_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_p
   if (!q_params || !q1_packed || !q2_packed || !target_q_params || !target_q1_packed || !target_q2_packed || !returns ||
       !next_actions || !pi_actions || !log_pi || !pi_next_actions || !log_pi_next || !q_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (int e = check_idql_batch(batch, N, RING_TRANSITION)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                     \
   calql_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed,       \
@@ -3777,46 +3782,13 @@ int dppo_calql_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_p
 static int check_calql_pair(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim, int64_t N) {
   if (int e = check_sac_actor(a)) return e;
   if (int e = check_calql_q(q, obs_dim, N, 1, 1)) return e;
-  if (a->cond_dim != obs_dim || q->in_dim - obs_dim != a->out_dim / 2)
-    return fail(-1, "actor / Q descriptors do not pair: actor cond_dim=%d, Ta*Da=%d against obs_dim=%d, Q in_dim=%d", a->cond_dim,
-                a->out_dim / 2, obs_dim, q->in_dim);
-  return 0;
-}
-template <class P>
-struct CalqlActorWs {
-  MlpBufs<P> A, Q[2];
-  void *dza[2], *dzb[2];  // trunk i's two alternating [N][H] chain buffers; dza[i] takes the seed
-  void* dhcat;            // [N][2H] elem: trunk i's dx_0 in columns [i H, (i + 1) H)
-  void* w0a;              // [AF][2H] elem
-  float *actions, *logp, *sig, *qsel;
-  float* dout32;  // bf16 only (SacTail::d_out32)
-  uint8_t* sel;
-};
-template <class P>
-static size_t carve_calql_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, CalqlActorWs<P>& W) {
-  const size_t ES = P::ESIZE;
-  const int AF = a.out_dim / 2;
-  carve_mlp<P>(c, a, N, true, true, W.A);
-  for (int i = 0; i < 2; ++i) {
-    carve_mlp<P>(c, q, N, true, false, W.Q[i]);
-    W.dza[i] = c.take((size_t)N * q.hidden * ES);
-    W.dzb[i] = c.take((size_t)N * q.hidden * ES);
-  }
-  W.dhcat = c.take((size_t)N * 2 * q.hidden * ES);
-  W.w0a = c.take((size_t)AF * 2 * q.hidden * ES);
-  W.actions = (float*)c.take((size_t)N * AF * 4);
-  W.logp = (float*)c.take((size_t)N * 4);
-  W.sig = (float*)c.take((size_t)N * 4);
-  W.qsel = (float*)c.take((size_t)N * 4);
-  W.dout32 = ES == 4 ? nullptr : (float*)c.take((size_t)N * 2 * AF * 4);
-  W.sel = (uint8_t*)c.take((size_t)N);
-  return al256(c.off);
+  return check_sac_actor_q(a, q, obs_dim);
 }
 int64_t dppo_calql_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
   if (check_calql_pair(actor, q, obs_dim, N) || check_prec(prec)) return -1;
   return ws_bytes(prec, [&](Carver& c, auto p) {
-    CalqlActorWs<decltype(p)> W;
-    return carve_calql_actor<decltype(p)>(c, *actor, *q, N, W);
+    LnActorWs<decltype(p)> W;
+    return carve_ln_actor<decltype(p)>(c, *actor, *q, N, 2, true, W);
   });
 }
 template <class P>
@@ -3825,27 +3797,15 @@ static int calql_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, cons
                             const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
                             uint8_t* sel_out, float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
   Carver c{(char*)ws, 0, (size_t)wsb};
-  CalqlActorWs<P> W;
-  const size_t need = carve_calql_actor<P>(c, a, q, N, W);
+  LnActorWs<P> W;
+  const size_t need = carve_ln_actor<P>(c, a, q, N, 2, true, W);
   if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
-  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const PackLayout LQ = pack_layout<P>(q, 0);
   const ParamLayout plq = param_layout(q);
   const int AF = a.out_dim / 2, H = q.hidden;
-  float* actions = actions_out != nullptr ? actions_out : W.actions;
   float* logp = logp_out != nullptr ? logp_out : W.logp;
   uint8_t* sel = sel_out != nullptr ? sel_out : W.sel;
-  // as rlpd_actor_impl: the actor's rows [obs | 0], the W0 action columns of both trunks as [AF][2H], the actor's forward, the head
-  // with ONE image of the critic's rows [obs | a | 0]
-  IdqlRows r = idql_rows_of(b, N, OD, AF);
-  r.vin = W.A.in, r.KpV = LA.Kp0;
-  launch_idql_rows<P>(r, s);
-  launch_rlpd_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, H, 2, W.w0a, s);
-  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
-  SacHead h = sac_head_of(cfg, W.A.out, W.A.ldout, AF, noise, N);
-  h.ring = idql_rows_of(b, N, OD, AF);
-  h.actions = actions, h.logp = logp, h.sig_row = W.sig, h.q1in = h.q2in = W.Q[0].in, h.KpQ = LQ.Kp0;
-  launch_sac_head<P>(h, s);
-  W.Q[1].in = W.Q[0].in;
+  const SacHead h = ln_actor_front<P>(a, q, 2, ap, ak, qp, cfg, b, OD, N, noise, W, actions_out != nullptr ? actions_out : W.actions, logp, s);
   const float* prm[2] = {qp, qp + plq.total};
   const char* qk[2] = {qk1, qk2};
   // both forwards side by side; the choice of the twin per row seeds both chains (the other trunk's seed is 0, a tie's are halves)
@@ -3863,18 +3823,10 @@ static int calql_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, cons
   rlpd_chain_from_seed<P>(q, prm[1], qk[1], LQ, N, W.Q[1], W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, 2 * H, s2);
   rlpd_chain_from_seed<P>(q, prm[0], qk[0], LQ, N, W.Q[0], W.dza[0], W.dzb[0], W.dhcat, 2 * H, s);
   if (s2 != s) join_side(s, s2, 0);
-  RlpdTail tl;
-  memset(&tl, 0, sizeof(tl));
-  tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.K = 2 * H, tl.E = 1, tl.alpha = alpha;  // (E = 1: the seeds carry the weights)
-  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
-  launch_rlpd_tail<P>(tl, s);
   SacStats st;
   memset(&st, 0, sizeof(st));
   st.qsel = W.qsel, st.logp = logp, st.sig_row = W.sig, st.alpha = alpha, st.N = N, st.AF = AF, st.stats = stats;
-  launch_sac_stats(st, s);
-  mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s);
-  if (W.dout32 != nullptr)  // the two heads' bias gradient again, from the unrounded rows
-    launch_colsum<F32>(W.dout32, (int)N, 2 * AF, 2 * AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
+  ln_actor_back<P>(a, q, 2, 1, ap, ak, h, alpha, st, N, W, grad, d_a, s);  // (E = 1: the seeds carry the weights)
   return check_launch();
 }
 int dppo_calql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
@@ -3888,12 +3840,7 @@ int dppo_calql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q,
   if (cfg->deterministic) return fail(-1, "the actor loss samples: deterministic must be 0");
   if (!actor_params || !actor_packed || !q_params || !q1_packed || !q2_packed || !alpha || !actor_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  if (!batch) return fail(-1, "null batch");
-  if (!batch->obs) return fail(-1, "null pointer in batch");
-  if (batch->cap < 1 || batch->n_envs < 1 || batch->count < 1 || batch->count > batch->cap || batch->head < 0 || batch->head >= batch->cap)
-    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
-  if (!batch->inds && N > batch->count * batch->n_envs)
-    return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N, (long long)(batch->count * batch->n_envs));
+  if (int e = check_idql_batch(batch, N, RING_OBS)) return e;
 #define CALL(P)                                                                                                                      \
   calql_actor_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, \
                       *cfg, *batch, obs_dim, N, noise, alpha, actor_grad, stats, d_a, logp_out, sel_out, actions_out, workspace,      \
@@ -4108,12 +4055,7 @@ int dppo_dql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, i
       !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || !actor_grad || !stats || !workspace)
     return fail(-1, "null pointer");
   if (int e = check_dql_sizes(actor, N, K)) return e;
-  if (!batch) return fail(-1, "null batch");
-  if (!batch->obs) return fail(-1, "null pointer in batch");
-  if (batch->cap < 1 || batch->n_envs < 1 || batch->count < 1 || batch->count > batch->cap || batch->head < 0 || batch->head >= batch->cap)
-    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
-  if (!batch->inds && N > batch->count * batch->n_envs)
-    return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N, (long long)(batch->count * batch->n_envs));
+  if (int e = check_idql_batch(batch, N, RING_OBS)) return e;
   if (which != 0 && which != 1) return fail(-1, "which=%d must be 0 (-mean q1 / mean|q2|) or 1 (-mean q2 / mean|q1|)", which);
   if (!(eta >= -3.0e38 && eta <= 3.0e38)) return fail(-1, "eta=%g must be finite", eta);
   if (cfg->use_ddim) return fail(-1, "DQL does not support DDIM");
@@ -4208,7 +4150,7 @@ int dppo_sac_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
       !next_logp || !alpha || !q_grad || !stats || !workspace)
     return fail(-1, "null pointer");
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  if (int e = check_idql_batch(batch, N, true)) return e;
+  if (int e = check_idql_batch(batch, N, RING_TRANSITION)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                \
   twin_td_impl<P>(*q, q_params, (const char*)q1_packed, (const char*)q2_packed, target_q_params, (const char*)target_q1_packed, \
@@ -4222,10 +4164,7 @@ static int check_sac_pair(const dppo_net_desc* a, const dppo_net_desc* q, int ob
   if (int e = check_sac_actor(a)) return e;
   if (int e = check_qsm_q(q, obs_dim)) return e;
   if (int e = check_qsm_plain(q)) return e;
-  if (a->cond_dim != obs_dim || q->in_dim - obs_dim != a->out_dim / 2)
-    return fail(-1, "actor / Q descriptors do not pair: actor cond_dim=%d, Ta*Da=%d against obs_dim=%d, Q in_dim=%d", a->cond_dim,
-                a->out_dim / 2, obs_dim, q->in_dim);
-  return 0;
+  return check_sac_actor_q(a, q, obs_dim);
 }
 template <class P>
 struct SacWs {
@@ -4329,12 +4268,7 @@ int dppo_sac_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, i
   if (!actor_params || !actor_packed || !q_params || !q1_packed || !q2_packed || !alpha || !actor_grad || !stats || !workspace)
     return fail(-1, "null pointer");
   if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  if (!batch) return fail(-1, "null batch");
-  if (!batch->obs) return fail(-1, "null pointer in batch");
-  if (batch->cap < 1 || batch->n_envs < 1 || batch->count < 1 || batch->count > batch->cap || batch->head < 0 || batch->head >= batch->cap)
-    return fail(-1, "batch ring geometry: need 1 <= count <= cap, n_envs >= 1, 0 <= head < cap");
-  if (!batch->inds && N > batch->count * batch->n_envs)
-    return fail(-1, "N=%lld exceeds the %lld stored transitions", (long long)N, (long long)(batch->count * batch->n_envs));
+  if (int e = check_idql_batch(batch, N, RING_OBS)) return e;
 #define CALL(P)                                                                                                                   \
   sac_actor_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, \
                     *cfg, *batch, obs_dim, N, noise, alpha, actor_grad, stats, d_a, logp_out, sel_out, actions_out, workspace,      \

@@ -30,17 +30,14 @@ import copy
 import ctypes as C
 
 import torch
-from torch import nn
 
 from dppo_amd import hip
 from dppo_amd.model.common import off_policy
+from dppo_amd.model.common.ensemble import EnsembleCritics
 from dppo_amd.model.common.gaussian import GaussianModel
-from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss, flat_views
-from dppo_amd.model.rl.gaussian_rlpd import _Ensemble
-from dppo_amd.util.replay import DeviceReplay
 
 
-class IBRL_Gaussian(GaussianModel):
+class IBRL_Gaussian(EnsembleCritics, GaussianModel):
     child_node_defaults = {"actor": {"plain_fixed_std": True}}  # read by dppo_amd.cfg.loader.instantiate
 
     def __init__(self, actor, critic, n_critics, soft_action_sample=False, soft_action_sample_beta=10, **kwargs):
@@ -56,46 +53,13 @@ class IBRL_Gaussian(GaussianModel):
             raise ValueError("IBRL's members are LayerNorm plain trunks: CriticObsAct(use_layernorm=True, double_q=False)")
         super().__init__(network=actor, **kwargs)  # loads network_path into ``network`` first: the copies below start from it
         self.soft_action_sample, self.soft_action_sample_beta = bool(soft_action_sample), float(soft_action_sample_beta)
-        self.n_critics = int(n_critics)
         self.target_actor = copy.deepcopy(self.network)
         self.bc_policy = copy.deepcopy(self.network)
         for p in self.bc_policy.parameters():
             p.requires_grad = False
-        self.critic_networks = nn.ModuleList([copy.deepcopy(critic).to(self.device) for _ in range(n_critics)])
-        self.target_networks = nn.ModuleList([copy.deepcopy(critic).to(self.device) for _ in range(n_critics)])
-        object.__setattr__(self, "_ens", _Ensemble(self.critic_networks))
-        object.__setattr__(self, "_tens", _Ensemble(self.target_networks))
+        self._init_ensemble(critic, n_critics)
         for name in ("_ws_act", "_ws_q"):
             object.__setattr__(self, name, hip.Workspace())
-
-    # ------------------------------------------------------------------ the flat images (RLPD's, as they are)
-    def critic_flat_params(self) -> torch.Tensor:
-        """[E][P] fp32: what one flat optimiser steps (call ``critics_updated()`` after a kernel wrote it behind torch's back)."""
-        return self._ens.flat_params()
-
-    def critic_flat_grads(self) -> torch.Tensor:
-        return self._ens.flat_grads()
-
-    def target_flat_params(self) -> torch.Tensor:
-        return self._tens.flat_params()
-
-    def critics_updated(self):
-        self._ens.mark_updated()
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        """The reference's ``base_model.*`` (a stateless meta-device copy of one member) is accepted and ignored."""
-        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("base_model.")}, strict=strict, **kw)
-
-    def get_random_indices(self, sz=None, num_ind=2):
-        """``num_ind`` different members out of ``sz``, from torch's CPU generator (reference :61-67); stays on the host: the pair is
-        passed to the library by value."""
-        return torch.randperm(self.n_critics if sz is None else sz)[:num_ind]
-
-    def update_target_critic(self, tau):
-        """target <- target * (1 - tau) + source * tau over the whole [E][P] image in one call."""
-        t, s = self.target_flat_params(), self.critic_flat_params()
-        hip.check(hip.load().dppo_polyak(t.data_ptr(), s.data_ptr(), float(tau), t.numel(), hip.stream()), "dppo_polyak")
-        self._tens.mark_updated()
 
     def update_target_actor(self, tau):
         """target_actor <- target_actor * (1 - tau) + network * tau over the actor's flat image in one call."""
@@ -171,15 +135,11 @@ class IBRL_Gaussian(GaussianModel):
         member's parameters in ``critic_flat_grads()`` ([E][P]); ``last_stats``: {loss, mean q, mean y}; ``last_y`` (N,);
         ``last_bc_share`` (device double: the share of rows where BC won); ``last_pair``.  ``obs`` may be a ``DeviceReplay`` (rows
         ``inds``).  ``next_actions_*`` (N, Ta, Da) replace the samples, ``noise_*`` (N, Ta, Da) and ``mask_*`` (L, N, H) their draws."""
-        if pair is None:
-            pair = self.get_random_indices()
-        p0, p1 = int(pair[0]), int(pair[1])
+        (p0, p1), batch, N, keep = self._td_head("IBRL", pair, obs, inds, actions, next_obs, rewards, terminated)
         q = self.critic_networks[0]
-        batch, N, keep = off_policy.as_batch("IBRL", obs, inds, actions, next_obs, rewards, terminated)
         dev = self.critic_flat_params().device
         if next_actions_bc is None or next_actions_rl is None:
-            nxt = off_policy.rows_of("IBRL", obs, inds, nxt=True) if isinstance(obs, DeviceReplay) else off_policy.state_of(next_obs, "IBRL")
-            nxt = {"state": nxt.reshape(N, -1)}
+            nxt = self._next_cond("IBRL", obs, inds, next_obs, N)
             if next_actions_bc is None:
                 next_actions_bc = self._sample(self.bc_policy, nxt, True, noise_bc, drop_mask=mask_bc)[0]
             if next_actions_rl is None:
@@ -200,10 +160,7 @@ class IBRL_Gaussian(GaussianModel):
             C.byref(dq), self.prec, E, self.critic_flat_params().data_ptr(), qk, self.target_flat_params().data_ptr(), tk, p0, p1,
             C.byref(batch), OD, next_actions_bc.data_ptr(), next_actions_rl.data_ptr(), N, float(gamma), grads.data_ptr(),
             stats.data_ptr(), y.data_ptr(), share.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_ibrl_q_loss_fwd_bwd")
-        for name, v in (("last_stats", stats), ("last_y", y), ("last_bc_share", share), ("last_pair", (p0, p1))):
-            object.__setattr__(self, name, v)
-        params = self._ens.parameters()
-        return _FusedDenoiseLoss.apply(stats[0], flat_views(grads, params), *params)
+        return self._td_tail(stats, grads, (p0, p1), last_y=y, last_bc_share=share)
 
     def loss_actor(self, obs):
         raise NotImplementedError("dppo_amd: IBRL's actor loss (the min over the E members, the backward through dropout and the "

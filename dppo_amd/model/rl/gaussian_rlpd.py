@@ -18,66 +18,18 @@ action-gradient chain through LayerNorm, one tail over E * hidden whose epilogue
 dq/da, then the actor's backward.  It runs on the GPU only; on a CPU model it raises ``NotImplementedError``."""
 from __future__ import annotations
 
-import copy
 import ctypes as C
 
 import torch
-from torch import nn
 
 from dppo_amd import hip
 from dppo_amd.model.common import off_policy
+from dppo_amd.model.common.ensemble import EnsembleCritics, _Ensemble  # noqa: F401  (_Ensemble: imported from here too)
 from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss, flat_views
 from dppo_amd.model.rl.gaussian_sac import SAC_Gaussian
-from dppo_amd.util.replay import DeviceReplay
 
 
-class _Ensemble:
-    """E members of one architecture whose parameters are views of one flat [E][P] buffer, member e at [e P, (e + 1) P)."""
-
-    def __init__(self, members):
-        self.members = list(members)
-        self._flat = self._grad = None
-
-    def flat_params(self) -> torch.Tensor:
-        ms = self.members
-        own = [m.flat_params() for m in ms]
-        P, flat = own[0].numel(), self._flat
-        if flat is not None and all(o.data_ptr() == flat.data_ptr() + 4 * e * P for e, o in enumerate(own)):
-            return flat
-        flat = torch.empty(len(ms) * P, dtype=torch.float32, device=own[0].device)
-        for e, m in enumerate(ms):  # re-home member e: its parameters, its flat image and its trunk's become slices of ``flat``
-            sl = flat[e * P:(e + 1) * P]
-            sl.copy_(own[e])
-            off = 0
-            for p in m.trunk_parameters():
-                p.data = sl[off:off + p.numel()].view(p.shape)
-                off += p.numel()
-            object.__setattr__(m, "_flat", sl)
-            m._packed.clear()
-        self._flat = flat
-        return flat
-
-    def flat_grads(self) -> torch.Tensor:
-        flat = self.flat_params()
-        if self._grad is None or self._grad.device != flat.device or self._grad.numel() != flat.numel():
-            self._grad = torch.zeros_like(flat)
-        return self._grad
-
-    def parameters(self):
-        return [p for m in self.members for p in m.trunk_parameters()]
-
-    def images(self, prec):
-        """(ctypes array of the E kernel-image pointers, the tensors to keep alive)."""
-        self.flat_params()
-        bufs = [m.packed(prec)[0] for m in self.members]
-        return (C.c_void_p * len(bufs))(*[b.data_ptr() for b in bufs]), bufs
-
-    def mark_updated(self):
-        for m in self.members:
-            m.mark_updated()
-
-
-class RLPD_Gaussian(SAC_Gaussian):
+class RLPD_Gaussian(EnsembleCritics, SAC_Gaussian):
     def __init__(self, actor, critic, n_critics, backup_entropy=False, **kwargs):
         if getattr(critic, "double_q", True):
             raise ValueError("RLPD's members are single critics (double_q=False): the reference's loss reads one output of each")
@@ -85,36 +37,10 @@ class RLPD_Gaussian(SAC_Gaussian):
             raise ValueError("RLPD needs at least two critics: the TD target is the smaller of a random pair")
         SAC_Gaussian._check_actor(actor)
         super(SAC_Gaussian, self).__init__(network=actor, **kwargs)  # GaussianModel's: SAC_Gaussian's own wants the twin critic
-        self.n_critics, self.backup_entropy = int(n_critics), bool(backup_entropy)
-        self.critic_networks = nn.ModuleList([copy.deepcopy(critic).to(self.device) for _ in range(n_critics)])
-        self.target_networks = nn.ModuleList([copy.deepcopy(critic).to(self.device) for _ in range(n_critics)])
-        object.__setattr__(self, "_ens", _Ensemble(self.critic_networks))
-        object.__setattr__(self, "_tens", _Ensemble(self.target_networks))
+        self.backup_entropy = bool(backup_entropy)
+        self._init_ensemble(critic, n_critics)
         for name in ("_ws_s", "_ws_actor", "_ws_q"):
             object.__setattr__(self, name, hip.Workspace())
-
-    # ------------------------------------------------------------------ the flat images
-    def critic_flat_params(self) -> torch.Tensor:
-        """[E][P] fp32: what one flat optimiser steps (call ``critics_updated()`` after a kernel wrote it behind torch's back)."""
-        return self._ens.flat_params()
-
-    def critic_flat_grads(self) -> torch.Tensor:
-        return self._ens.flat_grads()
-
-    def target_flat_params(self) -> torch.Tensor:
-        return self._tens.flat_params()
-
-    def critics_updated(self):
-        self._ens.mark_updated()
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        """The reference's ``base_model.*`` (a stateless meta-device copy of one member) is accepted and ignored."""
-        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("base_model.")}, strict=strict, **kw)
-
-    def get_random_indices(self, sz=None, num_ind=2):
-        """``num_ind`` different members out of ``sz``, from torch's CPU generator (reference :56-62); stays on the host: the pair is
-        passed to the library by value."""
-        return torch.randperm(self.n_critics if sz is None else sz)[:num_ind]
 
     # ------------------------------------------------------------------ RL training (reference gaussian_rlpd.py:64-133)
     def loss_critic(self, obs, next_obs, actions, rewards, terminated, gamma, alpha, inds=None, next_actions=None, next_logp=None,
@@ -124,15 +50,12 @@ class RLPD_Gaussian(SAC_Gaussian):
         d loss / d every member's parameters in ``critic_flat_grads()`` ([E][P]); ``last_stats``: {loss, mean q, mean y}.  ``obs``
         may be a ``DeviceReplay`` (rows ``inds``).  ``next_actions`` (N, Ta, Da) with ``next_logp`` (N,), or ``noise`` (N, Ta, Da),
         replace the sample / its draws."""
-        if pair is None:
-            pair = self.get_random_indices()
-        p0, p1 = int(pair[0]), int(pair[1])
+        (p0, p1), batch, N, keep = self._td_head("RLPD", pair, obs, inds, actions, next_obs, rewards, terminated)
         q = self.critic_networks[0]
-        batch, N, keep = off_policy.as_batch("RLPD", obs, inds, actions, next_obs, rewards, terminated)
         dev = self.critic_flat_params().device
         if next_actions is None:
-            nxt = off_policy.rows_of("RLPD", obs, inds, nxt=True) if isinstance(obs, DeviceReplay) else off_policy.state_of(next_obs, "RLPD")
-            next_actions, next_logp = self.forward({"state": nxt.reshape(N, -1)}, deterministic=False, get_logprob=True, noise=noise)
+            next_actions, next_logp = self.forward(self._next_cond("RLPD", obs, inds, next_obs, N), deterministic=False,
+                                                   get_logprob=True, noise=noise)
         next_actions = next_actions.reshape(N, -1).contiguous().float()
         if self.backup_entropy:
             assert next_logp is not None, "next_actions needs next_logp"
@@ -151,10 +74,7 @@ class RLPD_Gaussian(SAC_Gaussian):
             C.byref(dq), self.prec, E, self.critic_flat_params().data_ptr(), qk, self.target_flat_params().data_ptr(), tk, p0, p1,
             C.byref(batch), OD, next_actions.data_ptr(), hip.ptr(next_logp), hip.ptr(alpha), N, float(gamma), grads.data_ptr(),
             stats.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_rlpd_q_loss_fwd_bwd")
-        object.__setattr__(self, "last_stats", stats)
-        object.__setattr__(self, "last_pair", (p0, p1))
-        params = self._ens.parameters()
-        return _FusedDenoiseLoss.apply(stats[0], flat_views(grads, params), *params)
+        return self._td_tail(stats, grads, (p0, p1))
 
     def loss_actor(self, obs, alpha, inds=None, noise=None):
         """mean(-(1/E) sum_e q_e(s, a) + alpha logp(a)) on a reparameterised sample (reference :100-112), and d loss / d actor
@@ -191,9 +111,3 @@ class RLPD_Gaussian(SAC_Gaussian):
             object.__setattr__(self, name, v)
         params = net.trunk_parameters()
         return _FusedDenoiseLoss.apply(stats[0], flat_views(grad, params), *params)
-
-    def update_target_critic(self, tau):
-        """target <- target * (1 - tau) + source * tau over the whole [E][P] image in one call."""
-        t, s = self.target_flat_params(), self.critic_flat_params()
-        hip.check(hip.load().dppo_polyak(t.data_ptr(), s.data_ptr(), float(tau), t.numel(), hip.stream()), "dppo_polyak")
-        self._tens.mark_updated()

@@ -3,12 +3,13 @@
 (statistics, each actor gradient, each critic gradient) and the workspace size.  Two builds of the library compute the same
 thing exactly when their fingerprints are equal; DPPO_HIP_LIB selects the build, one build per process.
 
-    python tools/update_fingerprint.py --out a.json [--only hopper/bf16] [--knobs default,38=0,1=0]
+    python tools/update_fingerprint.py --out a.json [--only hopper/bf16,rlpd_] [--knobs default,38=0,1=0]
     python tools/update_fingerprint.py --compare a.json b.json
 
 Cases: ppo_update in rollout mode for seven network pairs in both precisions under eleven knob sets (hopper and halfcheetah at
 N = 1300 -- 21 row tiles, the last of 20 rows; the others at N = 6500, enough for the low-rank route at their width), and at the
-default knobs one case per other entry point, each built from its own test module's helpers."""
+default knobs one case per other entry point, each built from its own test module's helpers; for the LayerNorm-critic family
+(RLPD's, Cal-QL's and IBRL's critic and actor / acting entries) the two smallest fixture cases of each, with the workspace size."""
 import argparse
 import ctypes as C
 import hashlib
@@ -36,6 +37,11 @@ def sha(t):
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
 
 
+def wanted(only, name):
+    """``only``: substrings of case names, comma-separated; the empty string takes every case"""
+    return any(o in name for o in only.split(","))
+
+
 def grads_of(tag, net, out, flat=None):
     """one hash per parameter tensor: of its .grad, or of its slice of a flat gradient"""
     off = 0
@@ -56,7 +62,7 @@ def ppo_cases(only, knob_sets):
         for prec in ("fp32", "bf16"):
             sets = [k for k in knob_sets if sname != "ln_relu" or k == "default"]
             names = {k: f"ppo/{sname}/{prec}/{k}" for k in sets}
-            if not any(only in n for n in names.values()):
+            if not any(wanted(only, n) for n in names.values()):
                 continue
             Kft, R = 10, 800
             m, a, c = build_model(sname, dict(denoising_steps=20, ft_denoising_steps=Kft, randn_clip_value=3), 73, prec)
@@ -71,7 +77,7 @@ def ppo_cases(only, knob_sets):
             inds = torch.randperm(R * Kft, generator=gen)[:N].to(DEV).contiguous()
             ws = lib.dppo_ppo_workspace_bytes(C.byref(m.actor_ft.net_desc()), C.byref(m.critic.net_desc()), hip.PREC_BY_NAME[prec], N)
             for k in sets:
-                if only not in names[k]:
+                if not wanted(only, names[k]):
                     continue
                 knob = [int(x) for x in k.split("=")] if k != "default" else None
                 try:
@@ -203,6 +209,74 @@ def plain_case(case, prec):
     return out
 
 
+# The LayerNorm-critic family (RLPD, Cal-QL, IBRL): one fresh model per case, so that its grow-only workspace has the size the
+# entry's query answered; every tensor the entry writes.
+def rlpd_q_case(case, n, prec):
+    from tests import test_rlpd as R
+    m = R.make_model(case, prec, DEV, R.K.backup_entropy(case, n))
+    res = R.run_critic(m, case, n)
+    out = {"loss": sha(res["loss"]), "stats": sha(res["stats"]), "workspace_bytes": m._ws_q.buf.numel()}
+    out.update((f"q.{k}", sha(g)) for k, g in R.named_grads(m))
+    return out
+
+
+def rlpd_actor_case(case, n, prec):
+    from tests import test_rlpd_actor as R
+    m = R.make_model(case, prec, DEV)
+    res = R.run_actor(m, R.dev_inputs(case, n))
+    out = {k: sha(v) for k, v in res.items()}
+    out["workspace_bytes"] = m._ws_actor.buf.numel()
+    return out
+
+
+def calql_q_case(case, n, prec):
+    from tests import test_calql as Q
+    m = Q.make_model(case, n, prec, DEV)
+    res = Q.run_critic(m, case, n, False)
+    out = {"loss": sha(res["loss"]), "stats": sha(res["stats"]), "y": sha(res["y"]), "workspace_bytes": m._ws_calql.buf.numel()}
+    out.update((f"q.{k}", sha(g)) for k, g in Q.named_grads(m))
+    return out
+
+
+def calql_actor_case(case, prec):
+    from tests import test_calql_actor as Q
+    m = Q.make_model(case, prec, DEV)
+    res = Q.run_actor(m, Q.dev_inputs(case))
+    out = {k: sha(v) for k, v in res.items()}
+    out["workspace_bytes"] = m._ws_actor.buf.numel()
+    return out
+
+
+def ibrl_act_case(case, n, soft, prec):
+    from tests import test_ibrl as B
+    m = B.make_model(case, prec, DEV, soft)
+    out = {k: sha(v) for k, v in B.run_forward(m, case, n).items()}
+    out["workspace_bytes"] = m._ws_act.buf.numel()
+    return out
+
+
+def ibrl_q_case(case, n, prec):
+    from tests import test_ibrl as B
+    m = B.make_model(case, prec, DEV)
+    res = B.run_critic(m, case, n)
+    out = {"loss": sha(res["loss"]), "stats": sha(res["stats"]), "y": sha(res["y"]), "bc_share": sha(res["share"]),
+           "workspace_bytes": m._ws_q.buf.numel()}
+    out.update((f"q.{k}", sha(g)) for k, g in B.named_grads(m))
+    return out
+
+
+def ln_family_cases(table, prec):
+    for case, n in (("tiny", 77), ("chunk", 77)):  # chunk_77: RLPD's case without the entropy backup
+        table[f"rlpd_q/{case}_{n}/{prec}"] = lambda c=case, k=n: rlpd_q_case(c, k, prec)
+        table[f"rlpd_actor/{case}_{n}/{prec}"] = lambda c=case, k=n: rlpd_actor_case(c, k, prec)
+        table[f"calql_q/{case}_{n}/{prec}"] = lambda c=case, k=n: calql_q_case(c, k, prec)
+        table[f"calql_actor/{case}_{n}/{prec}"] = lambda c=case, k=n: calql_actor_case(f"{c}_{k}", prec)
+    for case, n in (("tiny", 77), ("chunk", 130)):  # E = 3 and 5: the stream rotation wraps; N off a tile boundary
+        for soft in (False, True):
+            table[f"ibrl_act/{case}_{n}_{'soft' if soft else 'greedy'}/{prec}"] = lambda c=case, k=n, s=soft: ibrl_act_case(c, k, s, prec)
+        table[f"ibrl_q/{case}_{n}/{prec}"] = lambda c=case, k=n: ibrl_q_case(c, k, prec)
+
+
 def other_cases(only):
     from tests.golden import make_golden_idql_cases as K
     table = {}
@@ -220,8 +294,9 @@ def other_cases(only):
         table[f"idql/{net}_{n}/{prec}"] = lambda a=net, b=n, p=prec: idql_case(a, b, p)
         for case in ("plain_ddpm", "plain_small_ddim"):
             table[f"plain/{case}/{prec}"] = lambda c=case, p=prec: plain_case(c, p)
+        ln_family_cases(table, prec)
     for name, fn in table.items():
-        if only in name:
+        if wanted(only, name):
             yield name, fn()
 
 
@@ -236,7 +311,7 @@ def compare(a, b):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
-    ap.add_argument("--only", default="", help="substring of the case names to run")
+    ap.add_argument("--only", default="", help="substrings of the case names to run, comma-separated")
     ap.add_argument("--knobs", default=",".join(KNOB_SETS))
     ap.add_argument("--compare", nargs=2)
     args = ap.parse_args()
