@@ -15,8 +15,10 @@ import time
 import numpy as np
 import torch
 
+from dppo_amd.agent.finetune.train_agent import episode_stats
 from dppo_amd.cfg.loader import instantiate
 from dppo_amd.env.synthetic import make_venv
+from dppo_amd.util.rollout import stack_obs
 
 log = logging.getLogger(__name__)
 
@@ -47,10 +49,7 @@ class EvalAgent:
         self.result_path = os.path.join(self.logdir, "result.npz")
 
     def reset_env_all(self, options_venv=None):
-        obs = self.venv.reset_arg(options_list=options_venv or [{} for _ in range(self.n_envs)])
-        if isinstance(obs, list):
-            obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
-        return obs
+        return stack_obs(self.venv.reset_arg(options_list=options_venv or [{} for _ in range(self.n_envs)]))
 
     def _cond(self, obs):
         out = {}
@@ -76,23 +75,14 @@ class EvalAgent:
         for step in range(S):
             action = self._act(self._cond(prev_obs)).cpu().numpy()[:, :self.act_steps]
             prev_obs, reward, terminated, truncated, _ = self.venv.step(action)
-            if isinstance(prev_obs, list):
-                prev_obs = {k: np.stack([o[k] for o in prev_obs]) for k in prev_obs[0]}
+            prev_obs = stack_obs(prev_obs)
             reward_trajs[step] = reward
             firsts[step + 1] = terminated | truncated
-        ep_reward, ep_best = [], []
-        for e in range(E):  # episodes that start and end inside the window (:82-120)
-            starts = np.where(firsts[:, e] == 1)[0]
-            for i in range(len(starts) - 1):
-                a, b = starts[i], starts[i + 1]
-                if b - a > 1:
-                    seg = reward_trajs[a:b, e]
-                    ep_reward.append(seg.sum())
-                    ep_best.append(seg.sum() if self.furniture_sparse_reward else seg.max() / self.act_steps)
-        n_ep = len(ep_reward)
-        res = {"num_episode": n_ep, "eval_success_rate": float(np.mean(np.array(ep_best) >= self.best_reward_threshold_for_success)) if n_ep else 0.0,
-               "eval_episode_reward": float(np.mean(ep_reward)) if n_ep else 0.0,
-               "eval_best_reward": float(np.mean(ep_best)) if n_ep else 0.0, "time": time.time() - t0}
+        # episodes that start and end inside the window (:82-120); furniture's sparse reward: an episode's best is its sum
+        avg_ep, avg_best, success, n_ep = episode_stats(firsts, reward_trajs, self.act_steps, self.best_reward_threshold_for_success,
+                                                        best_is_sum=self.furniture_sparse_reward)
+        res = {"num_episode": n_ep, "eval_success_rate": success, "eval_episode_reward": avg_ep, "eval_best_reward": avg_best,
+               "time": time.time() - t0}
         if not n_ep:
             log.info("[WARNING] No episode completed within the iteration!")
         log.info("eval: num episode %4d | success rate %8.4f | avg episode reward %8.4f | avg best reward %8.4f", n_ep,

@@ -1,6 +1,6 @@
-"""What the off-policy fine-tuning agents share (IDQL, QSM, DQL, SAC, RLPD, Cal-QL): the reference's ``TrainAgent`` set-up, the
-device-resident replay ring, one env step with its ``final_obs`` bootstrap and ring append, the episode statistics, the checkpoint,
-the logging tail, the iteration of the replay-ratio agents (IDQL, QSM, DQL) as ``run``, and that of the agents which explore at
+"""What the off-policy fine-tuning agents share (IDQL, QSM, DQL, SAC, RLPD, Cal-QL) on top of ``TrainAgent`` (set-up, checkpoint,
+episode statistics, logging tail): the device-resident replay ring, one env step with its ``final_obs`` bootstrap and ring append,
+the iteration of the replay-ratio agents (IDQL, QSM, DQL) as ``run``, and that of the agents which explore at
 random first and evaluate by an episode count (SAC, RLPD, Cal-QL) as ``run_by_episode_count``.
 
 A replay-ratio agent supplies its hyper-parameters and optimisers, ``nets`` and ``update_minibatch``; the defaults of
@@ -11,24 +11,18 @@ between the three is the handful of small methods in front of ``run_by_episode_c
 """
 from __future__ import annotations
 
-import logging
 import os
-import pickle
-import random
 import time
 
 import numpy as np
 import torch
 
-from dppo_amd.cfg.loader import instantiate
-from dppo_amd.env.synthetic import make_venv
+from dppo_amd.agent.finetune.train_agent import TrainAgent
 from dppo_amd.util.replay import DeviceReplay
-from dppo_amd.util.scheduler import CosineAnnealingWarmupRestarts
-
-log = logging.getLogger(__name__)
+from dppo_amd.util.rollout import stack_obs
 
 
-class OffPolicyAgent:
+class OffPolicyAgent(TrainAgent):
     nets = ()  # the model's networks whose kernel images follow a loaded checkpoint
     replay_cls = DeviceReplay  # the ring's class (Cal-QL's carries each transition's return)
     lr_schedulers = ("actor_lr_scheduler", "critic_lr_scheduler")  # stepped once per iteration, in this order
@@ -37,69 +31,16 @@ class OffPolicyAgent:
     log_keys = ("loss_actor", "loss_critic", "train_episode_reward", "time")
 
     def __init__(self, cfg, venv, who):
-        self.cfg = cfg
-        self.device = cfg.device
-        self.seed = cfg.get("seed", 42)
-        random.seed(self.seed)
-        np.random.seed(self.seed)
-        torch.manual_seed(self.seed)
-
-        # ---- TrainAgent (train_agent.py:21-120)
-        self.use_wandb = cfg.get("wandb", None) is not None
-        if self.use_wandb:
-            try:
-                import wandb
-                wandb.init(entity=cfg.wandb.entity, project=cfg.wandb.project, name=cfg.wandb.run, config=dict(cfg))
-                self._wandb = wandb
-            except ImportError:
-                log.warning("wandb is not installed; logging to the python logger and result.pkl only")
-                self.use_wandb = False
-        self.n_envs = cfg.env.n_envs
-        self.venv = venv if venv is not None else make_venv(cfg)
-        if hasattr(self.venv, "seed") and cfg.env.get("env_type", None) != "furniture":
-            self.venv.seed([self.seed + i for i in range(self.n_envs)])
-        self.n_cond_step, self.obs_dim, self.action_dim = cfg.cond_steps, cfg.obs_dim, cfg.action_dim
-        self.act_steps, self.horizon_steps = cfg.act_steps, cfg.horizon_steps
-        # the stored action chunk is the critic's action and the actor loss's x_start (reference IDQL :298-301, QSM :236-264)
-        assert self.act_steps == self.horizon_steps, f"{who} needs act_steps == horizon_steps"
-        self.reset_at_iteration = cfg.env.get("reset_at_iteration", True)
-        self.batch_size = cfg.train.batch_size
-        self.model = instantiate(cfg.model)
-        self.itr = 0
-        self.n_train_itr, self.val_freq = cfg.train.n_train_itr, cfg.train.val_freq
-        self.force_train = cfg.train.get("force_train", False)
-        self.n_steps = cfg.train.n_steps
-        self.best_reward_threshold_for_success = cfg.env.get("best_reward_threshold_for_success", 0)
-        self.max_grad_norm = cfg.train.get("max_grad_norm", None)
-        self.logdir = cfg.logdir
-        self.checkpoint_dir = os.path.join(self.logdir, "checkpoint")
-        self.result_path = os.path.join(self.logdir, "result.pkl")
-        os.makedirs(self.checkpoint_dir, exist_ok=True)
-        self.log_freq = cfg.train.get("log_freq", 1)
-        self.save_model_freq = cfg.train.save_model_freq
-        # ---- what every off-policy agent of the reference reads from cfg.train
-        self.gamma = cfg.train.gamma  # applied to the reward of every act_steps env steps
+        # the stored action chunk is the critic's action and the actor loss's x_start (reference IDQL :298-301, QSM :236-264);
+        # checked before wandb, the env and the model are set up
+        assert cfg.act_steps == cfg.horizon_steps, f"{who} needs act_steps == horizon_steps"
+        super().__init__(cfg, venv)
+        # ---- what every off-policy agent of the reference reads from cfg.train (gamma: applied to the reward of every act_steps
+        # env steps)
         self.scale_reward_factor = cfg.train.scale_reward_factor
         self.buffer_size = cfg.train.buffer_size
         self.replay = self.replay_cls(self.buffer_size, self.n_envs, self.n_cond_step * self.obs_dim,
                                    self.act_steps * self.action_dim, self.device)
-
-    @staticmethod
-    def _cosine(opt, sched_cfg, lr):
-        return CosineAnnealingWarmupRestarts(opt, first_cycle_steps=sched_cfg.first_cycle_steps, cycle_mult=1.0, max_lr=lr,
-                                             min_lr=sched_cfg.min_lr, warmup_steps=sched_cfg.warmup_steps, gamma=1.0)
-
-    def reset_env_all(self, options_venv=None):
-        obs = self.venv.reset_arg(options_list=options_venv or [{} for _ in range(self.n_envs)])
-        if isinstance(obs, list):
-            obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
-        return obs
-
-    def save_model(self):
-        """checkpoint/state_{itr}.pt = {"itr", "model": state_dict} (train_agent.py:125-135)."""
-        path = os.path.join(self.checkpoint_dir, f"state_{self.itr}.pt")
-        torch.save({"itr": self.itr, "model": self.model.state_dict()}, path)
-        log.info("Saved model to %s", path)
 
     def load(self, itr):
         data = torch.load(os.path.join(self.checkpoint_dir, f"state_{itr}.pt"), weights_only=True)
@@ -115,8 +56,7 @@ class OffPolicyAgent:
         the episode ended in (reference IDQL :171-177).  The env's own array is copied before the first such write.
         Returns (observation dict, reward, done)."""
         obs, reward, terminated, truncated, info = self.venv.step(action)
-        if isinstance(obs, list):
-            obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
+        obs = stack_obs(obs)
         if not eval_mode:
             nxt = obs["state"]
             for i in np.where(truncated)[0]:
@@ -128,41 +68,6 @@ class OffPolicyAgent:
             self.replay.append(state, nxt, stored, np.asarray(reward) * self.scale_reward_factor,
                                np.asarray(terminated).astype(np.float32))
         return obs, reward, terminated | truncated
-
-    def _episode_stats(self, firsts, reward_trajs):
-        """(average episode reward, average best reward, success rate) over the episodes that finish within the iteration
-        (reference :190-225)."""
-        ep_rewards, ep_best = [], []
-        for e in range(self.n_envs):
-            starts = np.where(firsts[:, e] == 1)[0]
-            for i in range(len(starts) - 1):
-                a, b = starts[i], starts[i + 1]
-                if b - a > 1:
-                    seg = reward_trajs[a:b, e]
-                    ep_rewards.append(seg.sum())
-                    ep_best.append(seg.max() / self.act_steps)
-        n_ep = len(ep_rewards)
-        avg_ep = float(np.mean(ep_rewards)) if n_ep else 0.0
-        avg_best = float(np.mean(ep_best)) if n_ep else 0.0
-        success = float(np.mean(np.array(ep_best) >= self.best_reward_threshold_for_success)) if n_ep else 0.0
-        return avg_ep, avg_best, success
-
-    def log_record(self, run_results, rec, t_start, eval_mode, stats, train_fields):
-        """A logging iteration's tail: ``time`` and the evaluation's or the training's fields into ``rec``, the log line, wandb,
-        ``rec`` onto ``run_results`` and all of it into result.pkl."""
-        avg_ep, avg_best, success = stats
-        rec["time"] = time.time() - t_start
-        if eval_mode:
-            rec.update(eval_success_rate=success, eval_episode_reward=avg_ep, eval_best_reward=avg_best)
-            log.info("eval: success rate %8.4f | avg episode reward %8.4f | avg best reward %8.4f", success, avg_ep, avg_best)
-        else:
-            rec.update(train_episode_reward=avg_ep, **train_fields)
-            log.info("%d: step %8d | " + self.log_line, rec["itr"], rec["step"], *[rec.get(k, float("nan")) for k in self.log_keys])
-        if self.use_wandb:
-            self._wandb.log({k: v for k, v in rec.items() if k != "itr"}, step=self.itr)
-        run_results.append(rec)
-        with open(self.result_path, "wb") as f:
-            pickle.dump(run_results, f)
 
     # ------------------------------------------------------------------------------------------------- IDQL, QSM, DQL
     def _sample(self, state, eval_mode):

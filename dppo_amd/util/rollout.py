@@ -1,6 +1,7 @@
 """Device-side rollout post-processing: GAE (reference agent/finetune/train_ppo_diffusion_agent.py:255-279)."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from dppo_amd import hip
@@ -32,6 +33,13 @@ def gae_device(reward: torch.Tensor, values: torch.Tensor, terminated: torch.Ten
 # double-buffered staging memory, and the env set may be split into groups that are software-pipelined: while the host
 # steps group g's simulators the device samples the action chunks of group g+1.
 # ----------------------------------------------------------------------------------------------------------------------
+def stack_obs(obs):
+    """What a vectorised env hands back, as one dict of (n_envs, ...) arrays: a list of per-env dicts is stacked key by key."""
+    if isinstance(obs, list):
+        obs = {k: np.stack([o[k] for o in obs]) for k in obs[0]}
+    return obs
+
+
 class PinnedHandoff:
     """obs numpy -> device tensor, action device tensor -> numpy, through two pinned staging buffers each way."""
 
@@ -83,8 +91,7 @@ class GroupedVecEnv:
 
     @staticmethod
     def _cat_obs(obs_list):
-        import numpy as np
-        obs_list = [{k: np.stack([x[k] for x in o]) for k in o[0]} if isinstance(o, list) else o for o in obs_list]
+        obs_list = [stack_obs(o) for o in obs_list]
         return {k: np.concatenate([o[k] for o in obs_list]) for k in obs_list[0]}
 
     def reset_arg(self, options_list=None):
@@ -93,7 +100,6 @@ class GroupedVecEnv:
                               for g, v in enumerate(self.groups)])
 
     def step(self, action):
-        import numpy as np
         n = self.groups[0].n_envs
         outs = [v.step(action[g * n:(g + 1) * n]) for g, v in enumerate(self.groups)]
         return (self._cat_obs([o[0] for o in outs]), np.concatenate([o[1] for o in outs]),
@@ -110,7 +116,6 @@ def collect_rollout(model, venv, prev_obs, n_steps: int, act_steps: int, obs_buf
     the other groups' simulators).  prev_obs: {"state": (n_envs, To, Do)} numpy.  Returns (reward (S,E), terminated (S,E),
     done (S,E), last obs dict) as numpy, like the reference's holders (:78-93).
     """
-    import numpy as np
     groups = getattr(venv, "groups", [venv])
     G = len(groups)
     E = obs_buf.shape[0] // n_steps
@@ -160,9 +165,7 @@ def collect_rollout(model, venv, prev_obs, n_steps: int, act_steps: int, obs_buf
         for g in range(G):
             action = handoffs[g].action_numpy(tickets[g])[:, :act_steps]
             o, r, term, trunc, _ = groups[g].step(action)
-            if isinstance(o, list):
-                o = {k: np.stack([x[k] for x in o]) for k in o[0]}
-            obs_g[g] = o["state"]
+            obs_g[g] = stack_obs(o)["state"]
             sl = slice(g * n, (g + 1) * n)
             reward[step, sl], terminated[step, sl], done[step, sl] = r, term, term | trunc
             if step + 1 < n_steps:  # the next sampler call of this group runs while the host steps the other groups
