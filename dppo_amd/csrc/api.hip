@@ -381,6 +381,20 @@ static int64_t ws_bytes(int prec, F carve) {
   Carver c{nullptr, 0, 0};
   return (int64_t)(prec == DPPO_PREC_F32 ? carve(c, F32{}) : carve(c, BF16{}));
 }
+// ... and its counterpart at the head of the driver: carve(c) runs the same carve_* function against the caller's buffer and fills
+// the driver's workspace struct; a short buffer (need_ws: or none) is refused
+template <class F>
+static int carve_ws(void* ws, int64_t wsb, F carve, bool need_ws = false) {
+  Carver c{(char*)ws, 0, (size_t)wsb};
+  const size_t need = carve(c);
+  if ((need_ws && !ws) || (int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  return 0;
+}
+// the row count of a call: one int's worth
+static int check_rows(int64_t N) {
+  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  return 0;
+}
 
 // Which kernels one network's fused backward launches, and on which streams: decided once per network per call (its shape step
 // at the head of carve_mlp, plan_route() right behind the carve) and only READ from there on -- by carve_mlp, the row builders' callers,
@@ -2067,7 +2081,7 @@ static size_t carve_gauss(Carver& c, const dppo_net_desc& a, const dppo_net_desc
 }
 int64_t dppo_gaussian_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* critic, int prec, int64_t N) {
   if (check_net(actor) || (critic && check_net(critic)) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   return ws_bytes(prec, [&](Carver& c, auto p) {
     MlpBufs<decltype(p)> A, Cb;
     double *m, *sc, *pa;
@@ -2079,11 +2093,9 @@ static int gauss_infer_impl(const dppo_net_desc& d, const float* prm, const char
                             const float* logvar, const float* obs, const float* noise, const float* actions, int64_t N,
                             float* out_actions, float* out_mean, float* out_logp, void* ws, int64_t wsb, hipStream_t s,
                             const dppo_dropout* drop = nullptr) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> A, Cb;
   double *m, *sc, *pa;
-  const size_t need = carve_gauss<P>(c, d, nullptr, N, false, A, Cb, m, sc, pa);
-  if (!ws || (int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_gauss<P>(c, d, nullptr, N, false, A, Cb, m, sc, pa); }, true)) return e;
   const PackLayout L = pack_layout<P>(d, 0);
   launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, d.cond_dim, N, A.in, L.Kp0, s);
   mlp_forward<P>(d, prm, pk, L, N, A, false, s, nullptr, false, drop);
@@ -2147,7 +2159,7 @@ int dppo_gaussian_logprob(const dppo_net_desc* actor, int prec, const float* par
   if (int e = check_gauss(actor, cfg, logvar)) return e;
   if (int e = check_prec(prec)) return e;
   if (!params || !packed || !obs || !actions || !logp) return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
 #define CALL(P)                                                                                                        \
   gauss_infer_impl<P>(*actor, params, (const char*)packed, *cfg, logvar, obs, nullptr, actions, N, nullptr, nullptr, logp, \
                       workspace, workspace_bytes, (hipStream_t)stream)
@@ -2160,11 +2172,10 @@ static int gauss_ppo_impl(const dppo_net_desc& a, const dppo_net_desc& cr, const
                           const float* actions, const float* returns, const float* oldvalues, const float* adv,
                           const float* oldlogp, int64_t N, const double* gmom, float* agrad, float* cgrad, float* lvgrad,
                           double* stats, void* ws, int64_t wsb, hipStream_t s, const dppo_obs_io* oio = nullptr) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> A, Cb;
   double *moments, *scratch, *partial;
-  const size_t need = carve_gauss<P>(c, a, &cr, N, true, A, Cb, moments, scratch, partial);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_gauss<P>(c, a, &cr, N, true, A, Cb, moments, scratch, partial); }))
+    return e;
   const PackLayout LA = pack_layout<P>(a, 0), LC = pack_layout<P>(cr, 0);
   // the critic pipeline on the side stream beside the actor's forward (one fork here, one join at the end)
   hipStream_t s2 = fork_side(s);
@@ -2245,7 +2256,7 @@ int dppo_gaussian_ppo_loss_fwd_bwd_obs(const dppo_net_desc* actor, const dppo_ne
 // ---- Gaussian behaviour cloning (GaussianModel.loss): the training buffers of one trunk, no critic ----------------------------
 int64_t dppo_gaussian_bc_workspace_bytes(const dppo_net_desc* actor, int prec, int64_t N) {
   if (check_net(actor) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   return ws_bytes(prec, [&](Carver& c, auto p) {
     MlpBufs<decltype(p)> A, Cb;
     double *m, *sc, *pa;
@@ -2256,11 +2267,10 @@ template <class P>
 static int gauss_bc_impl(const dppo_net_desc& a, const float* ap, const char* ak, const dppo_gaussian_cfg& cfg,
                          const float* logvar, const float* obs, const float* actions, int64_t N, double ent_coef, float* agrad,
                          float* lvgrad, double* out, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> A, Cb;
   double *moments, *scratch, *partial;
-  const size_t need = carve_gauss<P>(c, a, nullptr, N, true, A, Cb, moments, scratch, partial);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_gauss<P>(c, a, nullptr, N, true, A, Cb, moments, scratch, partial); }))
+    return e;
   const PackLayout LA = pack_layout<P>(a, 0);
   launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, a.cond_dim, N, A.in, LA.Kp0, s);
   mlp_forward<P>(a, ap, ak, LA, N, A, true, s);
@@ -2281,7 +2291,7 @@ int dppo_gaussian_bc_loss_fwd_bwd(const dppo_net_desc* actor, int prec, const fl
   if (!params || !packed || !obs || !actions || !grad || !loss_entropy || !workspace) return fail(-1, "null pointer");
   if (int e = check_gauss_train(actor, cfg, logvar_grad)) return e;
   if (cfg->deterministic) return fail(-1, "the behaviour-cloning loss is not defined for deterministic = 1");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
 #define CALL(P)                                                                                                              \
   gauss_bc_impl<P>(*actor, params, (const char*)packed, *cfg, logvar, obs, actions, N, ent_coef, grad, logvar_grad, loss_entropy, \
                    workspace, workspace_bytes, (hipStream_t)stream)
@@ -2329,7 +2339,7 @@ static size_t carve_gmm(Carver& c, const dppo_net_desc& am, const dppo_net_desc&
 int64_t dppo_gmm_workspace_bytes(const dppo_net_desc* mean, const dppo_net_desc* weights, const dppo_net_desc* critic, int prec,
                                  int64_t N) {
   if (check_net(mean) || check_net(weights) || (critic && check_net(critic)) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   return ws_bytes(prec, [&](Carver& c, auto p) {
     MlpBufs<decltype(p)> Am, Aw, Cb;
     double *m, *sc, *pa;
@@ -2341,11 +2351,10 @@ static int gmm_infer_impl(const dppo_net_desc& am, const dppo_net_desc& aw, cons
                           const char* wk, const dppo_gmm_cfg& cfg, const float* logvar, const float* obs, const int64_t* modes,
                           const float* noise, const float* actions, int64_t N, float* out_actions, float* out_logp, void* ws,
                           int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> Am, Aw, Cb;
   double *moments, *scratch, *partial;
-  const size_t need = carve_gmm<P>(c, am, aw, nullptr, N, GMM_MAX_MODES * 64, false, Am, Aw, Cb, moments, scratch, partial);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_gmm<P>(c, am, aw, nullptr, N, GMM_MAX_MODES * 64, false, Am, Aw, Cb, moments, scratch, partial); }))
+    return e;
   const PackLayout LM = pack_layout<P>(am, 0), LW = pack_layout<P>(aw, 0);
   launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, am.cond_dim, N, Am.in, LM.Kp0, s);
   launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, aw.cond_dim, N, Aw.in, LW.Kp0, s);
@@ -2382,7 +2391,7 @@ int dppo_gmm_logprob(const dppo_net_desc* mean, const dppo_net_desc* weights, in
   if (int e = check_prec(prec)) return e;
   if (!mean_params || !mean_packed || !weights_params || !weights_packed || !obs || !actions || !logp || !workspace)
     return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
 #define CALL(P)                                                                                                                \
   gmm_infer_impl<P>(*mean, *weights, mean_params, (const char*)mean_packed, weights_params, (const char*)weights_packed, *cfg, logvar, \
                     obs, nullptr, nullptr, actions, N, nullptr, logp, workspace, workspace_bytes, (hipStream_t)stream)
@@ -2395,11 +2404,10 @@ static int gmm_ppo_impl(const dppo_net_desc& am, const dppo_net_desc& aw, const 
                         const float* logvar, const float* obs, const float* actions, const float* returns, const float* oldvalues,
                         const float* adv, const float* oldlogp, int64_t N, const double* gmom, float* mgrad, float* wgrad,
                         float* cgrad, float* lvgrad, double* stats, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> Am, Aw, Cb;
   double *moments, *scratch, *partial;
-  const size_t need = carve_gmm<P>(c, am, aw, &cr, N, GMM_MAX_MODES * 64, true, Am, Aw, Cb, moments, scratch, partial);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_gmm<P>(c, am, aw, &cr, N, GMM_MAX_MODES * 64, true, Am, Aw, Cb, moments, scratch, partial); }))
+    return e;
   const PackLayout LM = pack_layout<P>(am, 0), LW = pack_layout<P>(aw, 0), LC = pack_layout<P>(cr, 0);
   hipStream_t s2 = fork_side(s);  // the critic pipeline beside the two actor trunks
   launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, cr.cond_dim, N, Cb.in, LC.Kp0, s2);
@@ -2453,7 +2461,7 @@ int dppo_gmm_ppo_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* we
 // ---- GMM behaviour cloning (GMMModel.loss): the training buffers of the two trunks, no critic -----------------------------------
 int64_t dppo_gmm_bc_workspace_bytes(const dppo_net_desc* mean, const dppo_net_desc* weights, int prec, int64_t N) {
   if (check_net(mean) || check_net(weights) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   return ws_bytes(prec, [&](Carver& c, auto p) {
     MlpBufs<decltype(p)> Am, Aw, Cb;
     double *m, *sc, *pa;
@@ -2464,11 +2472,10 @@ template <class P>
 static int gmm_bc_impl(const dppo_net_desc& am, const dppo_net_desc& aw, const float* mp, const char* mk, const float* wp,
                        const char* wk, const dppo_gmm_cfg& cfg, const float* logvar, const float* obs, const float* actions,
                        int64_t N, float* mgrad, float* wgrad, float* lvgrad, double* out, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> Am, Aw, Cb;
   double *moments, *scratch, *partial;
-  const size_t need = carve_gmm<P>(c, am, aw, nullptr, N, GMM_MAX_MODES * 64, true, Am, Aw, Cb, moments, scratch, partial);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_gmm<P>(c, am, aw, nullptr, N, GMM_MAX_MODES * 64, true, Am, Aw, Cb, moments, scratch, partial); }))
+    return e;
   const PackLayout LM = pack_layout<P>(am, 0), LW = pack_layout<P>(aw, 0);
   hipStream_t s2 = fork_side(s);  // the weights trunk beside the mean trunk, forward and backward
   launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, aw.cond_dim, N, Aw.in, LW.Kp0, s2);
@@ -2501,7 +2508,7 @@ int dppo_gmm_bc_loss_fwd_bwd(const dppo_net_desc* mean, const dppo_net_desc* wei
   if (int e = check_gmm_train(cfg, logvar_grad)) return e;
   if (cfg->std_mode == 0 && !(cfg->fixed_std > 0)) return fail(-1, "fixed_std must be positive");
   if (cfg->deterministic) return fail(-1, "the behaviour-cloning loss is not defined for deterministic = 1");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
 #define CALL(P)                                                                                                                   \
   gmm_bc_impl<P>(*mean, *weights, mean_params, (const char*)mean_packed, weights_params, (const char*)weights_packed, *cfg, logvar, \
                  obs, actions, N, mean_grad, weights_grad, logvar_grad, loss_entropy, workspace, workspace_bytes,                 \
@@ -2552,10 +2559,8 @@ static int unet_ppo_impl(const dppo_unet_desc& u, const dppo_net_desc& cr, const
                          const float* adv_k, const float* logprobs_k, const int64_t* inds, const int64_t* kinds, int64_t N,
                          const double* gmom, float* agrad, float* cgrad, double* stats, void* ws, int64_t wsb, hipStream_t s,
                          const dppo_obs_io* oio = nullptr) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   UnetPpoWs<P> W;
-  const size_t need = carve_unet_ppo<P>(c, u, &cr, N, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_unet_ppo<P>(c, u, &cr, N, W); })) return e;
   const PackLayout LC = pack_layout<P>(cr, 0);
   const int Kft = pcfg.ft_denoising_steps, AF = u.horizon_steps * u.action_dim;
   BuildRows br;  // critic rows + the zeroing / loss table side jobs; the conv actor builds its own input images
@@ -2664,10 +2669,8 @@ template <class P>
 static int unet_mse_impl(const dppo_unet_desc& u, const float* prm, const char* pk, const dppo_step* tsteps, int n_time,
                          const float* obs, const float* pairs, const int64_t* kinds, int64_t N, float* grad, double* loss,
                          void* ws, int64_t wsb, hipStream_t s, float* d_obs = nullptr) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   UnetPpoWs<P> W;
-  const size_t need = carve_unet_ppo<P>(c, u, nullptr, N, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_unet_ppo<P>(c, u, nullptr, N, W); })) return e;
   const int AF = u.horizon_steps * u.action_dim;
   launch_unet_index(nullptr, kinds, n_time, N, W.brow, W.krow, s);
   UnetTrainer<P>* T = unet_trainer_new<P>(u, prm, pk, N, W.uws, W.ubytes, s);
@@ -2764,7 +2767,7 @@ static int64_t idql_ws_bytes(const dppo_net_desc* q, const dppo_net_desc* v, int
                              bool train_v) {
   // (no V, no training: dppo_idql_q_forward, which reads one LayerNorm trunk -- a twin of them is not built)
   if ((v ? check_idql_pair(q, v) : check_idql_q(q, !double_q && !train_q)) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   return ws_bytes(prec, [&](Carver& c, auto p) {
     IdqlWs<decltype(p)> W;
     return carve_idql<decltype(p)>(c, *q, v, N, double_q != 0, train_q, train_v, W);
@@ -2790,10 +2793,8 @@ template <class P>
 static int idql_v_impl(const dppo_net_desc& q, const dppo_net_desc& v, const float* tp, const char* tk1, const char* tk2,
                        const float* vp, const char* vk, const dppo_idql_batch& b, int64_t N, double tau, bool twin, float* vgrad,
                        float* adv, double* stats, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   IdqlWs<P> W;
-  const size_t need = carve_idql<P>(c, q, &v, N, twin, false, true, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_idql<P>(c, q, &v, N, twin, false, true, W); })) return e;
   const PackLayout LQ = pack_layout<P>(q, 0), LV = pack_layout<P>(v, 0);
   IdqlRows r = idql_rows_of(b, N, v.cond_dim, q.in_dim - v.cond_dim);
   r.q1in = W.Q1.in, r.q2in = twin ? W.Q2.in : nullptr, r.vin = W.V.in, r.KpQ = LQ.Kp0, r.KpV = LV.Kp0;
@@ -2827,7 +2828,7 @@ int dppo_idql_v_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int
   if (!target_q_params || !target_q1_packed || (double_q && !target_q2_packed) || !v_params || !v_packed || !v_grad || !stats ||
       !workspace)
     return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (int e = check_idql_batch(batch, N, RING_ACTIONS)) return e;
   if (!(expectile >= 0.0 && expectile <= 1.0)) return fail(-1, "expectile tau=%g outside [0, 1]", expectile);
 #define CALL(P)                                                                                                                \
@@ -2841,10 +2842,8 @@ template <class P>
 static int idql_q_impl(const dppo_net_desc& q, const dppo_net_desc& v, const float* qp, const char* qk1, const char* qk2,
                        const float* vp, const char* vk, const dppo_idql_batch& b, int64_t N, double gamma, bool twin, float* qgrad,
                        double* stats, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   IdqlWs<P> W;
-  const size_t need = carve_idql<P>(c, q, &v, N, twin, true, false, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_idql<P>(c, q, &v, N, twin, true, false, W); })) return e;
   const PackLayout LQ = pack_layout<P>(q, 0), LV = pack_layout<P>(v, 0);
   const int64_t nq = param_layout(q).total;
   IdqlRows r = idql_rows_of(b, N, v.cond_dim, q.in_dim - v.cond_dim);
@@ -2881,7 +2880,7 @@ int dppo_idql_q_loss_fwd_bwd(const dppo_net_desc* q, const dppo_net_desc* v, int
   if (int e = check_prec(prec)) return e;
   if (!q_params || !q1_packed || (double_q && !q2_packed) || !v_params || !v_packed || !q_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (int e = check_idql_batch(batch, N, RING_TRANSITION)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                  \
@@ -2894,10 +2893,8 @@ template <class P>
 static int idql_fwd_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const float* obs, int OD,
                          int64_t obs_rows, const float* actions, int64_t N, bool twin, float* q1o, float* q2o, void* ws,
                          int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   IdqlWs<P> W;
-  const size_t need = carve_idql<P>(c, q, nullptr, N, twin, false, false, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_idql<P>(c, q, nullptr, N, twin, false, false, W); })) return e;
   const PackLayout LQ = pack_layout<P>(q, 0);
   IdqlRows r;
   memset(&r, 0, sizeof(r));
@@ -2921,7 +2918,7 @@ int dppo_idql_q_forward(const dppo_net_desc* q, int prec, const float* q_params,
   if (int e = check_prec(prec)) return e;
   if (!q_params || !q1_packed || !obs || !actions || !q1_out || !workspace || (double_q && (!q2_packed || !q2_out)))
     return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (obs_rows < 1 || obs_rows > N) return fail(-1, "obs_rows out of [1, N]");
   if (obs_dim < 1 || obs_dim >= q->in_dim)
     return fail(-1, "Q descriptor does not pair with obs_dim=%d: in_dim=%d must be obs_dim + the action width", obs_dim, q->in_dim);
@@ -2968,85 +2965,97 @@ static int check_qsm_plain(const dppo_net_desc* q) {
   if (qsm_tail_rows(2 * q->hidden) < 1) return fail(-1, "hidden=%d too wide for the action-gradient tail", q->hidden);
   return 0;
 }
+// M Q trunks' forward buffers with the pre-activations kept, and what their action-gradient chains need: nothing of a parameter
+// backward (no slab, no column-sum partials).  QSM's target: M = 2; the actor losses' workspace (QActorWs) builds on it.
 template <class P>
-struct QsmWs {
-  MlpBufs<P> Q1, Q2;
-  void *dza[2], *dzb[2];  // the chain's two alternating [N][H] buffers, per trunk
-  void* dhcat;            // [N][2H] elem: [dh_0 of Q1 | dh_0 of Q2]
-  void* w0a;              // [AD][2H] elem: the action columns of the two W0, stacked along K
+struct QChainWs {
+  MlpBufs<P> Q[RLPD_MAX_E];
+  void *dza[RLPD_MAX_E], *dzb[RLPD_MAX_E];  // trunk i's two alternating [N][H] chain buffers; dza[i] takes the seed
+  void* dhcat;                              // [N][M H] elem: trunk i's dh_0 in columns [i H, (i + 1) H)
+  void* w0a;                                // [AF][M H] elem: the action columns of the M W0, stacked along K
 };
-// forward buffers with the pre-activations kept, and nothing of a parameter backward (no slab, no column-sum partials)
 template <class P>
-static size_t carve_qsm_target(Carver& c, const dppo_net_desc& q, int AD, int64_t N, QsmWs<P>& W) {
+static size_t carve_q_chains(Carver& c, const dppo_net_desc& q, int AF, int64_t N, int M, QChainWs<P>& W) {
   const size_t ES = P::ESIZE;
-  carve_mlp<P>(c, q, N, true, false, W.Q1);
-  carve_mlp<P>(c, q, N, true, false, W.Q2);
-  for (int i = 0; i < 2; ++i) {
+  for (int i = 0; i < M; ++i) {
+    carve_mlp<P>(c, q, N, true, false, W.Q[i]);
     W.dza[i] = c.take((size_t)N * q.hidden * ES);
     W.dzb[i] = c.take((size_t)N * q.hidden * ES);
   }
-  W.dhcat = c.take((size_t)N * 2 * q.hidden * ES);
-  W.w0a = c.take((size_t)AD * 2 * q.hidden * ES);
+  W.dhcat = c.take((size_t)N * M * q.hidden * ES);
+  W.w0a = c.take((size_t)AF * M * q.hidden * ES);
   return al256(c.off);
 }
 int64_t dppo_qsm_actor_target_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
   if (check_qsm_q(q, obs_dim) || check_qsm_plain(q) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   return ws_bytes(prec, [&](Carver& c, auto p) {
-    QsmWs<decltype(p)> W;
-    return carve_qsm_target<decltype(p)>(c, *q, q->in_dim - obs_dim, N, W);
+    QChainWs<decltype(p)> W;
+    return carve_q_chains<decltype(p)>(c, *q, q->in_dim - obs_dim, N, 2, W);
   });
 }
-// The chain behind its seed: dza holds d q / d (pre-activation of the last hidden layer); data gradients only, down to dh_0 =
-// d q / d (layer 0's pre-activation), written into its half of dhcat (row stride 2H)
+// d q / d (layer 0's Linear output) of one plain trunk, into its columns of dhcat (row stride ldh), from a seed d q / d z_L that is
+// already in dza: data gradients only.  Per hidden layer from the top, the data GEMM with the act' epilogue (backward_plain's step
+// without its dW / db); a LayerNorm trunk runs the LayerNorm backward without parameter sums in front of each, and once more, in
+// place, on dh_0.  (Seeds: Wout (.) act'(z_L) by q_seeded_chain; the twin's choice per row by sac_select_kernel / calql_select_kernel.)
 template <class P>
-static void qsm_chain_gemms(const dppo_net_desc& q, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B, void* dza,
-                            void* dzb, void* dh0, hipStream_t s) {
+static void q_chain_from_seed(const dppo_net_desc& q, const float* prm, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B,
+                              void* dza, void* dzb, void* dh0, int ldh, hipStream_t s) {
+  const ParamLayout pl = param_layout(q);
   const int H = q.hidden, nb = q.n_blocks;
+  LnBwd ln;
+  memset(&ln, 0, sizeof(ln));
+  ln.ld = H, ln.ldx = H, ln.M = N, ln.H = H;  // (partial stays null: a data-gradient chain)
   void* dz = dza;
   void* other = dzb;
-  for (int b = nb - 1; b >= 0; --b) {  // dz <- (dz . W1_b) (.) act'(pre-activation below): backward_plain's step without its dW / db
+  for (int b = nb - 1; b >= 0; --b) {
+    if (q.use_layernorm) {
+      ln.dz = dz, ln.x = B.h[b + 1], ln.stats = B.ln_stats + (size_t)(b + 1) * N * 2, ln.gamma = prm + pl.n1w[b];
+      launch_ln_bwd<P>(ln, s);
+    }
     GemmNT g;
     memset(&g, 0, sizeof(g));
     g.M = (int)N, g.N = H, g.Kp = H, g.ldx = H, g.ldw = H;
     g.X = dz, g.W = pk + L.W1T[b], g.dsrc = b == 0 ? B.hpre[0] : B.z1[b - 1], g.dsrc_kind = 2, g.dsrc_ld = H, g.dact = q.act;
-    g.out_pre = b == 0 ? dh0 : other, g.ldo = b == 0 ? 2 * H : H;
+    g.out_pre = b == 0 ? dh0 : other, g.ldo = b == 0 ? ldh : H;
     launch_gemm_nt<P>(g, s);
     void* t = dz;
     dz = other, other = t;
   }
+  if (q.use_layernorm) {
+    ln.dz = dh0, ln.ld = ldh, ln.x = B.h[0], ln.stats = B.ln_stats, ln.gamma = prm + pl.n0w;
+    launch_ln_bwd<P>(ln, s);
+  }
 }
-// d q / d x of one plain trunk: the seed (out_dim is 1, so Wout is broadcast), then the chain
+// ... with the seed of the trunk's own Q in front (out_dim is 1, so Wout is broadcast): d q / d x of one trunk
 template <class P>
-static void qsm_action_chain(const dppo_net_desc& q, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B, void* dza,
-                             void* dzb, void* dh0, hipStream_t s) {
+static void q_seeded_chain(const dppo_net_desc& q, const float* prm, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B,
+                           void* dza, void* dzb, void* dh0, int ldh, hipStream_t s) {
   launch_qsm_seed<P>(pk + L.Wout, B.z1[q.n_blocks - 1], N, q.hidden, q.act, dza, s);
-  qsm_chain_gemms<P>(q, pk, L, N, B, dza, dzb, dh0, s);
+  q_chain_from_seed<P>(q, prm, pk, L, N, B, dza, dzb, dh0, ldh, s);
 }
 template <class P>
 static int qsm_target_impl(const dppo_net_desc& q, const float* qp, const char* qk1, const char* qk2, const dppo_idql_batch& b,
                            int OD, int64_t N, const float* noise, const int64_t* t, const float* sa, const float* sb, int K,
                            double coeff, float* pairs, float* obs_out, float* g_out, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
-  QsmWs<P> W;
+  QChainWs<P> W;
   const int AD = q.in_dim - OD, H = q.hidden;
-  const size_t need = carve_qsm_target<P>(c, q, AD, N, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_q_chains<P>(c, q, AD, N, 2, W); })) return e;
   const PackLayout L = pack_layout<P>(q, 0);
   const ParamLayout pl = param_layout(q);
   QsmRows r;
   memset(&r, 0, sizeof(r));
   r.ring = idql_rows_of(b, N, OD, AD);
   r.noise = noise, r.t = t, r.sa = sa, r.sb = sb, r.K = K, r.pairs = pairs, r.obs_out = obs_out;
-  r.q1in = W.Q1.in, r.q2in = W.Q2.in, r.KpQ = L.Kp0;
+  r.q1in = W.Q[0].in, r.q2in = W.Q[1].in, r.KpQ = L.Kp0;
   launch_qsm_rows<P>(r, s);
   // Q2's forward and chain on side stream 0 beside Q1's; the packing of the tail's weight operand rides in front of Q1's
   hipStream_t s2 = fork_side(s, 0);
-  mlp_forward<P>(q, qp + pl.total, qk2, L, N, W.Q2, true, s2);
-  qsm_action_chain<P>(q, qk2, L, N, W.Q2, W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, s2);
-  launch_qsm_pack_w0a<P>(qp, pl.total, pl.W0, q.in_dim, OD, AD, H, W.w0a, s);
-  mlp_forward<P>(q, qp, qk1, L, N, W.Q1, true, s);
-  qsm_action_chain<P>(q, qk1, L, N, W.Q1, W.dza[0], W.dzb[0], W.dhcat, s);
+  mlp_forward<P>(q, qp + pl.total, qk2, L, N, W.Q[1], true, s2);
+  q_seeded_chain<P>(q, qp + pl.total, qk2, L, N, W.Q[1], W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, 2 * H, s2);
+  launch_pack_w0a<P>(qp, pl.total, pl.W0, q.in_dim, OD, AD, H, 2, W.w0a, s);
+  mlp_forward<P>(q, qp, qk1, L, N, W.Q[0], true, s);
+  q_seeded_chain<P>(q, qp, qk1, L, N, W.Q[0], W.dza[0], W.dzb[0], W.dhcat, 2 * H, s);
   if (s2 != s) join_side(s, s2, 0);
   QsmTail tl;
   memset(&tl, 0, sizeof(tl));
@@ -3066,7 +3075,7 @@ int dppo_qsm_actor_target(const dppo_net_desc* q, int prec, const float* q_param
   if (!q_params || !q1_packed || !q2_packed || !noise || !t || !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || !pairs ||
       !obs_out || !workspace)
     return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (int e = check_idql_batch(batch, N, RING_ACTIONS)) return e;
   if (K < 1 || K > 1024) return fail(-1, "K=%d denoising steps outside [1, 1024]", K);
   if (!(coeff >= 0.0 && coeff <= 3.0e38)) return fail(-1, "q_grad_coeff=%g must be finite and >= 0", coeff);
@@ -3097,7 +3106,7 @@ static size_t carve_qsm_td(Carver& c, const dppo_net_desc& q, int64_t N, QsmTdWs
 }
 int64_t dppo_qsm_q_loss_workspace_bytes(const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
   if (check_qsm_q(q, obs_dim) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   return ws_bytes(prec, [&](Carver& c, auto p) {
     QsmTdWs<decltype(p)> W;
     return carve_qsm_td<decltype(p)>(c, *q, N, W);
@@ -3108,10 +3117,8 @@ static int twin_td_impl(const dppo_net_desc& q, const float* qp, const char* qk1
                         const char* tk2, const dppo_idql_batch& b, int OD, const float* next_actions, const float* next_logp,
                         const double* alpha, int64_t N, double gamma, float* qgrad, double* stats, void* ws, int64_t wsb,
                         hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   QsmTdWs<P> W;
-  const size_t need = carve_qsm_td<P>(c, q, N, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_qsm_td<P>(c, q, N, W); })) return e;
   const PackLayout L = pack_layout<P>(q, 0);
   const int64_t nq = param_layout(q).total;
   QsmTdRows r;
@@ -3157,7 +3164,7 @@ int dppo_qsm_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
   if (!q_params || !q1_packed || !q2_packed || !target_q_params || !target_q1_packed || !target_q2_packed || !next_actions ||
       !q_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (int e = check_idql_batch(batch, N, RING_TRANSITION)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                \
@@ -3248,14 +3255,12 @@ static int ensemble_td_impl(const dppo_net_desc& q, int E, const float* qp, cons
                             const void* const* tk, int p0, int p1, const dppo_idql_batch& b, int OD, const EnsembleBootstrap& bs,
                             int64_t N, double gamma, float* qgrad, double* stats, void* ws, int64_t wsb, hipStream_t s) {
   const bool ibrl = bs.next_bc != nullptr;
-  Carver c{(char*)ws, 0, (size_t)wsb};
   EnsembleTdWs<P> W;
-  const size_t need = carve_ensemble_td<P>(c, q, N, E, ibrl, W);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_ensemble_td<P>(c, q, N, E, ibrl, W); })) return e;
   // every member's buffers sit at one stride: the loss kernel reaches member e's from member 0's
   const int64_t q_stride = W.Q[1].out - W.Q[0].out, d_stride = (char*)W.Q[1].d_out - (char*)W.Q[0].d_out;
   bool even = true;
   for (int e = 1; e < E; ++e) even = even && W.Q[e].out - W.Q[0].out == e * q_stride && (char*)W.Q[e].d_out - (char*)W.Q[0].d_out == e * d_stride;
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
   if (!even) return fail(-1, "members' workspaces are not evenly spaced");
   const PackLayout L = pack_layout<P>(q, 0);
   const int64_t nq = param_layout(q).total;
@@ -3378,10 +3383,8 @@ static int ibrl_act_impl(const dppo_net_desc& a, const dppo_net_desc& q, const f
                          const float* obs, const float* noise_bc, const float* noise_rl, int64_t B, const IbrlSelect& sel_in,
                          float* a_bc_out, float* a_rl_out, float* q_bc_out, float* q_rl_out, uint8_t* took_out, void* ws, int64_t wsb,
                          hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   IbrlActWs<P> W;
-  const size_t need = carve_ibrl_act<P>(c, a, q, B, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_ibrl_act<P>(c, a, q, B, W); })) return e;
   const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
   const int AF = a.out_dim, OD = a.cond_dim;
   float* abc = a_bc_out ? a_bc_out : W.a_bc;
@@ -3496,60 +3499,51 @@ static int check_rlpd_pair(const dppo_net_desc* a, const dppo_net_desc* q, int o
   if (int e = check_rlpd_q(q, obs_dim, E)) return e;
   return check_sac_actor_q(a, q, obs_dim);
 }
-// An actor loss through M LayerNorm trunks (RLPD: the E members; Cal-QL: the twin, with its choice per row)
+// An actor loss through M Q trunks (RLPD: the E LayerNorm members; twin: SAC's plain pair and Cal-QL's LayerNorm pair, with their
+// choice per row): the chains' buffers, the actor's, and the head's rows
 template <class P>
-struct LnActorWs {
-  MlpBufs<P> A, Q[RLPD_MAX_E];
-  void *dza[RLPD_MAX_E], *dzb[RLPD_MAX_E];  // trunk i's two alternating [N][H] chain buffers; dza[i] takes the seed
-  void* dhcat;                              // [N][M H] elem: trunk i's dx_0 in columns [i H, (i + 1) H)
-  void* w0a;                                // [AF][M H] elem
+struct QActorWs : QChainWs<P> {
+  MlpBufs<P> A;
   float *actions, *logp, *sig;
-  float* qsel;    // Cal-QL only, as sel
-  float* dout32;  // bf16 only (SacTail::d_out32)
+  float* qsel;    // twin only, as sel
+  float* dout32;  // bf16 only: [N][2 AF] the head's gradient before its rounding to elem (SacTail::d_out32)
   uint8_t* sel;
 };
 template <class P>
-static size_t carve_ln_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, int M, bool calql, LnActorWs<P>& W) {
-  const size_t ES = P::ESIZE;
+static size_t carve_q_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, int M, bool twin, QActorWs<P>& W) {
   const int AF = a.out_dim / 2;
   carve_mlp<P>(c, a, N, true, true, W.A);
-  for (int i = 0; i < M; ++i) {
-    carve_mlp<P>(c, q, N, true, false, W.Q[i]);
-    W.dza[i] = c.take((size_t)N * q.hidden * ES);
-    W.dzb[i] = c.take((size_t)N * q.hidden * ES);
-  }
-  W.dhcat = c.take((size_t)N * M * q.hidden * ES);
-  W.w0a = c.take((size_t)AF * M * q.hidden * ES);
+  carve_q_chains<P>(c, q, AF, N, M, W);
   W.actions = (float*)c.take((size_t)N * AF * 4);
   W.logp = (float*)c.take((size_t)N * 4);
   W.sig = (float*)c.take((size_t)N * 4);
-  W.qsel = calql ? (float*)c.take((size_t)N * 4) : nullptr;
-  W.dout32 = ES == 4 ? nullptr : (float*)c.take((size_t)N * 2 * AF * 4);
-  W.sel = calql ? (uint8_t*)c.take((size_t)N) : nullptr;
+  W.qsel = twin ? (float*)c.take((size_t)N * 4) : nullptr;
+  W.dout32 = P::ESIZE == 4 ? nullptr : (float*)c.take((size_t)N * 2 * AF * 4);
+  W.sel = twin ? (uint8_t*)c.take((size_t)N) : nullptr;
   return al256(c.off);
 }
 int64_t dppo_rlpd_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
   if (check_rlpd_pair(actor, q, obs_dim, E) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   return ws_bytes(prec, [&](Carver& c, auto p) {
-    LnActorWs<decltype(p)> W;
-    return carve_ln_actor<decltype(p)>(c, *actor, *q, N, E, false, W);
+    QActorWs<decltype(p)> W;
+    return carve_q_actor<decltype(p)>(c, *actor, *q, N, E, false, W);
   });
 }
 // The front of such a loss, on s: the actor's rows [obs | 0], the W0 action columns of the M trunks as [AF][M H], the actor's forward
 // with the activations kept, and the head: sample, log-probability and ONE image of the critic's rows [obs | a | 0] that every trunk
-// reads.  -> the head, which the tail runs backwards.
+// reads (no forward writes its input rows).  -> the head, which the tail runs backwards.
 template <class P>
-static SacHead ln_actor_front(const dppo_net_desc& a, const dppo_net_desc& q, int M, const float* ap, const char* ak, const float* qp,
-                              const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N, const float* noise,
-                              LnActorWs<P>& W, float* actions, float* logp, hipStream_t s) {
+static SacHead q_actor_front(const dppo_net_desc& a, const dppo_net_desc& q, int M, const float* ap, const char* ak, const float* qp,
+                             const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N, const float* noise,
+                             QActorWs<P>& W, float* actions, float* logp, hipStream_t s) {
   const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
   const ParamLayout plq = param_layout(q);
   const int AF = a.out_dim / 2;
   IdqlRows r = idql_rows_of(b, N, OD, AF);
   r.vin = W.A.in, r.KpV = LA.Kp0;
   launch_idql_rows<P>(r, s);
-  launch_rlpd_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, q.hidden, M, W.w0a, s);
+  launch_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, q.hidden, M, W.w0a, s);
   mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
   SacHead h = sac_head_of(cfg, W.A.out, W.A.ldout, AF, noise, N);
   h.ring = idql_rows_of(b, N, OD, AF);
@@ -3558,70 +3552,43 @@ static SacHead ln_actor_front(const dppo_net_desc& a, const dppo_net_desc& q, in
   for (int i = 1; i < M; ++i) W.Q[i].in = W.Q[0].in;
   return h;
 }
-// The back, on s: one tail over the M trunks' dx_0 (E of them averaged; 1: the seeds carry the weights) whose epilogue is the head's
-// backward, the caller's statistics, the actor's backward.
+// The back, on s: one tail over the M trunks' dh_0 whose epilogue is the head's backward, the caller's statistics, the actor's
+// backward.  The tail is the one choice.  E >= 1: rlpd_tail_kernel, K = M H over a 16-lane butterfly, the sum divided by E (E members
+// averaged; 1: the seeds carry the weights).  E = 0: sac_tail_kernel, K = 2H in index order from LDS rows.  The two add in different
+// orders, so neither stands in for the other.
 static void launch_actor_stats(const RlpdActorStats& a, hipStream_t s) { launch_rlpd_actor_stats(a, s); }
 static void launch_actor_stats(const SacStats& a, hipStream_t s) { launch_sac_stats(a, s); }
 template <class P, class Stats>
-static void ln_actor_back(const dppo_net_desc& a, const dppo_net_desc& q, int M, int E, const float* ap, const char* ak,
-                          const SacHead& h, const double* alpha, const Stats& stats, int64_t N, LnActorWs<P>& W, float* grad, float* d_a,
-                          hipStream_t s) {
+static void q_actor_back(const dppo_net_desc& a, const dppo_net_desc& q, int M, int E, const float* ap, const char* ak,
+                         const SacHead& h, const double* alpha, const Stats& stats, int64_t N, QActorWs<P>& W, float* grad, float* d_a,
+                         hipStream_t s) {
   const PackLayout LA = pack_layout<P>(a, 0);
   const int AF = a.out_dim / 2;
-  RlpdTail tl;
-  memset(&tl, 0, sizeof(tl));
-  tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.K = M * q.hidden, tl.E = E, tl.alpha = alpha;
-  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
-  launch_rlpd_tail<P>(tl, s);
+  if (E > 0) {
+    RlpdTail tl;
+    memset(&tl, 0, sizeof(tl));
+    tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.K = M * q.hidden, tl.E = E, tl.alpha = alpha;
+    tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
+    launch_rlpd_tail<P>(tl, s);
+  } else {
+    SacTail tl;
+    memset(&tl, 0, sizeof(tl));
+    tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.H2 = M * q.hidden, tl.rows = qsm_tail_rows(M * q.hidden), tl.alpha = alpha;
+    tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
+    launch_sac_tail<P>(tl, s);
+  }
   launch_actor_stats(stats, s);
   mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s);
   if (W.dout32 != nullptr)  // the two heads' bias gradient again, from the unrounded rows
     launch_colsum<F32>(W.dout32, (int)N, 2 * AF, 2 * AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
-}
-// d q / d (layer 0's Linear output) of one LayerNorm trunk, into its columns of dhcat (row stride ldh), from a seed d q / d z_L that
-// is already in dza: per hidden layer from the top the LayerNorm backward without parameter sums and, except at layer 0, the data
-// GEMM with the act' epilogue.  (RLPD's members seed with Wout (.) act'(z_L); Cal-QL's twin with calql_select_kernel's weighted one.)
-template <class P>
-static void rlpd_chain_from_seed(const dppo_net_desc& q, const float* prm, const char* pk, const PackLayout& L, int64_t N,
-                                 MlpBufs<P>& B, void* dza, void* dzb, void* dh0, int ldh, hipStream_t s) {
-  const ParamLayout pl = param_layout(q);
-  const int H = q.hidden, nb = q.n_blocks;
-  LnBwd ln;
-  memset(&ln, 0, sizeof(ln));
-  ln.ld = H, ln.ldx = H, ln.M = N, ln.H = H;  // (partial stays null: a data-gradient chain)
-  void* dz = dza;
-  void* other = dzb;
-  for (int b = nb - 1; b >= 0; --b) {
-    ln.dz = dz, ln.x = B.h[b + 1], ln.stats = B.ln_stats + (size_t)(b + 1) * N * 2, ln.gamma = prm + pl.n1w[b];
-    launch_ln_bwd<P>(ln, s);
-    GemmNT g;
-    memset(&g, 0, sizeof(g));
-    g.M = (int)N, g.N = H, g.Kp = H, g.ldx = H, g.ldw = H;
-    g.X = dz, g.W = pk + L.W1T[b], g.dsrc = b == 0 ? B.hpre[0] : B.z1[b - 1], g.dsrc_kind = 2, g.dsrc_ld = H, g.dact = q.act;
-    g.out_pre = b == 0 ? dh0 : other, g.ldo = b == 0 ? ldh : H;
-    launch_gemm_nt<P>(g, s);
-    void* t = dz;
-    dz = other, other = t;
-  }
-  ln.dz = dh0, ln.ld = ldh, ln.x = B.h[0], ln.stats = B.ln_stats, ln.gamma = prm + pl.n0w;
-  launch_ln_bwd<P>(ln, s);
-}
-// ... with the seed of one member's own Q in front: Wout (.) act'(z_L)
-template <class P>
-static void rlpd_member_chain(const dppo_net_desc& q, const float* prm, const char* pk, const PackLayout& L, int64_t N, MlpBufs<P>& B,
-                              void* dza, void* dzb, void* dh0, int ldh, hipStream_t s) {
-  launch_qsm_seed<P>(pk + L.Wout, B.z1[q.n_blocks - 1], N, q.hidden, q.act, dza, s);
-  rlpd_chain_from_seed<P>(q, prm, pk, L, N, B, dza, dzb, dh0, ldh, s);
 }
 template <class P>
 static int rlpd_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, int E, const float* ap, const char* ak, const float* qp,
                            const void* const* qk, const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N,
                            const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
                            float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
-  LnActorWs<P> W;
-  const size_t need = carve_ln_actor<P>(c, a, q, N, E, false, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  QActorWs<P> W;
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_q_actor<P>(c, a, q, N, E, false, W); })) return e;
   const int64_t q_stride = W.Q[1].out - W.Q[0].out;
   for (int e = 1; e < E; ++e)
     if (W.Q[e].out - W.Q[0].out != e * q_stride) return fail(-1, "members' workspaces are not evenly spaced");
@@ -3629,21 +3596,21 @@ static int rlpd_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, int E
   const ParamLayout plq = param_layout(q);
   const int AF = a.out_dim / 2, H = q.hidden;
   float* logp = logp_out != nullptr ? logp_out : W.logp;
-  const SacHead h = ln_actor_front<P>(a, q, E, ap, ak, qp, cfg, b, OD, N, noise, W, actions_out != nullptr ? actions_out : W.actions, logp, s);
+  const SacHead h = q_actor_front<P>(a, q, E, ap, ak, qp, cfg, b, OD, N, noise, W, actions_out != nullptr ? actions_out : W.actions, logp, s);
   // the members take turns on the caller's stream and the three side streams: each runs its forward and its chain back to back
   hipStream_t st[4] = {s, fork_side(s, 0), fork_side(s, 1), fork_side(s, 2)};
   for (int e = 0; e < E; ++e) {
     const float* prm = qp + e * plq.total;
     mlp_forward<P>(q, prm, (const char*)qk[e], LQ, N, W.Q[e], true, st[e & 3]);
-    rlpd_member_chain<P>(q, prm, (const char*)qk[e], LQ, N, W.Q[e], W.dza[e], W.dzb[e], (char*)W.dhcat + (size_t)e * H * P::ESIZE,
-                         E * H, st[e & 3]);
+    q_seeded_chain<P>(q, prm, (const char*)qk[e], LQ, N, W.Q[e], W.dza[e], W.dzb[e], (char*)W.dhcat + (size_t)e * H * P::ESIZE,
+                      E * H, st[e & 3]);
   }
   for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
   RlpdActorStats sa;
   memset(&sa, 0, sizeof(sa));
   sa.q = W.Q[0].out, sa.q_stride = q_stride, sa.ldq = W.Q[0].ldout, sa.E = E, sa.logp = logp, sa.sig_row = W.sig, sa.alpha = alpha;
   sa.N = N, sa.AF = AF, sa.stats = stats;
-  ln_actor_back<P>(a, q, E, E, ap, ak, h, alpha, sa, N, W, grad, d_a, s);
+  q_actor_back<P>(a, q, E, E, ap, ak, h, alpha, sa, N, W, grad, d_a, s);
   return check_launch();
 }
 int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int E, const float* actor_params,
@@ -3658,7 +3625,7 @@ int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, 
   if (!actor_params || !actor_packed || !q_params || !q_packed || !alpha || !actor_grad || !stats || !workspace)
     return fail(-1, "null pointer");
   if (int e = check_member_images(q_packed, E)) return e;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (int e = check_idql_batch(batch, N, RING_OBS)) return e;
 #define CALL(P)                                                                                                                    \
   rlpd_actor_impl<P>(*actor, *q, E, actor_params, (const char*)actor_packed, q_params, q_packed, *cfg, *batch, obs_dim, N, noise,   \
@@ -3707,12 +3674,10 @@ static int calql_impl(const dppo_net_desc& q, const float* qp, const char* qk1, 
                       const float* next_actions, const float* pi_actions, const float* log_pi, const float* pi_next_actions,
                       const float* log_pi_next, const float* random_actions, int64_t N, double gamma, float* qgrad, double* stats,
                       float* y_out, float* random_out, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   CalqlWs<P> W;
   const int R = cfg.n_random, S = cfg.n_next;
   const int64_t M = N * (R + 3), MT = N * S;
-  const size_t need = carve_calql<P>(c, q, N, R, S, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_calql<P>(c, q, N, R, S, W); })) return e;
   const PackLayout L = pack_layout<P>(q, 0);
   const int64_t nq = param_layout(q).total;
   // both trunks read the same M rows, both targets the same N S rows: one image each
@@ -3784,49 +3749,62 @@ static int check_calql_pair(const dppo_net_desc* a, const dppo_net_desc* q, int 
   if (int e = check_calql_q(q, obs_dim, N, 1, 1)) return e;
   return check_sac_actor_q(a, q, obs_dim);
 }
-int64_t dppo_calql_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
-  if (check_calql_pair(actor, q, obs_dim, N) || check_prec(prec)) return -1;
+static int64_t twin_actor_ws_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int64_t N) {
   return ws_bytes(prec, [&](Carver& c, auto p) {
-    LnActorWs<decltype(p)> W;
-    return carve_ln_actor<decltype(p)>(c, *actor, *q, N, 2, true, W);
+    QActorWs<decltype(p)> W;
+    return carve_q_actor<decltype(p)>(c, *actor, *q, N, 2, true, W);
   });
 }
+int64_t dppo_calql_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
+  if (check_calql_pair(actor, q, obs_dim, N) || check_prec(prec)) return -1;
+  return twin_actor_ws_bytes(actor, q, prec, N);
+}
+// The actor's loss through the smaller Q of a twin, per row: SAC's (plain trunks) and Cal-QL's (LayerNorm trunks).  Between the shared
+// front and back, both forwards side by side, the choice per row, which seeds both chains, and the two chains side by side.  The
+// descriptor decides the three things that differ: the select kernel (SAC: a tie goes to Q1, the other trunk's seed is 0, sel_out is
+// a copy; Cal-QL: a tie's seeds are halves), the LayerNorm steps of the chain, and the tail (q_actor_back).
 template <class P>
-static int calql_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float* ap, const char* ak, const float* qp,
-                            const char* qk1, const char* qk2, const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N,
-                            const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
-                            uint8_t* sel_out, float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
-  LnActorWs<P> W;
-  const size_t need = carve_ln_actor<P>(c, a, q, N, 2, true, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+static int twin_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float* ap, const char* ak, const float* qp,
+                           const char* qk1, const char* qk2, const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N,
+                           const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
+                           uint8_t* sel_out, float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
+  QActorWs<P> W;
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_q_actor<P>(c, a, q, N, 2, true, W); })) return e;
   const PackLayout LQ = pack_layout<P>(q, 0);
-  const ParamLayout plq = param_layout(q);
   const int AF = a.out_dim / 2, H = q.hidden;
   float* logp = logp_out != nullptr ? logp_out : W.logp;
-  uint8_t* sel = sel_out != nullptr ? sel_out : W.sel;
-  const SacHead h = ln_actor_front<P>(a, q, 2, ap, ak, qp, cfg, b, OD, N, noise, W, actions_out != nullptr ? actions_out : W.actions, logp, s);
-  const float* prm[2] = {qp, qp + plq.total};
+  const SacHead h = q_actor_front<P>(a, q, 2, ap, ak, qp, cfg, b, OD, N, noise, W, actions_out != nullptr ? actions_out : W.actions, logp, s);
+  const float* prm[2] = {qp, qp + param_layout(q).total};
   const char* qk[2] = {qk1, qk2};
-  // both forwards side by side; the choice of the twin per row seeds both chains (the other trunk's seed is 0, a tie's are halves)
   hipStream_t s2 = fork_side(s, 0);
   mlp_forward<P>(q, prm[1], qk[1], LQ, N, W.Q[1], true, s2);
   mlp_forward<P>(q, prm[0], qk[0], LQ, N, W.Q[0], true, s);
   if (s2 != s) join_side(s, s2, 0);
-  CalqlSelect sl;
-  memset(&sl, 0, sizeof(sl));
-  sl.q1 = W.Q[0].out, sl.q2 = W.Q[1].out, sl.ldq = W.Q[0].ldout, sl.wout1 = qk[0] + LQ.Wout, sl.wout2 = qk[1] + LQ.Wout;
-  sl.z1 = W.Q[0].z1[q.n_blocks - 1], sl.z2 = W.Q[1].z1[q.n_blocks - 1], sl.N = N, sl.H = H, sl.act = q.act;
-  sl.dz1 = W.dza[0], sl.dz2 = W.dza[1], sl.sel = sel, sl.qsel = W.qsel;
-  launch_calql_select<P>(sl, s);
+  auto twin_of = [&](auto& sl) {  // what both select kernels read, and the two seeds they write
+    memset(&sl, 0, sizeof(sl));
+    sl.q1 = W.Q[0].out, sl.q2 = W.Q[1].out, sl.ldq = W.Q[0].ldout, sl.wout1 = qk[0] + LQ.Wout, sl.wout2 = qk[1] + LQ.Wout;
+    sl.z1 = W.Q[0].z1[q.n_blocks - 1], sl.z2 = W.Q[1].z1[q.n_blocks - 1], sl.N = N, sl.H = H, sl.act = q.act;
+    sl.dz1 = W.dza[0], sl.dz2 = W.dza[1], sl.qsel = W.qsel;
+  };
+  if (q.use_layernorm) {
+    CalqlSelect sl;
+    twin_of(sl);
+    sl.sel = sel_out != nullptr ? sel_out : W.sel;
+    launch_calql_select<P>(sl, s);
+  } else {
+    SacSelect sl;
+    twin_of(sl);
+    sl.sel = W.sel, sl.sel_out = sel_out;
+    launch_sac_select<P>(sl, s);
+  }
   s2 = fork_side(s, 0);
-  rlpd_chain_from_seed<P>(q, prm[1], qk[1], LQ, N, W.Q[1], W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, 2 * H, s2);
-  rlpd_chain_from_seed<P>(q, prm[0], qk[0], LQ, N, W.Q[0], W.dza[0], W.dzb[0], W.dhcat, 2 * H, s);
+  q_chain_from_seed<P>(q, prm[1], qk[1], LQ, N, W.Q[1], W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, 2 * H, s2);
+  q_chain_from_seed<P>(q, prm[0], qk[0], LQ, N, W.Q[0], W.dza[0], W.dzb[0], W.dhcat, 2 * H, s);
   if (s2 != s) join_side(s, s2, 0);
   SacStats st;
   memset(&st, 0, sizeof(st));
   st.qsel = W.qsel, st.logp = logp, st.sig_row = W.sig, st.alpha = alpha, st.N = N, st.AF = AF, st.stats = stats;
-  ln_actor_back<P>(a, q, 2, 1, ap, ak, h, alpha, st, N, W, grad, d_a, s);  // (E = 1: the seeds carry the weights)
+  q_actor_back<P>(a, q, 2, q.use_layernorm ? 1 : 0, ap, ak, h, alpha, st, N, W, grad, d_a, s);  // (E = 1: the seeds carry the weights)
   return check_launch();
 }
 int dppo_calql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
@@ -3842,8 +3820,8 @@ int dppo_calql_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q,
     return fail(-1, "null pointer");
   if (int e = check_idql_batch(batch, N, RING_OBS)) return e;
 #define CALL(P)                                                                                                                      \
-  calql_actor_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, \
-                      *cfg, *batch, obs_dim, N, noise, alpha, actor_grad, stats, d_a, logp_out, sel_out, actions_out, workspace,      \
+  twin_actor_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, \
+                     *cfg, *batch, obs_dim, N, noise, alpha, actor_grad, stats, d_a, logp_out, sel_out, actions_out, workspace,      \
                       workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
@@ -3865,7 +3843,7 @@ static int check_dql(const dppo_net_desc* a, const dppo_net_desc* q, int obs_dim
   return 0;
 }
 static int check_dql_sizes(const dppo_net_desc* a, int64_t N, int K) {
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (K < 1 || K > 1024) return fail(-1, "K=%d denoising steps outside [1, 1024]", K);
   if ((int64_t)(K + 1) * N > 0x7fffffff) return fail(-1, "(K + 1) * N out of range");
   if ((int64_t)K * a->time_dim > 65536 || time_backward_lds_bytes(K, a->time_dim) > 156 * 1024)
@@ -3876,7 +3854,7 @@ template <class P>
 struct DqlWs {
   MlpBufs<P> A, Q1, Q2;
   int32_t* krow;
-  void *dza, *dzb, *dhcat;  // the chosen Q trunk's data-gradient chain (qsm_action_chain)
+  void *dza, *dzb, *dhcat;  // the chosen Q trunk's data-gradient chain (q_seeded_chain)
   void *w0x, *w0q;          // [AF][H] / [AF][Hq] elem: the x columns of the actor's W0, the action columns of the chosen trunk's
   float *dx, *scale;
   double* rowsum;
@@ -3961,10 +3939,8 @@ static int dql_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float*
                     int OD, int64_t N, const float* chains, const float* noise_bc, const int64_t* t_bc, const float* sa,
                     const float* sb, double eta, int which, float* grad, double* stats, uint8_t* masks, float* d_a, void* ws,
                     int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   DqlWs<P> W;
-  const size_t need = carve_dql<P>(c, a, q, N, K, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_dql<P>(c, a, q, N, K, W); })) return e;
   const size_t ES = P::ESIZE;
   const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
   const ParamLayout pla = param_layout(a), plq = param_layout(q);
@@ -3984,7 +3960,7 @@ static int dql_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float*
   hipStream_t sq = fork_side(s, 0);
   mlp_forward<P>(q, qp, qk1, LQ, N, W.Q1, true, sq);
   mlp_forward<P>(q, qp + plq.total, qk2, LQ, N, W.Q2, true, sq);
-  qsm_action_chain<P>(q, which ? qk2 : qk1, LQ, N, which ? W.Q2 : W.Q1, W.dza, W.dzb, W.dhcat, sq);
+  q_seeded_chain<P>(q, qp + (which ? plq.total : 0), which ? qk2 : qk1, LQ, N, which ? W.Q2 : W.Q1, W.dza, W.dzb, W.dhcat, 2 * Hq, sq);
   launch_dql_pack_cols<P>(qp + (which ? plq.total : 0) + plq.W0, q.in_dim, OD, AF, Hq, W.w0q, sq);
   launch_dql_pack_cols<P>(ap + pla.W0, a.in_dim, 0, AF, H, W.w0x, s);
   // The layered path's operands: part of the packed image only where the fused kernels do NOT cover the shape (pack_impl);
@@ -4109,10 +4085,8 @@ template <class P>
 static int sac_sample_impl(const dppo_net_desc& d, const float* prm, const char* pk, const dppo_sac_cfg& cfg, const float* obs,
                            const float* noise, int64_t B, float* actions, float* logp, float* u_out, void* ws, int64_t wsb,
                            hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
   MlpBufs<P> A;
-  const size_t need = carve_sac_sample<P>(c, d, B, A);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_sac_sample<P>(c, d, B, A); })) return e;
   const PackLayout L = pack_layout<P>(d, 0);
   launch_build_direct<P>(nullptr, nullptr, obs, nullptr, 0, 0, d.cond_dim, B, A.in, L.Kp0, s);
   mlp_forward<P>(d, prm, pk, L, B, A, false, s);
@@ -4149,7 +4123,7 @@ int dppo_sac_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, const float* q_par
   if (!q_params || !q1_packed || !q2_packed || !target_q_params || !target_q1_packed || !target_q2_packed || !next_actions ||
       !next_logp || !alpha || !q_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (int e = check_idql_batch(batch, N, RING_TRANSITION)) return e;
   if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(-1, "discount gamma=%g outside [0, 1]", gamma);
 #define CALL(P)                                                                                                                \
@@ -4166,95 +4140,10 @@ static int check_sac_pair(const dppo_net_desc* a, const dppo_net_desc* q, int ob
   if (int e = check_qsm_plain(q)) return e;
   return check_sac_actor_q(a, q, obs_dim);
 }
-template <class P>
-struct SacWs {
-  MlpBufs<P> A, Q1, Q2;
-  void *dza[2], *dzb[2], *dhcat, *w0a;  // as QsmWs
-  float *actions, *logp, *sig, *qsel;
-  float* dout32;  // bf16 only: [N][2 AF] the head's gradient before its rounding to elem (SacTail::d_out32)
-  uint8_t* sel;
-};
-template <class P>
-static size_t carve_sac_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, SacWs<P>& W) {
-  const size_t ES = P::ESIZE;
-  const int AF = a.out_dim / 2;
-  carve_mlp<P>(c, a, N, true, true, W.A);
-  carve_mlp<P>(c, q, N, true, false, W.Q1);
-  carve_mlp<P>(c, q, N, true, false, W.Q2);
-  for (int i = 0; i < 2; ++i) {
-    W.dza[i] = c.take((size_t)N * q.hidden * ES);
-    W.dzb[i] = c.take((size_t)N * q.hidden * ES);
-  }
-  W.dhcat = c.take((size_t)N * 2 * q.hidden * ES);
-  W.w0a = c.take((size_t)AF * 2 * q.hidden * ES);
-  W.actions = (float*)c.take((size_t)N * AF * 4);
-  W.logp = (float*)c.take((size_t)N * 4);
-  W.sig = (float*)c.take((size_t)N * 4);
-  W.qsel = (float*)c.take((size_t)N * 4);
-  W.dout32 = ES == 4 ? nullptr : (float*)c.take((size_t)N * 2 * AF * 4);
-  W.sel = (uint8_t*)c.take((size_t)N);
-  return al256(c.off);
-}
 int64_t dppo_sac_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N) {
   if (check_sac_pair(actor, q, obs_dim) || check_prec(prec)) return -1;
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
-  return ws_bytes(prec, [&](Carver& c, auto p) {
-    SacWs<decltype(p)> W;
-    return carve_sac_actor<decltype(p)>(c, *actor, *q, N, W);
-  });
-}
-template <class P>
-static int sac_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, const float* ap, const char* ak, const float* qp,
-                          const char* qk1, const char* qk2, const dppo_sac_cfg& cfg, const dppo_idql_batch& b, int OD, int64_t N,
-                          const float* noise, const double* alpha, float* grad, double* stats, float* d_a, float* logp_out,
-                          uint8_t* sel_out, float* actions_out, void* ws, int64_t wsb, hipStream_t s) {
-  Carver c{(char*)ws, 0, (size_t)wsb};
-  SacWs<P> W;
-  const size_t need = carve_sac_actor<P>(c, a, q, N, W);
-  if ((int64_t)need > wsb) return fail(-1, "workspace too small: need %zu bytes, got %lld", need, (long long)wsb);
-  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
-  const ParamLayout plq = param_layout(q);
-  const int AF = a.out_dim / 2, H = q.hidden;
-  float* actions = actions_out != nullptr ? actions_out : W.actions;
-  float* logp = logp_out != nullptr ? logp_out : W.logp;
-  // the actor's rows [obs | 0], its forward with the activations kept, the head: sample, log-probability, the critic's rows
-  IdqlRows r = idql_rows_of(b, N, OD, AF);
-  r.vin = W.A.in, r.KpV = LA.Kp0;
-  launch_idql_rows<P>(r, s);
-  launch_qsm_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, H, W.w0a, s);
-  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s);
-  SacHead h = sac_head_of(cfg, W.A.out, W.A.ldout, AF, noise, N);
-  h.ring = idql_rows_of(b, N, OD, AF);
-  h.actions = actions, h.logp = logp, h.sig_row = W.sig, h.q1in = W.Q1.in, h.q2in = W.Q2.in, h.KpQ = LQ.Kp0;
-  launch_sac_head<P>(h, s);
-  // both Q forwards side by side; the choice of the twin per row seeds both data-gradient chains (the other trunk's seed is 0)
-  hipStream_t s2 = fork_side(s, 0);
-  mlp_forward<P>(q, qp + plq.total, qk2, LQ, N, W.Q2, true, s2);
-  mlp_forward<P>(q, qp, qk1, LQ, N, W.Q1, true, s);
-  if (s2 != s) join_side(s, s2, 0);
-  SacSelect sl;
-  memset(&sl, 0, sizeof(sl));
-  sl.q1 = W.Q1.out, sl.q2 = W.Q2.out, sl.ldq = W.Q1.ldout, sl.wout1 = qk1 + LQ.Wout, sl.wout2 = qk2 + LQ.Wout;
-  sl.z1 = W.Q1.z1[q.n_blocks - 1], sl.z2 = W.Q2.z1[q.n_blocks - 1], sl.N = N, sl.H = H, sl.act = q.act;
-  sl.dz1 = W.dza[0], sl.dz2 = W.dza[1], sl.sel = W.sel, sl.sel_out = sel_out, sl.qsel = W.qsel;
-  launch_sac_select<P>(sl, s);
-  s2 = fork_side(s, 0);
-  qsm_chain_gemms<P>(q, qk2, LQ, N, W.Q2, W.dza[1], W.dzb[1], (char*)W.dhcat + (size_t)H * P::ESIZE, s2);
-  qsm_chain_gemms<P>(q, qk1, LQ, N, W.Q1, W.dza[0], W.dzb[0], W.dhcat, s);
-  if (s2 != s) join_side(s, s2, 0);
-  SacTail tl;
-  memset(&tl, 0, sizeof(tl));
-  tl.head = h, tl.dh = W.dhcat, tl.wa = W.w0a, tl.H2 = 2 * H, tl.rows = qsm_tail_rows(2 * H), tl.alpha = alpha;
-  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
-  launch_sac_tail<P>(tl, s);
-  SacStats st;
-  memset(&st, 0, sizeof(st));
-  st.qsel = W.qsel, st.logp = logp, st.sig_row = W.sig, st.alpha = alpha, st.N = N, st.AF = AF, st.stats = stats;
-  launch_sac_stats(st, s);
-  mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s);
-  if (W.dout32 != nullptr)  // the two heads' bias gradient again, from the unrounded rows
-    launch_colsum<F32>(W.dout32, (int)N, 2 * AF, 2 * AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
-  return check_launch();
+  if (int e = check_rows(N)) return e;
+  return twin_actor_ws_bytes(actor, q, prec, N);  // twin_actor_impl, beside Cal-QL's
 }
 int dppo_sac_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, const float* actor_params,
                            const void* actor_packed, const float* q_params, const void* q1_packed, const void* q2_packed,
@@ -4267,11 +4156,11 @@ int dppo_sac_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, i
   if (cfg->deterministic) return fail(-1, "the actor loss samples: deterministic must be 0");
   if (!actor_params || !actor_packed || !q_params || !q1_packed || !q2_packed || !alpha || !actor_grad || !stats || !workspace)
     return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (int e = check_idql_batch(batch, N, RING_OBS)) return e;
 #define CALL(P)                                                                                                                   \
-  sac_actor_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, \
-                    *cfg, *batch, obs_dim, N, noise, alpha, actor_grad, stats, d_a, logp_out, sel_out, actions_out, workspace,      \
+  twin_actor_impl<P>(*actor, *q, actor_params, (const char*)actor_packed, q_params, (const char*)q1_packed, (const char*)q2_packed, \
+                     *cfg, *batch, obs_dim, N, noise, alpha, actor_grad, stats, d_a, logp_out, sel_out, actions_out, workspace,      \
                     workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
@@ -4279,7 +4168,7 @@ int dppo_sac_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, i
 int dppo_sac_alpha_loss(const float* logp, int64_t N, const double* log_alpha, double target_entropy, double* out,
                         dppo_stream_t stream) {
   if (!logp || !log_alpha || !out) return fail(-1, "null pointer");
-  if (N < 1 || N > 0x7fffffff) return fail(-1, "N out of range");
+  if (int e = check_rows(N)) return e;
   if (!(target_entropy >= -3.0e38 && target_entropy <= 3.0e38)) return fail(-1, "target_entropy=%g must be finite", target_entropy);
   launch_sac_alpha_loss(logp, N, log_alpha, target_entropy, out, (hipStream_t)stream);
   return check_launch();

@@ -33,9 +33,9 @@
 // sample at obs_n,  loss = mean_n [-min(q1, q2)(obs_n, a_n) + alpha logp_n].  The head writes ONE row image [obs | a | 0] that both
 // trunks read; each runs its forward (z, mean, rstd kept).  calql_select_kernel picks per row (q2 < q1: Q2; q1 == q2: both at one
 // half, torch.minimum's backward; everything else, a NaN included: Q1) and writes both chains' seeds w_i Wout_i (.) act'(z_L), zero
-// for the trunk a row did not select.  From there each trunk runs rlpd.h's data-gradient chain (rlpd_chain_from_seed, shared with
+// for the trunk a row did not select.  From there each trunk runs rlpd.h's data-gradient chain (q_chain_from_seed, shared with
 // dppo_rlpd_actor_fwd_bwd): per hidden layer from the top ln_bwd_kernel with no parameter sums and, except at layer 0, the data GEMM
-// with the act' epilogue.  Trunk i's dx_0 lands in columns [i H, (i + 1) H) of one [N][2H] image; launch_rlpd_pack_w0a (E = 2) packs
+// with the act' epilogue.  Trunk i's dx_0 lands in columns [i H, (i + 1) H) of one [N][2H] image; launch_pack_w0a (E = 2) packs
 // the action columns of both W0 as [AF][2H]; launch_rlpd_tail with K = 2H, E = 1 forms g = dQ_sel/da (the unselected half is zero,
 // a tie's halves add) and runs SAC's head backward; launch_sac_stats on qsel gives {loss, mean qsel, mean logp, mean sigma}.
 //

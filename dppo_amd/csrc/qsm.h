@@ -41,10 +41,11 @@ void launch_qsm_td_rows(const QsmTdRows& a, hipStream_t s);
 template <class P>
 void launch_qsm_seed(const void* wout, const void* z, int64_t N, int H, int act, void* dz, hipStream_t s);
 
-// wa[a][i * H + h] = elem(W0 of trunk i [h][OD + a]), i = 0, 1 (trunk 1's flat image starts at params + stride): [AD][2H]
+// wa[a][e * H + h] = elem(W0 of trunk e [h][OD + a]), e < E (trunk e's flat image starts at params + e * stride): [AF][E H], the
+// weight operand of every tail (the twins' at E = 2, RLPD's members')
 template <class P>
-void launch_qsm_pack_w0a(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AD, int H, void* wa,
-                         hipStream_t s);
+void launch_pack_w0a(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AF, int H, int E, void* wa,
+                     hipStream_t s);
 
 // g[n][a] = 0.5 * sum_k dh[n][k] wa[a][k], k over 2H in index order (fp32 fma);  pairs[n][1][a] = -coeff * g;  g_out[n][a] = g
 struct QsmTail {

@@ -133,23 +133,24 @@ template void launch_qsm_seed<BF16>(const void*, const void*, int64_t, int, int,
 
 // ---- the tail ---------------------------------------------------------------------------------------------------------------
 template <class P>
-__global__ __launch_bounds__(256) void qsm_pack_w0a_kernel(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD,
-                                                            int AD, int H, typename P::elem_t* wa) {
-  const int total = AD * 2 * H;
+__global__ __launch_bounds__(256) void pack_w0a_kernel(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AF,
+                                                        int H, int E, typename P::elem_t* wa) {
+  const int K = E * H, total = AF * K;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int a = i / (2 * H), k = i - a * 2 * H;
-    const int trunk = k >= H ? 1 : 0, h = k - trunk * H;
-    wa[i] = P::from_f32(params[trunk * stride + w0_off + (int64_t)h * in_dim + OD + a]);
+    const int a = i / K, k = i - a * K;
+    const int e = k / H, h = k - e * H;
+    wa[i] = P::from_f32(params[e * stride + w0_off + (int64_t)h * in_dim + OD + a]);
   }
 }
 template <class P>
-void launch_qsm_pack_w0a(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AD, int H, void* wa,
-                         hipStream_t s) {
-  hipLaunchKernelGGL((qsm_pack_w0a_kernel<P>), dim3(qsm_grid((int64_t)AD * 2 * H)), dim3(256), 0, s, params, stride, w0_off, in_dim,
-                     OD, AD, H, (typename P::elem_t*)wa);
+void launch_pack_w0a(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AF, int H, int E, void* wa,
+                     hipStream_t s) {
+  const int blocks = (AF * E * H + 255) / 256;
+  hipLaunchKernelGGL((pack_w0a_kernel<P>), dim3(blocks > 2048 ? 2048 : blocks), dim3(256), 0, s, params, stride, w0_off, in_dim, OD, AF,
+                     H, E, (typename P::elem_t*)wa);
 }
-template void launch_qsm_pack_w0a<F32>(const float*, int64_t, int64_t, int, int, int, int, void*, hipStream_t);
-template void launch_qsm_pack_w0a<BF16>(const float*, int64_t, int64_t, int, int, int, int, void*, hipStream_t);
+template void launch_pack_w0a<F32>(const float*, int64_t, int64_t, int, int, int, int, int, void*, hipStream_t);
+template void launch_pack_w0a<BF16>(const float*, int64_t, int64_t, int, int, int, int, int, void*, hipStream_t);
 
 // `rows` rows of dh per block as fp32 in LDS (row stride H2 + 4 floats: rows that differ by one land four banks apart, so
 // the 16-byte reads of a wave that spans several rows do not collide); thread o of the block's rows * AD outputs walks K = 2H in

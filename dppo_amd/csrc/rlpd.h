@@ -39,7 +39,7 @@
 //   + the actor's parameter backward.  Nothing of a critic's is written: no weight gradient, column sum or gradient buffer.
 //   Shipped halfcheetah (E = 10, L = 2): 4 + 3 + 10 x 5 + 10 x 4 + 2 = 99 before the actor's backward.
 // Not built: a member-batched GEMM, weight gradients grouped across members.  (IBRL's model and critic loss: ibrl.h; Cal-QL: calql.h; its actor runs this file's
-// chain from a seed of its own: rlpd_chain_from_seed in api.hip.)
+// chain from a seed of its own: q_chain_from_seed in api.hip.)
 //
 // Launches of one forward of a trunk: L x (1 GEMM + 1 row kernel) + 1 GEMM.
 #pragma once
@@ -112,11 +112,7 @@ void launch_rlpd_loss(const RlpdLoss& a, hipStream_t s);
 void launch_rlpd_out_bias(const double* partial, int64_t N, int E, float* grad, int64_t stride, int64_t bout, hipStream_t s);
 
 // ---- the actor's loss through the ensemble's mean ---------------------------------------------------------------------------------
-// wa[a][e * H + h] = elem(W0 of member e [h][OD + a]) (member e's flat image starts at params + e * stride): [AF][E H]
-template <class P>
-void launch_rlpd_pack_w0a(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AF, int H, int E, void* wa,
-                          hipStream_t s);
-
+// (the tail's weight operand [AF][E H] is qsm.h's launch_pack_w0a)
 // The chains' tail and the head's backward in one launch.  K = E H is split over RLPD_TAIL_LANES lanes per output (n, j): lane l
 // takes the 4-element groups l, l + 16, ... of the row (so the members in index order), one fma per element, and the 16 partials
 // are added by a fixed xor butterfly.  Operands come straight from global memory: no LDS tile, so no ceiling on K.  An output

@@ -265,26 +265,6 @@ template void launch_rlpd_loss<F32>(const RlpdLoss&, hipStream_t);
 template void launch_rlpd_loss<BF16>(const RlpdLoss&, hipStream_t);
 
 // ---- the actor's loss through the ensemble's mean (gaussian_rlpd.py:100-112) ------------------------------------------------------
-template <class P>
-__global__ __launch_bounds__(256) void rlpd_pack_w0a_kernel(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD,
-                                                             int AF, int H, int E, typename P::elem_t* wa) {
-  const int K = E * H, total = AF * K;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int a = i / K, k = i - a * K;
-    const int e = k / H, h = k - e * H;
-    wa[i] = P::from_f32(params[e * stride + w0_off + (int64_t)h * in_dim + OD + a]);
-  }
-}
-template <class P>
-void launch_rlpd_pack_w0a(const float* params, int64_t stride, int64_t w0_off, int in_dim, int OD, int AF, int H, int E, void* wa,
-                          hipStream_t s) {
-  const int blocks = (AF * E * H + 255) / 256;
-  hipLaunchKernelGGL((rlpd_pack_w0a_kernel<P>), dim3(blocks > 2048 ? 2048 : blocks), dim3(256), 0, s, params, stride, w0_off, in_dim,
-                     OD, AF, H, E, (typename P::elem_t*)wa);
-}
-template void launch_rlpd_pack_w0a<F32>(const float*, int64_t, int64_t, int, int, int, int, int, void*, hipStream_t);
-template void launch_rlpd_pack_w0a<BF16>(const float*, int64_t, int64_t, int, int, int, int, int, void*, hipStream_t);
-
 // 16 outputs per block, 16 lanes per output; every lane of a wave runs the product (an output past the end redoes the last one and
 // writes nothing), so the butterfly never meets an idle lane.  Lane 0 of an output then runs the head's backward.
 template <class P>
@@ -358,13 +338,7 @@ __global__ __launch_bounds__(256) void rlpd_actor_stats_kernel(const RlpdActorSt
     const float t = alpha * lp;
     v[0] += (double)(-q + t), v[1] += q, v[2] += lp, v[3] += a.sig_row[n];
   }
-  for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w)
-      for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
-    __syncthreads();
-  }
+  sac_tree<4>(sh, v);
   if (threadIdx.x == 0) {
     const double dn = (double)a.N;
     a.stats[0] = sh[0][0] / dn, a.stats[1] = sh[1][0] / dn, a.stats[2] = sh[2][0] / dn, a.stats[3] = sh[3][0] / (dn * a.AF);

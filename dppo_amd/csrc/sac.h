@@ -112,6 +112,18 @@ struct SacTail {
 template <class P>
 void launch_sac_tail(const SacTail& a, hipStream_t s);
 
+// sh[k][0] <- the sum of the 256 threads' v[k], added pairwise in a fixed tree
+template <int K>
+__device__ __forceinline__ void sac_tree(double (*sh)[256], const double* v) {
+  for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w)
+      for (int k = 0; k < K; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
+    __syncthreads();
+  }
+}
+
 // stats = {mean(-q_sel + alpha logp), mean q_sel, mean logp, mean sigma}: thread i sums rows i, i + 256, ... in double, the 256
 // partials are added pairwise in a fixed tree
 struct SacStats {

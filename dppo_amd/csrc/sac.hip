@@ -189,16 +189,6 @@ template void launch_sac_tail<F32>(const SacTail&, hipStream_t);
 template void launch_sac_tail<BF16>(const SacTail&, hipStream_t);
 
 // ---- fixed-order sums ------------------------------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ void sac_tree(double (*sh)[256], const double* v) {
-  for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w)
-      for (int k = 0; k < K; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
-    __syncthreads();
-  }
-}
 __global__ __launch_bounds__(256) void sac_stats_kernel(const SacStats a) {
   __shared__ double sh[4][256];
   const float alpha = (float)*a.alpha;

@@ -27,7 +27,6 @@ import torch
 
 from dppo_amd import hip
 from dppo_amd.model.common import off_policy
-from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss, flat_views
 from dppo_amd.model.rl.gaussian_sac import SAC_Gaussian
 from dppo_amd.util.replay import DeviceReplay
 
@@ -116,35 +115,8 @@ class CalQL_Gaussian(SAC_Gaussian):
         mean q_sel, mean logp, mean sigma}; ``last_d_a`` (N, Ta*Da) = d loss / d a through the twin; ``last_logp`` (N,);
         ``last_actions`` (N, Ta*Da); ``last_sel`` (N,) bytes: 0 Q1 was taken, 1 Q2 (q2 < q1), 2 a tie (both at one half,
         ``torch.minimum``'s backward).  ``obs`` may be a ``DeviceReplay`` (rows ``inds``)."""
-        q, net = self.critic, self.network
-        if not next(net.parameters()).is_cuda:
+        if not next(self.network.parameters()).is_cuda:
             raise NotImplementedError("dppo_amd: Cal-QL's actor loss runs on the GPU only; a CPU path would be a follow-up and is "
                                       "not built")
-        batch, N, keep = off_policy.as_batch("Cal-QL", obs, inds)
-        dev = net.flat_params().device
-        AF = self.horizon_steps * net.action_dim
-        cfg = self._cfg(False, noise)
-        if noise is not None:
-            noise = noise.reshape(N, AF).contiguous().float()
-        alpha = self._dev_scalar(alpha, dev)
-        lib, da, dq = hip.load(), net.net_desc(), q.net_desc()
-        OD = q.cond_dim
-        ws = self._ws_actor.get(lib.dppo_calql_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N), dev,
-                                "dppo_calql_actor_workspace_bytes")
-        k1, k2 = q.packed(self.prec)
-        grad = torch.empty_like(net.flat_params())
-        stats = torch.empty(hip.SAC_STAT_COUNT, dtype=torch.float64, device=dev)
-        d_a = torch.empty(N, AF, dtype=torch.float32, device=dev)
-        logp = torch.empty(N, dtype=torch.float32, device=dev)
-        sel = torch.empty(N, dtype=torch.uint8, device=dev)
-        actions = torch.empty(N, AF, dtype=torch.float32, device=dev)
-        hip.check(lib.dppo_calql_actor_fwd_bwd(
-            C.byref(da), C.byref(dq), self.prec, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(),
-            q.flat_params().data_ptr(), k1.data_ptr(), k2.data_ptr(), C.byref(cfg), C.byref(batch), OD, N, hip.ptr(noise),
-            alpha.data_ptr(), grad.data_ptr(), stats.data_ptr(), d_a.data_ptr(), logp.data_ptr(), sel.data_ptr(),
-            actions.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_calql_actor_fwd_bwd")
-        for name, v in (("last_loss_grad", grad), ("last_stats", stats), ("last_d_a", d_a), ("last_logp", logp), ("last_sel", sel),
-                        ("last_actions", actions)):
-            object.__setattr__(self, name, v)
-        params = net.trunk_parameters()
-        return _FusedDenoiseLoss.apply(stats[0], flat_views(grad, params), *params)
+        return self._loss_actor("Cal-QL", "dppo_calql_actor_workspace_bytes", "dppo_calql_actor_fwd_bwd", self.critic,
+                                lambda: (self.critic.flat_params(), *self.critic.packed(self.prec)), (), True, obs, alpha, inds, noise)

@@ -25,7 +25,6 @@ import torch
 from dppo_amd import hip
 from dppo_amd.model.common import off_policy
 from dppo_amd.model.common.ensemble import EnsembleCritics, _Ensemble  # noqa: F401  (_Ensemble: imported from here too)
-from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss, flat_views
 from dppo_amd.model.rl.gaussian_sac import SAC_Gaussian
 
 
@@ -81,33 +80,8 @@ class RLPD_Gaussian(EnsembleCritics, SAC_Gaussian):
         parameters in ``last_loss_grad``; no member's gradient is touched.  ``noise`` (N, Ta, Da) replaces the draws.
         ``last_stats``: {loss, mean of the members' mean q, mean logp, mean sigma}; ``last_d_a`` (N, Ta*Da) = d loss / d a through
         the ensemble; ``last_logp`` (N,); ``last_actions`` (N, Ta*Da).  ``obs`` may be a ``DeviceReplay`` (rows ``inds``)."""
-        q, net = self.critic_networks[0], self.network
-        if not next(net.parameters()).is_cuda:
+        if not next(self.network.parameters()).is_cuda:
             raise NotImplementedError("dppo_amd: RLPD's actor loss runs on the GPU only; a CPU path is not built")
-        batch, N, keep = off_policy.as_batch("RLPD", obs, inds)
-        dev = net.flat_params().device
-        AF = self.horizon_steps * net.action_dim
-        cfg = self._cfg(False, noise)
-        if noise is not None:
-            noise = noise.reshape(N, AF).contiguous().float()
-        alpha = self._dev_scalar(alpha, dev)
-        lib, da, dq, E = hip.load(), net.net_desc(), q.net_desc(), self.n_critics
-        OD = q.cond_dim
-        ws = self._ws_actor.get(lib.dppo_rlpd_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N, E), dev,
-                                "dppo_rlpd_actor_workspace_bytes")
-        qk, keep_q = self._ens.images(self.prec)
-        grad = torch.empty_like(net.flat_params())
-        stats = torch.empty(hip.SAC_STAT_COUNT, dtype=torch.float64, device=dev)
-        d_a = torch.empty(N, AF, dtype=torch.float32, device=dev)
-        logp = torch.empty(N, dtype=torch.float32, device=dev)
-        actions = torch.empty(N, AF, dtype=torch.float32, device=dev)
-        hip.check(lib.dppo_rlpd_actor_fwd_bwd(
-            C.byref(da), C.byref(dq), self.prec, E, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(),
-            self.critic_flat_params().data_ptr(), qk, C.byref(cfg), C.byref(batch), OD, N, hip.ptr(noise), alpha.data_ptr(),
-            grad.data_ptr(), stats.data_ptr(), d_a.data_ptr(), logp.data_ptr(), actions.data_ptr(), ws.data_ptr(), ws.numel(),
-            hip.stream()), "dppo_rlpd_actor_fwd_bwd")
-        for name, v in (("last_loss_grad", grad), ("last_stats", stats), ("last_d_a", d_a), ("last_logp", logp),
-                        ("last_actions", actions)):
-            object.__setattr__(self, name, v)
-        params = net.trunk_parameters()
-        return _FusedDenoiseLoss.apply(stats[0], flat_views(grad, params), *params)
+        return self._loss_actor("RLPD", "dppo_rlpd_actor_workspace_bytes", "dppo_rlpd_actor_fwd_bwd", self.critic_networks[0],
+                                lambda: (self.critic_flat_params(), self._ens.images(self.prec)[0]), (self.n_critics,), False, obs,
+                                alpha, inds, noise)

@@ -122,8 +122,15 @@ class SAC_Gaussian(GaussianModel):
         ``last_loss_grad``.  ``noise`` (N, Ta, Da) replaces the draws.  ``last_stats``: {loss, mean q_sel, mean logp, mean sigma};
         ``last_d_a`` (N, Ta*Da) = d loss / d a through the critic; ``last_logp`` (N,); ``last_sel`` (N,) bytes (1: Q2 was the
         smaller); ``last_actions`` (N, Ta*Da)."""
-        q, net = self.critic, self.network
-        batch, N, keep = off_policy.as_batch("SAC", obs, inds)
+        return self._loss_actor("SAC", "dppo_sac_actor_workspace_bytes", "dppo_sac_actor_fwd_bwd", self.critic,
+                                lambda: (self.critic.flat_params(), *self.critic.packed(self.prec)), (), True, obs, alpha, inds, noise)
+
+    def _loss_actor(self, algo, ws_entry, entry, q, q_args, members, has_sel, obs, alpha, inds, noise):
+        """What SAC's, Cal-QL's and RLPD's ``loss_actor`` share.  ``q``: the module whose descriptor the Q trunks have;
+        ``q_args()``: the Q trunks' flat parameters, then the twin's two kernel images or the ensemble's image table with
+        ``members`` = (E,); called behind the workspace query, where each of the three flattened and packed its critics."""
+        net = self.network
+        batch, N, keep = off_policy.as_batch(algo, obs, inds)
         dev = net.flat_params().device
         AF = self.horizon_steps * net.action_dim
         cfg = self._cfg(False, noise)
@@ -132,22 +139,21 @@ class SAC_Gaussian(GaussianModel):
         alpha = self._dev_scalar(alpha, dev)
         lib, da, dq = hip.load(), net.net_desc(), q.net_desc()
         OD = q.cond_dim
-        ws = self._ws_actor.get(lib.dppo_sac_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N), dev,
-                                "dppo_sac_actor_workspace_bytes")
-        k1, k2 = q.packed(self.prec)
+        ws = self._ws_actor.get(getattr(lib, ws_entry)(C.byref(da), C.byref(dq), self.prec, OD, N, *members), dev, ws_entry)
+        q_params, *images = q_args()
         grad = torch.empty_like(net.flat_params())
         stats = torch.empty(hip.SAC_STAT_COUNT, dtype=torch.float64, device=dev)
         d_a = torch.empty(N, AF, dtype=torch.float32, device=dev)
         logp = torch.empty(N, dtype=torch.float32, device=dev)
-        sel = torch.empty(N, dtype=torch.uint8, device=dev)
+        sel = torch.empty(N, dtype=torch.uint8, device=dev) if has_sel else None
         actions = torch.empty(N, AF, dtype=torch.float32, device=dev)
-        hip.check(lib.dppo_sac_actor_fwd_bwd(
-            C.byref(da), C.byref(dq), self.prec, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(),
-            q.flat_params().data_ptr(), k1.data_ptr(), hip.ptr(k2), C.byref(cfg), C.byref(batch), OD, N, hip.ptr(noise),
-            alpha.data_ptr(), grad.data_ptr(), stats.data_ptr(), d_a.data_ptr(), logp.data_ptr(), sel.data_ptr(),
-            actions.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_sac_actor_fwd_bwd")
-        for name, v in (("last_loss_grad", grad), ("last_stats", stats), ("last_d_a", d_a), ("last_logp", logp), ("last_sel", sel),
-                        ("last_actions", actions)):
+        hip.check(getattr(lib, entry)(
+            C.byref(da), C.byref(dq), self.prec, *members, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(),
+            q_params.data_ptr(), *[hip.ptr(k) if torch.is_tensor(k) else k for k in images], C.byref(cfg), C.byref(batch), OD, N,
+            hip.ptr(noise), alpha.data_ptr(), grad.data_ptr(), stats.data_ptr(), d_a.data_ptr(), logp.data_ptr(),
+            *([sel.data_ptr()] if has_sel else []), actions.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), entry)
+        for name, v in (("last_loss_grad", grad), ("last_stats", stats), ("last_d_a", d_a), ("last_logp", logp),
+                        ("last_actions", actions)) + ((("last_sel", sel),) if has_sel else ()):
             object.__setattr__(self, name, v)
         params = net.trunk_parameters()
         return _FusedDenoiseLoss.apply(stats[0], flat_views(grad, params), *params)

@@ -9,7 +9,8 @@ thing exactly when their fingerprints are equal; DPPO_HIP_LIB selects the build,
 Cases: ppo_update in rollout mode for seven network pairs in both precisions under eleven knob sets (hopper and halfcheetah at
 N = 1300 -- 21 row tiles, the last of 20 rows; the others at N = 6500, enough for the low-rank route at their width), and at the
 default knobs one case per other entry point, each built from its own test module's helpers; for the LayerNorm-critic family
-(RLPD's, Cal-QL's and IBRL's critic and actor / acting entries) the two smallest fixture cases of each, with the workspace size."""
+(RLPD's, Cal-QL's and IBRL's critic and actor / acting entries) and the plain twin-Q family (QSM's, DQL's and SAC's) the two smallest
+fixture cases of each, with the workspace size."""
 import argparse
 import ctypes as C
 import hashlib
@@ -277,6 +278,48 @@ def ln_family_cases(table, prec):
         table[f"ibrl_q/{case}_{n}/{prec}"] = lambda c=case, k=n: ibrl_q_case(c, k, prec)
 
 
+# The plain twin-Q family (QSM, DQL, SAC): as above, one fresh model per case and every tensor the entry writes.
+def hashed(res, ws):
+    out = {k: sha(v) for k, v in res.items()}
+    out["workspace_bytes"] = ws.buf.numel()
+    return out
+
+
+def qsm_case(which, net, n, prec):
+    from tests import test_qsm as Q
+    m, b = Q.make_model(net, prec, DEV), Q.dev_batch(net, n)
+    if which == "q":
+        return hashed(Q.run_critic(m, b), m._ws_q)
+    return hashed(Q.run_actor(m, net, b), m._ws_target)
+
+
+def dql_case(case, n, prec):
+    from tests import test_dql as D
+    m = D.make_model(case, prec, DEV)
+    return hashed(D.run_actor(m, case, n, D.given_chain(load_golden("g26_dql"), case, n)), m._ws_actor)
+
+
+def sac_case(which, case, n, prec):
+    from tests import test_sac as S
+    m, b = S.make_model(case, prec, DEV), S.dev_batch(case, n)
+    if which == "sample":
+        return hashed(dict(zip(("a", "logp", "u"), S.run_sample(m, b))), m._ws_s)
+    if which == "q":
+        return hashed(S.run_critic(m, b), m._ws_q)
+    return hashed(S.run_actor(m, b), m._ws_actor)
+
+
+def twin_q_cases(table, prec):
+    for net in ("scratch", "transport"):  # transport: Q in_dim 171, wider than one k tile
+        for which in ("q", "actor"):
+            table[f"qsm_{which}/{net}_77/{prec}"] = lambda w=which, c=net: qsm_case(w, c, 77, prec)
+    for case in ("scratch", "hopper"):
+        table[f"dql_actor/{case}_77/{prec}"] = lambda c=case: dql_case(c, 77, prec)
+    for case in ("tiny", "chunk"):
+        for which in ("sample", "q", "actor"):
+            table[f"sac_{which}/{case}_77/{prec}"] = lambda w=which, c=case: sac_case(w, c, 77, prec)
+
+
 def other_cases(only):
     from tests.golden import make_golden_idql_cases as K
     table = {}
@@ -295,6 +338,7 @@ def other_cases(only):
         for case in ("plain_ddpm", "plain_small_ddim"):
             table[f"plain/{case}/{prec}"] = lambda c=case, p=prec: plain_case(c, p)
         ln_family_cases(table, prec)
+        twin_q_cases(table, prec)
     for name, fn in table.items():
         if wanted(only, name):
             yield name, fn()
