@@ -1,4 +1,4 @@
-"""What the off-policy fine-tuning agents share (IDQL, QSM, DQL, SAC, RLPD, Cal-QL) on top of ``TrainAgent`` (set-up, checkpoint,
+"""What the off-policy fine-tuning agents share (IDQL, QSM, DQL, SAC, RLPD, Cal-QL, IBRL) on top of ``TrainAgent`` (set-up, checkpoint,
 episode statistics, logging tail): the device-resident replay ring, one env step with its ``final_obs`` bootstrap and ring append,
 the iteration of the replay-ratio agents (IDQL, QSM, DQL) as ``run``, and that of the agents which explore at
 random first and evaluate by an episode count (SAC, RLPD, Cal-QL) as ``run_by_episode_count``.
@@ -7,7 +7,8 @@ A replay-ratio agent supplies its hyper-parameters and optimisers, ``nets`` and 
 ``lr_schedulers``, ``log_line`` / ``log_keys``, ``_sample`` (how an action is drawn) and ``_metrics`` (the logged fields from the
 last minibatch's losses) are those of an agent with one actor and one critic optimiser (QSM, DQL).  An episode-count agent
 supplies ``update_iteration`` (or its own ``_update``), ``log_alpha``, ``n_explore_steps`` and ``n_eval_episode``; what else differs
-between the three is the handful of small methods in front of ``run_by_episode_count``.
+between them is the handful of small methods in front of ``run_by_episode_count`` (IBRL, which has no temperature and never acts at
+random, overrides ``_train_fields`` and ``explores_at_random``).
 """
 from __future__ import annotations
 
@@ -133,6 +134,7 @@ class OffPolicyAgent(TrainAgent):
     # Which of "eval", "update" and "log" wait for ``itr > n_explore_steps``; the others start at ``itr >= n_explore_steps``.  (The
     # reference's agents differ: SAC has ``>`` in all three tests, RLPD in the log line's only, Cal-QL in none.)
     strictly_past_exploration = ("log",)
+    explores_at_random = True  # the first ``n_explore_steps`` iterations act at random (IBRL never does: its model always acts)
 
     def _explore_action(self):
         """Uniformly random actions (reference SAC :121-122): the env's own ``action_space.sample()`` where it has one."""
@@ -158,9 +160,18 @@ class OffPolicyAgent(TrainAgent):
         or None where no update was due."""
         return self.update_iteration()
 
+    def _train_fields(self, losses):
+        """A logging train iteration's fields from the last update's device scalars: the only device reads of the loop."""
+        fields = dict(loss_critic=float(losses[0]), alpha=float(self.log_alpha.detach().exp()))
+        if losses[1] is not None:  # (SAC: no actor update yet)
+            fields["loss_actor"] = float(losses[1])
+        return fields
+
     def run_by_episode_count(self):
-        """The iteration of the agents whose evaluation ends by an episode count and whose first ``n_explore_steps`` iterations
-        act at random (the reference's SAC, RLPD and Cal-QL agents): rollout, ``_update()``, schedules, checkpoint, record."""
+        """The iteration of the agents whose evaluation ends by an episode count (the reference's SAC, RLPD, Cal-QL and IBRL
+        agents): rollout, ``_update()``, schedules, checkpoint, record.  With ``explores_at_random`` the first ``n_explore_steps``
+        iterations act at random (SAC, RLPD, Cal-QL); IBRL's model acts from iteration 0 and the count only gates evaluation, update
+        and log line."""
         model, dev = self.model, self.device
         E = self.n_envs
         X, strict = self.n_explore_steps, self.strictly_past_exploration
@@ -184,7 +195,7 @@ class OffPolicyAgent(TrainAgent):
             # ---------------- rollout
             for step in range(self._begin_rollout(eval_mode)):
                 state = torch.from_numpy(prev_obs["state"]).float().to(dev)
-                if self.itr < self.n_explore_steps:
+                if self.explores_at_random and self.itr < self.n_explore_steps:
                     action = self._explore_action()
                 else:
                     action = model(cond={"state": state}, deterministic=eval_mode).cpu().numpy()[:, :self.act_steps]
@@ -209,11 +220,7 @@ class OffPolicyAgent(TrainAgent):
                 self.save_model()
             rec = {"itr": self.itr, "step": cnt_train_step}
             if self.itr % self.log_freq == 0 and past("log"):
-                fields = {}
-                if not eval_mode and losses is not None:  # the only device reads of the loop, on logging iterations
-                    fields.update(loss_critic=float(losses[0]), alpha=float(self.log_alpha.detach().exp()))
-                    if losses[1] is not None:  # (SAC: no actor update yet)
-                        fields["loss_actor"] = float(losses[1])
+                fields = self._train_fields(losses) if not eval_mode and losses is not None else {}
                 self.log_record(run_results, rec, t_start, eval_mode, stats, fields)
             else:
                 run_results.append(rec)

@@ -1170,7 +1170,10 @@ static void backward_fused(const dppo_net_desc& d, const float* prm, const char*
 // a plain MLP's backward, layer by layer
 template <class P>
 static void backward_plain(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
-                           MlpBufs<P>& B, float* grad, const int32_t* krow, const dppo_step* ksteps, int Kft, hipStream_t s) {
+                           MlpBufs<P>& B, float* grad, const int32_t* krow, const dppo_step* ksteps, int Kft, hipStream_t s,
+                           const DropBwd* drop = nullptr) {
+  // drop (mask, scale): the forward ran with dropout (ibrl.h); the kept pre-activations are z', and each hidden layer's d/dz' becomes
+  // d/dz in place where LayerNorm's backward sits in a LayerNorm trunk.  Null: every caller from before runs launch for launch.
   const ParamLayout pl = param_layout(d);
   const int H = d.hidden, nb = d.n_blocks;
   weight_grad<P>(B.d_out, L.Kpo, d.out_dim, B.a2[nb - 1], H, H, M, B, grad + pl.Wout, H, s);
@@ -1191,7 +1194,14 @@ static void backward_plain(const dppo_net_desc& d, const float* prm, const char*
   LnBwd ln;
   memset(&ln, 0, sizeof(ln));
   ln.ld = H, ln.ldx = H, ln.M = M, ln.H = H, ln.partial = B.ln_part;
+  DropBwd db;
+  memset(&db, 0, sizeof(db));
+  if (drop != nullptr) db = *drop, db.ld = H, db.M = M, db.H = H;
   for (int b = nb - 1; b >= 0; --b) {
+    if (drop != nullptr) {
+      db.dz = dz, db.layer = b + 1;
+      launch_drop_bwd<P>(db, s);
+    }
     if (d.use_layernorm) {
       ln.dz = dz, ln.dz32 = wide ? dz32 : nullptr, ln.x = B.h[b + 1], ln.stats = B.ln_stats + (size_t)(b + 1) * M * 2, ln.gamma = prm + pl.n1w[b];
       ln.dgamma = grad + pl.n1w[b], ln.dbeta = grad + pl.n1b[b];
@@ -1213,6 +1223,10 @@ static void backward_plain(const dppo_net_desc& d, const float* prm, const char*
   if (d.use_layernorm) {
     ln.dz = dz, ln.dz32 = wide ? dz32 : nullptr, ln.x = B.h[0], ln.stats = B.ln_stats, ln.gamma = prm + pl.n0w, ln.dgamma = grad + pl.n0w, ln.dbeta = grad + pl.n0b;
     launch_ln_bwd<P>(ln, s);
+  }
+  if (drop != nullptr) {
+    db.dz = dz, db.layer = 0;
+    launch_drop_bwd<P>(db, s);
   }
   weight_grad<P>(dz, H, H, B.in, L.Kp0, d.in_dim, M, B, grad + pl.W0, d.in_dim, s);
   launch_colsum<P>(dz, (int)M, H, H, B.part, REDUCE_BLOCKS, grad + pl.b0, 1.f, s);
@@ -1265,10 +1279,10 @@ static void backward_layered(const dppo_net_desc& d, const float* prm, const cha
 template <class P>
 static void mlp_backward(const dppo_net_desc& d, const float* prm, const char* pk, const PackLayout& L, int64_t M,
                          MlpBufs<P>& B, float* grad, const int32_t* krow, const dppo_step* ksteps, int Kft,
-                         hipStream_t s, const LossArgs* fin = nullptr) {
+                         hipStream_t s, const LossArgs* fin = nullptr, const DropBwd* drop = nullptr) {
   if (B.route.fused) return backward_fused<P>(d, prm, pk, L, M, B, grad, krow, ksteps, Kft, s, fin);
   if (fin) launch_loss_finalize(*fin, s);  // (the fused backward finalises them in one of its reduction launches)
-  if (d.plain) return backward_plain<P>(d, prm, pk, L, M, B, grad, krow, ksteps, Kft, s);
+  if (d.plain) return backward_plain<P>(d, prm, pk, L, M, B, grad, krow, ksteps, Kft, s, drop);
   backward_layered<P>(d, prm, pk, L, M, B, grad, krow, ksteps, Kft, s);
 }
 
@@ -3630,6 +3644,134 @@ int dppo_rlpd_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, 
 #define CALL(P)                                                                                                                    \
   rlpd_actor_impl<P>(*actor, *q, E, actor_params, (const char*)actor_packed, q_params, q_packed, *cfg, *batch, obs_dim, N, noise,   \
                      alpha, actor_grad, stats, d_a, logp_out, actions_out, workspace, workspace_bytes, (hipStream_t)stream)
+  return DPPO_DISPATCH(prec, CALL);
+#undef CALL
+}
+
+// IBRL's actor loss through the ensemble's min (ibrl.h).  The actor is the plain fixed-std trunk with dropout; the members, their
+// forwards and their chains are RLPD's.  What differs from rlpd_actor_impl: the head (no log-probability, no second output half),
+// the choice per row between the forwards and the chains, the tail without 1/E, and the dropout steps of the actor's backward.
+template <class P>
+struct IbrlActorWs : QChainWs<P> {
+  MlpBufs<P> A;
+  float *actions, *mu, *qmin;
+  float* dout32;  // bf16 only: [N][AF] the head's gradient before its rounding to elem
+  uint8_t* sel;
+  uint8_t* mask;  // [LA][N][H]: the dropout mask the forward used
+};
+template <class P>
+static size_t carve_ibrl_actor(Carver& c, const dppo_net_desc& a, const dppo_net_desc& q, int64_t N, int E, IbrlActorWs<P>& W) {
+  const int AF = a.out_dim;
+  carve_mlp<P>(c, a, N, true, true, W.A);
+  carve_q_chains<P>(c, q, AF, N, E, W);
+  W.actions = (float*)c.take((size_t)N * AF * 4);
+  W.mu = (float*)c.take((size_t)N * AF * 4);
+  W.qmin = (float*)c.take((size_t)N * 4);
+  W.dout32 = P::ESIZE == 4 ? nullptr : (float*)c.take((size_t)N * AF * 4);
+  W.sel = (uint8_t*)c.take((size_t)N);
+  W.mask = (uint8_t*)c.take((size_t)(a.n_blocks + 1) * N * a.hidden);
+  return al256(c.off);
+}
+static int check_ibrl_actor_nets(const dppo_net_desc* actor, const dppo_net_desc* q, int obs_dim, int E) {
+  if (!actor || !q) return fail(-1, "null pointer: descriptor");
+  if (int e = check_ibrl_act_nets(actor, q, E)) return e;
+  if (actor->cond_dim != obs_dim)
+    return fail(-1, "actor / Q descriptors do not pair: actor cond_dim=%d against obs_dim=%d", actor->cond_dim, obs_dim);
+  return 0;
+}
+int64_t dppo_ibrl_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E) {
+  if (check_ibrl_actor_nets(actor, q, obs_dim, E) || check_prec(prec)) return -1;
+  if (int e = check_rows(N)) return e;
+  return ws_bytes(prec, [&](Carver& c, auto p) {
+    IbrlActorWs<decltype(p)> W;
+    return carve_ibrl_actor<decltype(p)>(c, *actor, *q, N, E, W);
+  });
+}
+template <class P>
+static int ibrl_actor_impl(const dppo_net_desc& a, const dppo_net_desc& q, int E, const float* ap, const char* ak, const float* qp,
+                           const void* const* qk, const dppo_gaussian_cfg& cfg, const dppo_dropout* drop, const dppo_idql_batch& b,
+                           int OD, int64_t N, const float* noise, float* grad, double* stats, float* d_a, float* actions_out,
+                           float* qmin_out, uint8_t* sel_out, void* ws, int64_t wsb, hipStream_t s) {
+  IbrlActorWs<P> W;
+  if (int e = carve_ws(ws, wsb, [&](Carver& c) { return carve_ibrl_actor<P>(c, a, q, N, E, W); })) return e;
+  const int64_t q_stride = W.Q[1].out - W.Q[0].out;
+  for (int e = 1; e < E; ++e)
+    if (W.Q[e].out - W.Q[0].out != e * q_stride) return fail(-1, "members' workspaces are not evenly spaced");
+  const PackLayout LA = pack_layout<P>(a, 0), LQ = pack_layout<P>(q, 0);
+  const ParamLayout plq = param_layout(q);
+  const int AF = a.out_dim, H = q.hidden;
+  // the actor's rows [obs | 0], the members' W0 action columns, the actor's forward with dropout: the mask it used is kept
+  IdqlRows r = idql_rows_of(b, N, OD, AF);
+  r.vin = W.A.in, r.KpV = LA.Kp0;
+  launch_idql_rows<P>(r, s);
+  launch_pack_w0a<P>(qp, plq.total, plq.W0, q.in_dim, OD, AF, H, E, W.w0a, s);
+  const bool dropping = drop != nullptr && (drop->p > 0.f || drop->mask != nullptr);
+  dppo_dropout dl;
+  memset(&dl, 0, sizeof(dl));
+  if (dropping) {
+    dl = *drop;
+    if (dl.mask_out == nullptr) dl.mask_out = W.mask;
+  }
+  mlp_forward<P>(a, ap, ak, LA, N, W.A, true, s, nullptr, false, dropping ? &dl : nullptr);
+  IbrlHead h;
+  memset(&h, 0, sizeof(h));
+  h.cfg = cfg, h.ring = idql_rows_of(b, N, OD, AF), h.out = W.A.out, h.ldo = W.A.ldout, h.noise = noise;
+  h.actions = actions_out != nullptr ? actions_out : W.actions, h.mu = W.mu, h.qin = W.Q[0].in, h.Kp = LQ.Kp0;
+  launch_ibrl_head<P>(h, s);
+  for (int e = 1; e < E; ++e) W.Q[e].in = W.Q[0].in;
+  // the members' forwards on the caller's stream and the three side streams; the choice needs all of them
+  hipStream_t st[4] = {s, fork_side(s, 0), fork_side(s, 1), fork_side(s, 2)};
+  for (int e = 0; e < E; ++e) mlp_forward<P>(q, qp + e * plq.total, (const char*)qk[e], LQ, N, W.Q[e], true, st[e & 3]);
+  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
+  IbrlMin mn;
+  memset(&mn, 0, sizeof(mn));
+  mn.q = W.Q[0].out, mn.q_stride = q_stride, mn.ldq = W.Q[0].ldout, mn.E = E, mn.N = N, mn.H = H, mn.act = q.act;
+  for (int e = 0; e < E; ++e)
+    mn.wout[e] = (const char*)qk[e] + LQ.Wout, mn.z[e] = W.Q[e].z1[q.n_blocks - 1], mn.dz[e] = W.dza[e];
+  mn.qmin = qmin_out != nullptr ? qmin_out : W.qmin, mn.sel = sel_out != nullptr ? sel_out : W.sel;
+  launch_ibrl_min<P>(mn, s);
+  // every member's chain from its seed (zero on the rows it did not win), on the same streams
+  for (int i = 1; i < 4; ++i) st[i] = fork_side(s, i - 1);
+  for (int e = 0; e < E; ++e)
+    q_chain_from_seed<P>(q, qp + e * plq.total, (const char*)qk[e], LQ, N, W.Q[e], W.dza[e], W.dzb[e],
+                         (char*)W.dhcat + (size_t)e * H * P::ESIZE, E * H, st[e & 3]);
+  for (int i = 1; i < 4; ++i) join_side(s, st[i], i - 1);
+  IbrlTail tl;
+  memset(&tl, 0, sizeof(tl));
+  tl.dh = W.dhcat, tl.wa = W.w0a, tl.K = E * H, tl.AF = AF, tl.tanh_mean = cfg.tanh_mean, tl.N = N, tl.mu = W.mu;
+  tl.d_out = W.A.d_out, tl.ldd = LA.Kpo, tl.d_out32 = W.dout32, tl.d_a = d_a;
+  launch_ibrl_tail<P>(tl, s);
+  IbrlActorStats sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.qmin = mn.qmin, sa.q = W.Q[0].out, sa.q_stride = q_stride, sa.ldq = W.Q[0].ldout, sa.E = E, sa.N = N, sa.stats = stats;
+  launch_ibrl_actor_stats(sa, s);
+  DropBwd db;
+  memset(&db, 0, sizeof(db));
+  if (dropping) db.mask = dl.mask_out, db.scale = 1.f / (1.f - dl.p);
+  mlp_backward<P>(a, ap, ak, LA, N, W.A, grad, nullptr, nullptr, 0, s, nullptr, dropping ? &db : nullptr);
+  if (W.dout32 != nullptr)  // the out bias again, from the unrounded rows
+    launch_colsum<F32>(W.dout32, (int)N, AF, AF, W.A.part, REDUCE_BLOCKS, grad + param_layout(a).bout, 1.f, s);
+  return check_launch();
+}
+int dppo_ibrl_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int E, const float* actor_params,
+                            const void* actor_packed, const float* q_params, const void* const* q_packed,
+                            const dppo_gaussian_cfg* cfg, const dppo_dropout* drop, const dppo_idql_batch* batch, int obs_dim,
+                            int64_t N, const float* noise, float* actor_grad, double* stats, float* d_a, float* actions_out,
+                            float* qmin_out, uint8_t* sel_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream) {
+  if (int e = check_ibrl_actor_nets(actor, q, obs_dim, E)) return e;
+  if (int e = check_prec(prec)) return e;
+  if (int e = check_gauss(actor, cfg, nullptr)) return e;
+  if (cfg->std_mode != 0) return fail(-1, "IBRL's actor has a fixed std (std_mode 0): a learned std is not built here");
+  if (cfg->deterministic) return fail(-1, "the actor loss samples: deterministic must be 0");
+  if (drop)
+    if (int e = check_dropout(drop)) return e;
+  if (!actor_params || !actor_packed || !q_params || !q_packed || !actor_grad || !stats || !workspace) return fail(-1, "null pointer");
+  if (int e = check_member_images(q_packed, E)) return e;
+  if (int e = check_rows(N)) return e;
+  if (int e = check_idql_batch(batch, N, RING_OBS)) return e;
+#define CALL(P)                                                                                                                       \
+  ibrl_actor_impl<P>(*actor, *q, E, actor_params, (const char*)actor_packed, q_params, q_packed, *cfg, drop, *batch, obs_dim, N, noise, \
+                     actor_grad, stats, d_a, actions_out, qmin_out, sel_out, workspace, workspace_bytes, (hipStream_t)stream)
   return DPPO_DISPATCH(prec, CALL);
 #undef CALL
 }

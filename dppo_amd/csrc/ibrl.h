@@ -37,8 +37,33 @@
 // Launches of dppo_ibrl_q_loss_fwd_bwd with L hidden layers per member (read off the code, not traced), side-stream events aside:
 //   1 row builder + 2 target forwards x (2 L + 1) + E forwards x (2 L + 1) + 2 (target, its share) + 3 (loss, statistics, out-layer
 //   bias gradients) + E backwards as in rlpd.h.  That is dppo_rlpd_q_loss_fwd_bwd's list plus two.
-// Not built: loss_actor (the min over E members, the backward through dropout, a fixed-std tanh-mean head backward), a member-batched
-// GEMM.
+//
+// The actor's loss through the ensemble's MIN (gaussian_ibrl.py:115-128 on GaussianModel.forward, model/common/gaussian.py:85-120).
+//   mu = tanh(trunk(obs)) (tanh_mean),  a = mu + sigma clamp(eps, +-c)  (sigma = fixed_std; the reference clamps the sample between
+//   bounds that move with mu, so d a / d mu = 1 on every element),  q_e = member_e(obs, a),  m_n = min_e q_e,  loss = -mean_n m_n.
+// The min is torch.min's: a NaN Q is the row's min, and A TIE GOES TO THE LOWEST MEMBER INDEX (torch's CPU kernel does the same;
+// the reference has no rule of its own).  Only the selected member's dq/da reaches the actor:  d_a = -g / N,  d_u = d_a (1 - mu^2).
+// Route (dppo_ibrl_actor_fwd_bwd, the driver beside rlpd_actor_impl):
+//   the actor's rows and its forward with the activations kept and dropout live; the mask used goes into the workspace (or the
+//   caller's mask_out), so the backward reads the forward's own mask whether it was given or drawn;
+//   ibrl_head_kernel: tanh mean, clipped draw, sample, the mean kept, and the ONE critic row image [obs | a | 0];
+//   the E members' LayerNorm forwards on the rotating streams; ibrl_min_kernel: per row the argmin, qmin, sel and every member's
+//   chain seed Wout (.) act'(z_L), zeroed on the rows it did not win; q_chain_from_seed per member into its columns of [N][E H] (a zero
+//   row stays exactly zero through LayerNorm's backward and the data GEMMs, so the tail's sum over K = E H is the selected member's
+//   product plus exact zeros); pack_w0a_kernel; ibrl_tail_kernel (rlpd_tail_kernel's 16-lane split of K and xor butterfly, no 1/E)
+//   whose epilogue is the head's backward with single-width d_out; ibrl_actor_stats_kernel through sac_tree's fixed order; then the
+//   actor's parameter backward, where drop_bwd_kernel turns d/dz' into d/dz = d/dz' keep s in place in front of each hidden
+//   layer's weight gradient, column sum and next data GEMM.  The mask is applied explicitly: act'(0) is 0 for ReLU, not for Mish.
+//   In bf16 drop_bwd_kernel reads the elem rows the data GEMMs wrote and rounds keep s once more (exact at p = 0.5, where s = 2).
+//   Measured at p = 0.25 against the same rows kept in fp32: the worst tensor stays at 1.15 x the bf16-Linear yardstick
+//   and 1 - cosine moves from 1.21 x to 1.24 x, against a bound of 2 x, so the fp32 rows the critics' LayerNorm backward needs are
+//   not carved here.  The out bias is redone from the unrounded d_out as in sac.h.
+// Launches with LA hidden layers in the actor and LQ in a member (read off the code, not traced), side-stream events aside:
+//   1 row builder + 1 W0 pack + LA x (1 GEMM + 1 dropout row kernel) + 1 GEMM + 1 head + E x [LQ x (1 GEMM + 1 row kernel) + 1 GEMM]
+//   + 1 min/select + E x [LQ LayerNorm backwards + (LQ - 1) data GEMMs] + 1 tail + 1 statistics + the actor's backward with LA
+//   dropout backward row kernels (bf16: + 2 for the out bias).  Shipped can (LA = LQ = 3, E = 5): 2 + 7 + 1 + 35 + 1 + 25 + 2 = 73
+//   before the actor's backward.  A chain that runs only where a member has rows was not tried.
+// Not built: the dropout BC pre-training, a member-batched GEMM, graph capture of the iteration, pixel observations.
 #pragma once
 #include "rlpd.h"
 
@@ -106,5 +131,77 @@ struct IbrlSelect {
   uint8_t* took_bc;          // [N]
 };
 void launch_ibrl_select(const IbrlSelect& a, hipStream_t s);
+
+// ---- the actor's loss through the ensemble's min ------------------------------------------------------------------------------------
+// d/dz' -> d/dz of one hidden layer of a dropout trunk, in place: dz[m][h] = keep ? dz[m][h] * scale : 0 (one wave per row, as DropRows)
+struct DropBwd {
+  void* dz;           // [M][ld] elem, in and out
+  int ld;
+  int64_t M;
+  int H, layer;
+  float scale;
+  const uint8_t* mask;  // [L][M][H], 1 = keep
+};
+template <class P>
+void launch_drop_bwd(const DropBwd& a, hipStream_t s);
+
+// One thread per 16-byte chunk of the critic's row image [obs | a | 0]; the thread that owns an action column forms it:
+//   mu = tanh_mean ? tanh(out) : out,  a = mu + fixed_std * clamp(z, +-randn_clip),  z given or Philox keyed by the cfg at n AF + j
+struct IbrlHead {
+  dppo_gaussian_cfg cfg;
+  IdqlRows ring;     // where obs comes from; N, OD, AD = AF
+  const float* out;  // [N][ldo] the trunk's output
+  int ldo;
+  const float* noise;   // [N][AF] or null
+  float *actions, *mu;  // [N][AF] each
+  void* qin;            // [N][Kp] elem
+  int Kp;
+};
+template <class P>
+void launch_ibrl_head(const IbrlHead& a, hipStream_t s);
+
+// Per row (one wave): sel = argmin_e q_e (a NaN is the min; a tie goes to the lowest index), qmin, and member e's chain seed
+// dz_e[n][h] = elem(wout_e[h] * act'(z_e[n][h])) where e == sel, 0 elsewhere
+struct IbrlMin {
+  const float* q;    // member e's Q: column 0 of [N][ldq] at q + e * q_stride
+  int64_t q_stride;  // floats
+  int ldq, E;
+  const void* wout[RLPD_MAX_E];  // [H] elem
+  const void* z[RLPD_MAX_E];     // [N][H] elem: the last hidden layer's z
+  void* dz[RLPD_MAX_E];          // [N][H] elem
+  int64_t N;
+  int H, act;
+  float* qmin;   // [N]
+  uint8_t* sel;  // [N]
+};
+template <class P>
+void launch_ibrl_min(const IbrlMin& a, hipStream_t s);
+
+// g[n][j] = sum_k dh[n][k] wa[j][k] (RlpdTail's split of K = E H and butterfly; no 1/E: the seeds carry the choice), then
+//   d_a = -g / N,  d_out[n][j] = d_a (1 - mu^2) (tanh_mean) or d_a;  columns [AF, ldd) zeroed
+struct IbrlTail {
+  const void* dh;  // [N][K] elem
+  const void* wa;  // [AF][K] elem
+  int K, AF, tanh_mean;
+  int64_t N;
+  const float* mu;  // [N][AF]
+  void* d_out;      // [N][ldd] elem
+  int ldd;
+  float* d_out32;  // [N][AF] fp32 or null: the same before its rounding to elem
+  float* d_a;      // [N][AF] or null
+};
+template <class P>
+void launch_ibrl_tail(const IbrlTail& a, hipStream_t s);
+
+// stats = {-mean qmin, mean qmin, mean over rows and members of q}: rows in double per thread, then sac_tree's fixed order
+struct IbrlActorStats {
+  const float* qmin;
+  const float* q;
+  int64_t q_stride;
+  int ldq, E;
+  int64_t N;
+  double* stats;
+};
+void launch_ibrl_actor_stats(const IbrlActorStats& a, hipStream_t s);
 
 }  // namespace dppo

@@ -47,6 +47,29 @@
 
 namespace dppo {
 
+// four consecutive elements of a row as fp32 and back (8 or 16 bytes): the row kernels of this family (ibrl.hip's too)
+template <class P>
+__device__ __forceinline__ void load4(const typename P::elem_t* p, float (&v)[4]) {
+  if constexpr (P::ESIZE == 4) {
+    const float4 t = *(const float4*)p;
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+    const u32x2 t = *(const u32x2*)p;
+    v[0] = bf2f(t.x & 0xffff), v[1] = bf2f(t.x >> 16), v[2] = bf2f(t.y & 0xffff), v[3] = bf2f(t.y >> 16);
+  }
+}
+template <class P>
+__device__ __forceinline__ void store4(typename P::elem_t* p, const float (&v)[4]) {
+  if constexpr (P::ESIZE == 4) {
+    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    u32x2 pk;
+    pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
+    pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+    *(u32x2*)p = pk;
+  }
+}
+
 constexpr float PLAIN_LN_EPS = 1e-5f;  // nn.LayerNorm's default
 constexpr int LN_ROWS_PB = 4;          // rows per 256-thread block: one wave per row
 

@@ -249,6 +249,10 @@ SYMBOLS = {
     "dppo_ibrl_q_loss_workspace_bytes": (_L, [_ND, _I, _I, _L, _I]),
     "dppo_ibrl_q_loss_fwd_bwd": (_I, [_ND, _I, _I, _P, C.POINTER(C.c_void_p), _P, C.POINTER(C.c_void_p), _I, _I, C.POINTER(IdqlBatch), _I,
                                       _P, _P, _L, _D, _P, _P, _P, _P, _P, _L, _P]),
+    # ... and the actor loss through the min of the members' Q, backwards through the actor's dropout
+    "dppo_ibrl_actor_workspace_bytes": (_L, [_ND, _ND, _I, _I, _L, _I]),
+    "dppo_ibrl_actor_fwd_bwd": (_I, [_ND, _ND, _I, _I, _P, _P, _P, C.POINTER(C.c_void_p), C.POINTER(GaussianCfg), C.POINTER(Dropout),
+                                     C.POINTER(IdqlBatch), _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     # the *_obs entries: pre-gathered mode only (no `inds`), + dppo_obs_io* / d_obs
     "dppo_ppo_loss_fwd_bwd_obs": (_I, [_ND, _ND, _I, _P, _P, _P, _P, C.POINTER(DiffusionCfg), C.POINTER(PpoCfg), _P,
                                        _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, C.POINTER(ObsIO)]),

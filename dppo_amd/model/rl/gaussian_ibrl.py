@@ -22,8 +22,13 @@ Deviations from the reference, documented and not imitated:
   * the soft choice draws one uniform ``u`` per row and takes BC iff ``u < p_bc`` with ``p_bc = 1 / (1 + exp(w_rl - w_bc))`` in
     fp32, where the reference hands the softmax of the two weights to ``torch.multinomial``: the same distribution, other draws.
 
-``loss_actor`` (the min over E members, the backward through dropout) is the follow-up and raises, as do ``TrainIBRLAgent`` and the
-dropout BC pre-training, which do not exist yet."""
+``loss_actor`` is one call as well (``dppo_ibrl_actor_fwd_bwd``): the online actor's forward with dropout, the fixed-std head with its
+tanh mean, all E members' forwards, the min per row (a tie goes to the lowest member index), every member's action-gradient chain
+from a seed that is zero on the rows it did not win, one tail over E * hidden, the head's backward and the actor's backward through
+its dropout masks.  It runs on the GPU only.  ``TrainIBRLAgent`` (agent/finetune/train_ibrl_agent.py) drives the three.
+
+Not built: the dropout BC pre-training (``pre_gaussian_mlp_ibrl``; ``GaussianModel.loss`` refuses the plain fixed-std actor), pixel
+observations."""
 from __future__ import annotations
 
 import copy
@@ -35,6 +40,7 @@ from dppo_amd import hip
 from dppo_amd.model.common import off_policy
 from dppo_amd.model.common.ensemble import EnsembleCritics
 from dppo_amd.model.common.gaussian import GaussianModel
+from dppo_amd.model.diffusion.diffusion import _FusedDenoiseLoss, flat_views
 
 
 class IBRL_Gaussian(EnsembleCritics, GaussianModel):
@@ -58,7 +64,7 @@ class IBRL_Gaussian(EnsembleCritics, GaussianModel):
         for p in self.bc_policy.parameters():
             p.requires_grad = False
         self._init_ensemble(critic, n_critics)
-        for name in ("_ws_act", "_ws_q"):
+        for name in ("_ws_act", "_ws_q", "_ws_actor"):
             object.__setattr__(self, name, hip.Workspace())
 
     def update_target_actor(self, tau):
@@ -162,6 +168,45 @@ class IBRL_Gaussian(EnsembleCritics, GaussianModel):
             stats.data_ptr(), y.data_ptr(), share.data_ptr(), ws.data_ptr(), ws.numel(), hip.stream()), "dppo_ibrl_q_loss_fwd_bwd")
         return self._td_tail(stats, grads, (p0, p1), last_y=y, last_bc_share=share)
 
-    def loss_actor(self, obs):
-        raise NotImplementedError("dppo_amd: IBRL's actor loss (the min over the E members, the backward through dropout and the "
-                                  "fixed-std tanh-mean head) is the follow-up to this model; it is not built")
+    def loss_actor(self, obs, inds=None, *, noise=None, mask=None, want_mask=False):
+        """-mean_n min_e q_e(s_n, a_n) on the online actor's reparameterised sample a = mu + fixed_std clamp(eps) (reference
+        :115-128), and d loss / d actor parameters in ``last_loss_grad``: through the selected member alone, the tanh mean and the
+        actor's dropout (live iff ``network.training`` and its ``dropout`` > 0).  The min is torch.min's: a tie goes to the lowest
+        member index.  No member's gradient is touched.  ``noise`` (N, Ta, Da) and ``mask`` (L, N, H) uint8 replace the draws.
+        ``last_stats``: {loss, mean of the min q, mean over rows and members of q}; ``last_d_a`` (N, Ta*Da) = d loss / d a;
+        ``last_actions`` (N, Ta*Da); ``last_qmin`` (N,); ``last_sel`` (N,) bytes: the selected member; ``last_drop_mask`` (L, N, H)
+        the mask used where ``want_mask`` asks for it and dropout is live, else None (the backward reads the workspace's copy).
+        ``obs`` may be a ``DeviceReplay`` (rows ``inds``)."""
+        net, q = self.network, self.critic_networks[0]
+        if not next(net.parameters()).is_cuda:
+            raise NotImplementedError("dppo_amd: IBRL's actor loss runs on the GPU only; a CPU path would be a follow-up and is "
+                                      "not built")
+        batch, N, keep = off_policy.as_batch("IBRL", obs, inds)
+        dev = net.flat_params().device
+        AF = self.horizon_steps * net.action_dim
+        cfg = net.gaussian_cfg(deterministic=False, randn_clip=self.randn_clip_value)
+        if noise is None:
+            cfg.seed_lo, cfg.seed_hi = self._seed()
+        else:
+            noise = noise.reshape(N, AF).contiguous().float()
+        drop, keep_m, mask_out = self._dropout_of(net, N, dev, mask, want_mask=want_mask)
+        lib, da, dq, E = hip.load(), net.net_desc(), q.net_desc(), self.n_critics
+        OD = q.cond_dim
+        ws = self._ws_actor.get(lib.dppo_ibrl_actor_workspace_bytes(C.byref(da), C.byref(dq), self.prec, OD, N, E), dev,
+                                "dppo_ibrl_actor_workspace_bytes")
+        qk, keep_q = self._ens.images(self.prec)
+        grad = torch.empty_like(net.flat_params())
+        stats = torch.empty(hip.IDQL_STAT_COUNT, dtype=torch.float64, device=dev)
+        d_a, actions = (torch.empty(N, AF, dtype=torch.float32, device=dev) for _ in range(2))
+        qmin = torch.empty(N, dtype=torch.float32, device=dev)
+        sel = torch.empty(N, dtype=torch.uint8, device=dev)
+        hip.check(lib.dppo_ibrl_actor_fwd_bwd(
+            C.byref(da), C.byref(dq), self.prec, E, net.flat_params().data_ptr(), net.packed(self.prec, 0).data_ptr(),
+            self.critic_flat_params().data_ptr(), qk, C.byref(cfg), C.byref(drop) if drop is not None else None, C.byref(batch), OD, N,
+            hip.ptr(noise), grad.data_ptr(), stats.data_ptr(), d_a.data_ptr(), actions.data_ptr(), qmin.data_ptr(), sel.data_ptr(),
+            ws.data_ptr(), ws.numel(), hip.stream()), "dppo_ibrl_actor_fwd_bwd")
+        for name, v in (("last_loss_grad", grad), ("last_stats", stats), ("last_d_a", d_a), ("last_actions", actions),
+                        ("last_qmin", qmin), ("last_sel", sel), ("last_drop_mask", mask_out)):
+            object.__setattr__(self, name, v)
+        params = net.trunk_parameters()
+        return _FusedDenoiseLoss.apply(stats[0], flat_views(grad, params), *params)

@@ -41,6 +41,29 @@ class DeviceReplay:
             dst[slot].copy_(torch.as_tensor(np.asarray(src) if not torch.is_tensor(src) else src).reshape(dst[slot].shape),
                             non_blocking=True)
 
+    def extend(self, prev_obs, next_obs, action, reward, terminated) -> None:
+        """T env steps at once, each argument with a leading dimension T: what T calls of ``append`` in that order leave behind,
+        wrap-around and eviction included (``deque.extend``), in one indexed copy per array.  A subclass with an ``append`` of its
+        own is fed step by step."""
+        srcs = [torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x) for x in (prev_obs, next_obs, action, reward, terminated)]
+        T = int(srcs[0].shape[0])
+        if type(self).append is not DeviceReplay.append:
+            for t in range(T):
+                self.append(*[x[t] for x in srcs])
+            return
+        if T == 0:
+            return
+        first = (self.head + self.steps) % self.cap  # where the first new step goes, full or not
+        live = min(T, self.cap)                      # only the last ``cap`` new steps survive
+        slots = ((first + torch.arange(T - live, T)) % self.cap).to(self.obs.device)
+        for dst, src in zip((self.obs, self.next_obs, self.actions, self.reward, self.terminated), srcs):
+            rows = src[T - live:].reshape(live, *dst.shape[1:]).to(device=dst.device, dtype=dst.dtype, non_blocking=True)
+            dst.index_copy_(0, slots, rows)
+        total = self.steps + T
+        if total > self.cap:
+            self.head = (self.head + total - self.cap) % self.cap
+        self.steps = min(total, self.cap)
+
     def slot_of(self, inds: torch.Tensor) -> torch.Tensor:
         """Storage row (slot * n_envs + e) of each logical index: the mapping the row builder applies on the device."""
         s, e = torch.div(inds, self.n_envs, rounding_mode="floor"), inds % self.n_envs

@@ -1083,6 +1083,23 @@ int dppo_ibrl_q_loss_fwd_bwd(const dppo_net_desc* q, int prec, int E, const floa
                              const dppo_idql_batch* batch, int obs_dim, const float* next_actions_bc, const float* next_actions_rl,
                              int64_t N, double gamma, float* q_grad, double* stats, float* y_out, double* bc_share, void* workspace,
                              int64_t workspace_bytes, dppo_stream_t stream);
+/* IBRL_Gaussian.loss_actor (reference :115-128) = -mean_n min_e q_e(obs_n, a_n) with a_n = mu_n + fixed_std * clamp(eps_n, +-randn_clip),
+ * mu_n = tanh(trunk(obs_n)) where cfg->tanh_mean (d a / d mu = 1 on every element, clamped or not).  actor: the plain fixed-std trunk
+ * dppo_ibrl_act accepts (out_dim = Ta*Da), cfg its dppo_gaussian_cfg (std_mode 0 and deterministic 0, anything else is refused); drop
+ * or NULL: dropout in its trunk, forward AND backward (d/dz = d/dz' * keep * 1/(1 - p), the mask applied explicitly); the mask used
+ * goes to drop->mask_out where that is given.  q, q_params [E][P], q_packed[E]: the ensemble dppo_ibrl_q_loss_fwd_bwd trains, 2 <= E
+ * <= 16; batch / obs_dim / N as dppo_rlpd_actor_fwd_bwd's (obs alone is read); noise (N, Ta*Da) or NULL: Philox keyed by the cfg's
+ * seed, as dppo_gaussian_sample keys it.  The min is torch.min's: a NaN Q is the row's min, and a TIE GOES TO THE LOWEST MEMBER INDEX.
+ * Only the selected member's dq/da reaches the actor.  actor_grad <- d loss / d actor params (flat, OVERWRITTEN); stats[3] <- {loss,
+ * mean of the min q, mean over rows and members of q} (device doubles, fixed summation order).  Optional (NULL): d_a (N, Ta*Da) =
+ * -g / N, actions_out (N, Ta*Da), qmin_out (N,), sel_out (N,) bytes: the selected member.  A row's outputs depend on that row alone
+ * and are the same bits in every call.  No weight gradient, column sum or gradient buffer of any member is written. */
+int64_t dppo_ibrl_actor_workspace_bytes(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int obs_dim, int64_t N, int E);
+int dppo_ibrl_actor_fwd_bwd(const dppo_net_desc* actor, const dppo_net_desc* q, int prec, int E, const float* actor_params,
+                            const void* actor_packed, const float* q_params, const void* const* q_packed,
+                            const dppo_gaussian_cfg* cfg, const dppo_dropout* drop, const dppo_idql_batch* batch, int obs_dim,
+                            int64_t N, const float* noise, float* actor_grad, double* stats, float* d_a, float* actions_out,
+                            float* qmin_out, uint8_t* sel_out, void* workspace, int64_t workspace_bytes, dppo_stream_t stream);
 
 #ifdef __cplusplus
 }

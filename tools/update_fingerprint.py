@@ -266,6 +266,15 @@ def ibrl_q_case(case, n, prec):
     return out
 
 
+def ibrl_actor_case(case, n, prec):
+    from tests import test_ibrl_actor as B
+    m = B.make_model(case, prec, DEV)
+    res = B.run_actor(m, B.dev_inputs(case, n))
+    out = {k: sha(v) for k, v in res.items() if v is not None}
+    out["workspace_bytes"] = m._ws_actor.buf.numel()
+    return out
+
+
 def ln_family_cases(table, prec):
     for case, n in (("tiny", 77), ("chunk", 77)):  # chunk_77: RLPD's case without the entropy backup
         table[f"rlpd_q/{case}_{n}/{prec}"] = lambda c=case, k=n: rlpd_q_case(c, k, prec)
@@ -276,6 +285,7 @@ def ln_family_cases(table, prec):
         for soft in (False, True):
             table[f"ibrl_act/{case}_{n}_{'soft' if soft else 'greedy'}/{prec}"] = lambda c=case, k=n, s=soft: ibrl_act_case(c, k, s, prec)
         table[f"ibrl_q/{case}_{n}/{prec}"] = lambda c=case, k=n: ibrl_q_case(c, k, prec)
+        table[f"ibrl_actor/{case}_{n}/{prec}"] = lambda c=case, k=n: ibrl_actor_case(c, k, prec)
 
 
 # The plain twin-Q family (QSM, DQL, SAC): as above, one fresh model per case and every tensor the entry writes.
